@@ -1,6 +1,17 @@
 """bench.py -- throughput of the Mean-Teacher training step on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload unet3d|unet2d|vnet|swin|cross|...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up, warm up, time EXACTLY K steps, write the last
+timed step's outputs if ``--dump-outputs DIR`` is given, print the line.  ``--full`` adds everything listed below the
+contract fields (roofline, others, cpu_baseline, host enqueue, the distributed checks and exchange prices); the
+``--no-*`` options trim a ``--full`` run.
+
+``--dump-outputs DIR`` (rank 0): after the timed steps, ``DIR/<name>.npy`` for the step's scalar buffer(s) (losses),
+every network's flat parameters and module buffers and the students' last flat gradient -- float32 (buffers float64),
+at most 64 MB, a fixed seeded sample of an array that does not fit.  Inputs, weights and dropout are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 ``--gpus N`` with N > 1 is self-launching: when the process was not started by ``torch.distributed.run``
 (no ``WORLD_SIZE`` in the environment) it re-executes itself as
@@ -16,7 +27,8 @@ Default workload = BASELINE.json configs[2], the north-star target: Mean-Teacher
 2 classes, 4 labeled + 4 unlabeled volumes per GPU.  Pure data parallel: every rank owns its own 4+4 shard -> weak
 scaling; value = samples of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = the
+max-over-ranks milliseconds of one timed step), ``outputs`` (what --dump-outputs wrote), and with --full
   roofline     live HIP-event timing of the dominant kernel: achieved / frac = the flops the matrix pipe EXECUTES over the
                launches' summed duration against that pipe's peak (<= 1): fp32 MFMA 157.3 TF with Winograd launches at 1 / 3.375
                (1 / 2.25) of their direct-convolution count; the Linear GEMMs / window attention of SwinUnet in their bf16x3 form
@@ -34,8 +46,9 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                SAME batch as the GPU line: thread count swept over {16, 32, 64} on a reduced batch, then 2 warm-up + 5 timed
                steps of the full batch at the best count, median (rank 0, N=1 only)
   host_enqueue_ms_per_step   the host time to ENQUEUE one step into an empty queue (median of 5 single steps, device idle before each)
-  distributed  world size seen, per-rank times, ``affinity_rank0`` (NUMA pinning, N > 1), ``predicted`` = a MODEL of the gradient
-               exchange (mis_hip/dist.py::predict_exchange; at N = 1 for 8 GPUs), and at N > 1 the measured exchange figures
+  distributed  (world size seen, per-rank times and ``affinity_rank0`` (NUMA pinning, N > 1) in every run) ``predicted`` = a MODEL
+               of the gradient exchange (mis_hip/dist.py::predict_exchange; at N = 1 for 8 GPUs), and at N > 1 the bit check of
+               the ranks' weights and the measured exchange figures
 """
 import argparse
 import json
@@ -251,8 +264,11 @@ class _StubTrainer:
         return dict(loss=float(self.w.abs().mean()))
 
 
-def run_workload(name, args, rank, world, kernel_events=True):
-    """Warm-up, then EXACTLY args.steps timed steps between barrier + device sync; returns (rank 0) the result dict."""
+def run_workload(name, args, rank, world, kernel_events=True, full=False, dump_dir=None):
+    """Warm-up, then EXACTLY args.steps timed steps between barrier + device sync; returns (rank 0) the result dict.
+    ``full``: also the diagnostic regions behind the timed steps (LDS poisoning in front of the warm-up, host enqueue of
+    single steps, the data-parallel checks at N > 1, and -- with ``kernel_events`` -- the serial roofline region).
+    ``dump_dir``: rank 0 writes what the last timed step computed there (dump_outputs)."""
     import torch
     import torch.distributed as tdist
     stub = args.stub
@@ -289,7 +305,7 @@ def run_workload(name, args, rank, world, kernel_events=True):
         sync()
         return time.perf_counter() - t0
 
-    if not stub:
+    if not stub and full:
         # once per run, in front of the warm-up: NaNs into every CU's LDS (the test suite's fixture, tests/conftest.py) -- a kernel
         # that reads an LDS cell it never wrote shows up as non-finite losses here instead of depending on the previous process
         from mis_hip import lib as _lib
@@ -307,11 +323,15 @@ def run_workload(name, args, rank, world, kernel_events=True):
         tr.step(vol, lab)
     dt_local = timed(args.steps)
     host_loop_ms = enqueue[-1][0] / enqueue[-1][1] * 1e3
+    # what the last timed step computed, before any region behind it changes the weights
+    dumped = None
+    if dump_dir is not None and rank == 0:
+        dumped = dump_outputs(tr, dump_dir)
     # the host's own cost of enqueueing ONE step: into an empty queue (device idle), median of 5.  The loop figure above is
     # not that once the host is faster than the device: the runtime's queues fill up and the loop waits for the device in them
     # (20 steps of ~600 launches), i.e. it converges to the device time
-    host_enqueue_ms = host_loop_ms
-    if not stub and not pmc_child:
+    host_enqueue_ms = host_loop_ms if (stub or pmc_child) else None
+    if not stub and not pmc_child and full:
         one = []
         for _ in range(5):
             sync()
@@ -329,15 +349,15 @@ def run_workload(name, args, rank, world, kernel_events=True):
         dt = max(per_rank)                         # MAX over ranks
 
     # ---- data parallel: prove the exchange happened and price it (before any diagnostic region changes the weights)
-    dist_info = None
-    if _dist_on(world):
+    dist_info = dict(world_size_seen=tdist.get_world_size()) if _dist_on(world) else None
+    if _dist_on(world) and full:
         dist_info = _distributed_checks(tr, timed, args, rank, world, dev, stub, dt_local, retape=lambda: _retape(tr, vol, lab))
 
     # ---- roofline region: the same step with the side streams off, every MFMA launch bracketed by HIP events on its
     # launch stream.  A launch's duration measures the kernel only when it has the chip to itself: in the timed region
     # above the teacher forward and the weight gradients run on side streams beside the main stream's launches.
     prof, serial_dt, serial_steps = None, None, 0
-    if not stub and kernel_events:
+    if not stub and kernel_events and full:
         from mis_hip import ops, plan as _plan, step as _stepmod
         keep = (_stepmod.TWO_STREAM, _plan.WGRAD_STREAM, getattr(tr, "use_tape", False))
         _stepmod.TWO_STREAM, _plan.WGRAD_STREAM = False, False
@@ -459,7 +479,8 @@ def run_workload(name, args, rank, world, kernel_events=True):
                                   (getattr(tr, a, None) for a in ("model", "model1", "model2")) if m is not None]
     res = dict(value=round(shape[0] * world * args.steps / dt, 3), unit=UNIT.get(name, "images/s"), grad_bytes=grad_bytes,
                ms_per_step=round(step_s * 1e3, 3), step_flop_frac=round(step_frac, 4),
-               host_enqueue_ms_per_step=round(host_enqueue_ms, 3), host_enqueue_loop_ms_per_step=round(host_loop_ms, 3),
+               host_enqueue_ms_per_step=None if host_enqueue_ms is None else round(host_enqueue_ms, 3),
+               host_enqueue_loop_ms_per_step=round(host_loop_ms, 3), outputs=dumped,
                step_enqueue=("launch tape: the recorded C-ABI launch sequence of one eager step, replayed (%d entries; "
                              "MIS_STEP_TAPE=0: the eager op graph)" % len(tr._tape)) if getattr(tr, "_tape", None) is not None
                else "eager op graph",
@@ -470,6 +491,52 @@ def run_workload(name, args, rank, world, kernel_events=True):
     if not stub:
         torch.cuda.empty_cache()
     return res
+
+
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: all arrays together stay below 64 MB (npy headers included)
+
+
+def _step_outputs(tr):
+    """What a caller of the timed step holds after it, in a fixed order: the step's device scalar buffer(s) (losses and
+    schedule weights, ``trainer.losses()``), and per network its flat parameters, the module buffers (BatchNorm running
+    statistics, as float64) and -- for the students -- the flat gradient of the last step."""
+    import torch
+    if isinstance(tr, _StubTrainer):
+        return [("w", tr.w), ("g", tr.g)]
+    arrays = [(a, getattr(tr, a)) for a in ("out", "out1", "out2") if isinstance(getattr(tr, a, None), torch.Tensor)]
+    for a in ("model", "model1", "model2", "ema_model"):
+        m = getattr(tr, a, None)
+        if m is None:
+            continue
+        arrays.append((f"{a}_params", m.flat_param))
+        if a != "ema_model":
+            arrays.append((f"{a}_grad", m.flat_grad))
+        bufs = [b.detach().reshape(-1).double() for _, b in m.named_buffers()]
+        if bufs:
+            arrays.append((f"{a}_buffers", torch.cat(bufs)))
+    return arrays
+
+
+def dump_outputs(tr, out_dir, budget=DUMP_BUDGET_BYTES):
+    """``--dump-outputs DIR``: the arrays of _step_outputs as ``DIR/<name>.npy`` (float32; buffers float64).  The smallest
+    arrays are written whole; one larger than its share of the budget left is replaced by a fixed sample of its elements
+    (legacy NumPy RandomState seeded 1337, indices ascending), the same for every run of the same workload."""
+    import numpy as np
+    arrays = [(n, t.detach().reshape(-1).cpu().numpy()) for n, t in _step_outputs(tr)]
+    os.makedirs(out_dir, exist_ok=True)
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i][1].nbytes)
+    left, info = budget, {}
+    for k, i in enumerate(order):
+        name, a = arrays[i]
+        total = a.size
+        share = left // (len(order) - k)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            a = a[np.sort(np.random.RandomState(1337).choice(total, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+        info[name] = dict(dtype=str(a.dtype), elements=int(a.size), of=int(total))
+    return dict(dir=os.path.abspath(out_dir), arrays={n: info[n] for n, _ in arrays})
 
 
 def _retape(tr, vol, lab):
@@ -768,6 +835,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="unet3d", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: LDS poisoning, host enqueue, roofline region, PMC traffic, the "
+                         "'others' block, CPU baselines and (N>1) the data-parallel checks; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB; rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-others", action="store_true", help="skip the 'others' block (the other single-GPU configs)")
     ap.add_argument("--no-kernel-events", action="store_true", help="skip the per-launch HIP events")
@@ -821,14 +893,16 @@ def main():
         two_stream, wgrad_stream = _step.TWO_STREAM, _plan.WGRAD_STREAM
 
     wl = WORKLOADS[args.workload]
+    full = args.full
+    headline = dict(kernel_events=not args.no_kernel_events, full=full, dump_dir=args.dump_outputs)
     try:
         if os.environ.get("MIS_MAIN_PRIORITY") and not args.stub:
             # experiment: the whole workload on a stream of this HIP priority (the side streams keep the default one)
             import torch as _t
             with _t.cuda.stream(_t.cuda.Stream(priority=int(os.environ["MIS_MAIN_PRIORITY"]))):
-                res = run_workload(args.workload, args, rank, world, kernel_events=not args.no_kernel_events)
+                res = run_workload(args.workload, args, rank, world, **headline)
         else:
-            res = run_workload(args.workload, args, rank, world, kernel_events=not args.no_kernel_events)
+            res = run_workload(args.workload, args, rank, world, **headline)
     except BaseException as e:
         if _dist_on(world) and rank == 0 and "MIS_BENCH_LAUNCHED" not in os.environ:
             print(json.dumps({"metric": "training images-or-volumes/sec/node (Mean-Teacher step)", "value": None,
@@ -852,9 +926,10 @@ def main():
                        "step_enqueue": res.get("step_enqueue", "eager op graph")},
             "distributed": dict(res["distributed"] or {"world_size_seen": 1}, backend=backend,
                                 per_rank_ms_per_step=res["per_rank_ms_per_step"], max_ms_per_step=res["ms_per_step"],
-                                affinity_rank0=affinity, predicted=_predicted_exchange(res, world)),
+                                affinity_rank0=affinity, predicted=_predicted_exchange(res, world) if full else None),
             "host_enqueue_ms_per_step": res["host_enqueue_ms_per_step"],
-            "host_enqueue_frac": round(res["host_enqueue_ms_per_step"] / res["ms_per_step"], 3),
+            "host_enqueue_frac": None if res["host_enqueue_ms_per_step"] is None else
+            round(res["host_enqueue_ms_per_step"] / res["ms_per_step"], 3),
             "host_enqueue_note": "one step into an empty queue (median of 5); host_enqueue_loop_ms_per_step = the timed loop's own "
                                  "enqueue time per step, which includes waiting in full queues once the host outruns the device",
             "host_enqueue_loop_ms_per_step": res.get("host_enqueue_loop_ms_per_step"),
@@ -871,14 +946,16 @@ def main():
                 "mis_gemm_set_split_precision(0) / MIS_GEMM_BF3=0 selects the fp32 MFMA)")
         if args.stub:
             out["data"] = "stub (CPU/gloo launcher test, not a measurement)"
+        if res["outputs"] is not None:
+            out["outputs"] = res["outputs"]
     mark("setup_and_headline")
-    if not _dist_on(world) and not args.stub and not args.no_others and args.workload == "unet3d":
+    if full and not _dist_on(world) and not args.stub and not args.no_others and args.workload == "unet3d":
         # the other single-GPU configurations of BASELINE.json, shorter runs of the same protocol
         import copy
         oargs = copy.copy(args)      # the same protocol as the headline workload (a short warm-up leaves first-launch costs in the timed steps)
         others = {}
         for name in OTHERS:
-            r = run_workload(name, oargs, rank, world, kernel_events=not args.no_kernel_events)
+            r = run_workload(name, oargs, rank, world, kernel_events=not args.no_kernel_events, full=True)
             rf = r["roofline"] or {}
             extra = {}
             if name in ("swin", "cross"):
@@ -887,7 +964,7 @@ def main():
                 from mis_hip import tops as _tops
                 prev = _tops.set_split_precision(0)
                 try:
-                    r32 = run_workload(name, oargs, rank, world, kernel_events=False)
+                    r32 = run_workload(name, oargs, rank, world, kernel_events=False, full=True)
                 finally:
                     _tops.set_split_precision(prev)
                 extra = dict(linear_gemm_arithmetic="bf16x3: every fp32 operand cut exactly into three bf16 pieces, six piece "
@@ -913,13 +990,13 @@ def main():
                                 dominant_kernel_algorithmic_tflops=rf.get("algorithmic_tflops"))
         out["others"] = others
         mark("others")
-    if _dist_on(world) and not args.no_others and args.workload == "unet3d":
+    if full and _dist_on(world) and not args.no_others and args.workload == "unet3d":
         # config 5 (cross teaching, the BASELINE configuration that is DEFINED on 8 GPUs: 16+16 images per GPU) behind the
         # default workload: two students, two gradient bucketers, the second student's backward on a side stream
         import copy
         oargs = copy.copy(args)
         oargs.steps, oargs.warmup = max(5, args.steps // 2), min(args.warmup, 2)
-        r = run_workload("cross", oargs, rank, world, kernel_events=False)
+        r = run_workload("cross", oargs, rank, world, kernel_events=False, full=True)
         if rank == 0:
             out["others"] = {"cross": dict(workload=WORKLOADS["cross"]["config"], value=r["value"], unit=r["unit"],
                                            ms_per_step=r["ms_per_step"], steps=oargs.steps, n_gpus=world,
@@ -929,7 +1006,7 @@ def main():
                                                             predicted=_predicted_exchange(r, world)))}
     if rank == 0:
         single = not _dist_on(world) and not args.stub
-        if single and not args.no_traffic and not args.no_kernel_events and out["roofline"]:
+        if full and single and not args.no_traffic and not args.no_kernel_events and out["roofline"]:
             # HBM bytes of the dominant kernel from the PMC counters, collected by re-executing this command (before the
             # CPU baseline occupies the host's cores)
             torch.cuda.synchronize()
@@ -940,7 +1017,7 @@ def main():
             if tr is None:
                 rf["traffic_unavailable"] = why
             mark("traffic")
-        if single and not args.no_cpu_baseline and wl["cpu_sample"] is not None:
+        if full and single and not args.no_cpu_baseline and wl["cpu_sample"] is not None:
             # one budget for the CPU legs of the line (MIS_BENCH_CPU_BUDGET_S, default 170 s; 120 of them for the headline workload)
             cpu_t0 = time.perf_counter()
             cpu_budget = float(os.environ.get("MIS_BENCH_CPU_BUDGET_S", "170"))
@@ -957,7 +1034,8 @@ def main():
                 o2["cpu_baseline"] = cpu_baseline("unet2d", WORKLOADS["unet2d"], budget_s=60.0, deadline=cpu_t0 + cpu_budget)
                 o2["gpu_over_cpu"] = round(o2["value"] / o2["cpu_baseline"]["value"], 2)
         if single:
-            mark("cpu_baseline")
+            if full:
+                mark("cpu_baseline")
             out["timing_s"] = {b[0]: round(b[1] - a[1], 1) for a, b in zip(marks, marks[1:])}
             out["timing_s"]["total"] = round(marks[-1][1] - marks[0][1], 1)
         print(json.dumps(out), flush=True)

@@ -12,11 +12,11 @@ tag=${1:-r05}
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"
+python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 for w in unet2d vnet uamt3d swin cross cross224 cnnvit unetr swinunetr; do
-    python bench.py --workload $w --no-cpu-baseline > "$out/bench_$w.json" 2> "$out/bench_$w.err"
+    python bench.py --full --workload $w --no-cpu-baseline > "$out/bench_$w.json" 2> "$out/bench_$w.err"
 done
-python bench.py --serial --no-cpu-baseline --no-others > "$out/bench_unet3d_serial.json" 2> "$out/bench_unet3d_serial.err"
+python bench.py --full --serial --no-cpu-baseline --no-others > "$out/bench_unet3d_serial.json" 2> "$out/bench_unet3d_serial.err"
 for w in unet3d unet2d vnet swin; do
     rocprofv3 --kernel-trace --stats -d "$out/prof_$w" -o "$w" --output-format csv -- \
         python bench.py --workload $w --serial --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-kernel-events > "$out/prof_$w.log" 2>&1

@@ -6,11 +6,11 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 for w in swin cross cross224 cnnvit unetr; do
-    python bench.py --workload $w --no-cpu-baseline > "$out/bench_$w.json" 2> "$out/bench_$w.err"
+    python bench.py --full --workload $w --no-cpu-baseline > "$out/bench_$w.json" 2> "$out/bench_$w.err"
 done
-MIS_STEP_TAPE=0 python bench.py --workload swin --no-cpu-baseline > "$out/bench_swin_eager.json" 2> "$out/bench_swin_eager.err"
-MIS_BENCH_GRAPH=1 python bench.py --workload swin --no-cpu-baseline > "$out/bench_swin_hipgraph.json" 2> "$out/bench_swin_hipgraph.err"
-MIS_GEMM_REGA=0 python bench.py --workload swin --no-cpu-baseline > "$out/bench_swin_norega.json" 2> "$out/bench_swin_norega.err"
+MIS_STEP_TAPE=0 python bench.py --full --workload swin --no-cpu-baseline > "$out/bench_swin_eager.json" 2> "$out/bench_swin_eager.err"
+MIS_BENCH_GRAPH=1 python bench.py --full --workload swin --no-cpu-baseline > "$out/bench_swin_hipgraph.json" 2> "$out/bench_swin_hipgraph.err"
+MIS_GEMM_REGA=0 python bench.py --full --workload swin --no-cpu-baseline > "$out/bench_swin_norega.json" 2> "$out/bench_swin_norega.err"
 for w in unet3d swin cross; do
     rocprofv3 --kernel-trace --stats -d "$out/prof_$w" -o "$w" --output-format csv -- \
         python bench.py --workload $w --serial --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-kernel-events --no-traffic > "$out/prof_$w.log" 2>&1

@@ -23,7 +23,7 @@ def _run(extra, env_extra=None):
 
 @pytest.mark.timeout(900)
 def test_self_launch_world2_gloo():
-    out = _run(["--gpus", "2"])
+    out = _run(["--gpus", "2", "--full"])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1
     assert out["distributed"]["world_size_seen"] == 2 and out["distributed"]["backend"] == "gloo"
     per = out["distributed"]["per_rank_ms_per_step"]
@@ -46,7 +46,7 @@ def test_missing_gradient_exchange_fails_the_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MIS_STUB_SKIP_SYNC"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--steps", "3", "--warmup", "1",
-                        "--gpus", "2"], capture_output=True, text=True, timeout=600, env=env)
+                        "--gpus", "2", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode != 0 and "data-parallel check FAILED" in (p.stderr + p.stdout)
     # a failed multi-process run still prints ONE JSON line: the status, the ranks' stderr tail, RCCL's warnings (none over gloo)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -87,3 +87,49 @@ def test_cpu_baseline_gives_up_steps_before_its_deadline_not_the_protocol_silent
         assert late["full_batch_at_other_thread_count"] is None and "1 warm-up + 3 timed" in late["sample"]
     finally:
         torch.set_num_threads(threads)
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line carries the headline figure only; --dump-outputs writes the stub step's arrays, identical for
+    two runs with the same arguments."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        out = _run(["--dump-outputs", str(tmp_path / d)])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in out
+        assert out["roofline"] is None
+        assert "others" not in out and "cpu_baseline" not in out and out["distributed"]["predicted"] is None
+        assert set(out["outputs"]["arrays"]) == {"w", "g"}
+        runs.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("w", "g")})
+    for n, a in runs[0].items():
+        assert a.dtype == np.float32 and a.size == 1 << 14 and np.array_equal(a, runs[1][n])
+    assert np.abs(runs[0]["w"]).sum() > 0
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_budget(tmp_path):
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    tr = bench._StubTrainer(None)
+    tr.w.copy_(torch.arange(tr.w.numel(), dtype=torch.float32))
+    tr.g.fill_(2.0)
+    got = []
+    for d in ("a", "b"):
+        info = bench.dump_outputs(tr, str(tmp_path / d), budget=40000)
+        assert info["arrays"]["w"]["of"] == 1 << 14 and info["arrays"]["w"]["elements"] < 1 << 14
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 40000 + 2 * 256
+        got.append(np.load(tmp_path / d / "w.npy"))
+    w = got[0]
+    assert w.dtype == np.float32 and np.array_equal(w, got[1])
+    assert np.all(np.diff(w) > 0) and w.min() >= 0 and w.max() < 1 << 14     # ascending distinct elements of w

@@ -211,7 +211,7 @@ def test_bench_multi_gpu_code_path_on_a_single_rank_rccl_group():
     env.update(MIS_BENCH_DIST_AT_WORLD1="1", MIS_FORCE_BUCKETER="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--no-kernel-events"], capture_output=True, text=True, timeout=1100, env=env)
+                        "--full", "--no-kernel-events"], capture_output=True, text=True, timeout=1100, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout

@@ -67,7 +67,14 @@ def test_oracle_reproduces_reference_goldens(name):
         lg = r["logits"].double().flatten()
         np.testing.assert_allclose(lg[_sample_idx(lg.numel())].numpy(), z[pre + "logits_samples"], rtol=0, atol=2e-5)
         gn = np.array([float(r["grads"][n].double().norm()) for n in pnames])
-        np.testing.assert_allclose(gn, z[pre + "grad_norms"], rtol=1e-3, atol=1e-6 * z[pre + "grad_norms"].max())
+        # a conv bias in front of a normalisation has a zero gradient (float64: ~1e-15); its fp32 norm in the golden is the
+        # reference's rounding noise, which depends on the CPU's summation order (thread count, ISA).  For those tensors --
+        # float64 norm below the reference's own fp32 error -- the oracle must be within that error of the golden
+        ref, ref64 = z[pre + "grad_norms"], z[pre + "grad_norms64"]
+        floor = np.where(ref64 < np.abs(ref - ref64), np.abs(ref - ref64), 0.0)
+        tol = 1e-3 * ref + np.maximum(1e-6 * ref.max(), floor)
+        bad = np.abs(gn - ref) > tol
+        assert not bad.any(), [(n, a, b, t) for n, a, b, t, f in zip(pnames, gn, ref, tol, bad) if f]
         sabs = np.array([float(student[n].double().abs().sum()) for n in pnames])
         np.testing.assert_allclose(sabs, z[pre + "student_abssum"], rtol=1e-5, atol=1e-6)
         tabs = np.array([float(teacher[n].double().abs().sum()) for n in pnames])
