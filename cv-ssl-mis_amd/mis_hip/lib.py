@@ -121,6 +121,11 @@ PROTOTYPES = {
     "mis_uamt_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
     "mis_uamt_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_ll, c_d, c_f,
                             c_p, c_p, c_ll, c_p, c_ll, c_p]),
+    "mis_beta_sample": (c_i, [c_p, c_i, c_d, c_u, c_p, c_p]),
+    "mis_ict_mix": (c_i, [c_p, c_p, c_p, c_i, c_i, c_ll, c_p]),
+    "mis_ict_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
+    "mis_ict_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_f, c_p, c_p,
+                           c_ll, c_p, c_ll, c_p]),
     "mis_cross_pseudo_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_i, c_p, c_p, c_ll,
                                     c_p, c_ll, c_p]),
     "mis_cross_pseudo_mt_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_f, c_p,

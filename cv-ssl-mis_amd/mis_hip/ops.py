@@ -752,6 +752,57 @@ def uamt_tail(student, teacher, mean_probs, label, labeled_bs, out, max_iteratio
                              _l.stream_ptr()), "mis_uamt_tail")
 
 
+ICT_BETA_SALT = 0x1C7BE7A0
+
+
+def beta_sample(lam, alpha, state, salt=ICT_BETA_SALT):
+    """lam[m] ~ Beta(alpha, alpha) on the device, keyed by (seed, iter_num) of ``state`` and ``salt`` (ICT mix factors,
+    reference np.random.beta(ict_alpha, ict_alpha, size=(L // 2, 1, 1, 1)))."""
+    L = _l.load()
+    _l.require_gpu(lam, state)
+    assert lam.dtype == torch.float32 and lam.is_contiguous() and lam.numel() > 0
+    if not float(alpha) > 0.0:
+        raise ValueError(f"Beta(alpha, alpha) needs alpha > 0, got {alpha}")
+    _l.check(L.mis_beta_sample(_l.ptr(lam), lam.numel(), float(alpha), int(salt) & 0xFFFFFFFF, _l.ptr(state),
+                               _l.stream_ptr()), "mis_beta_sample")
+
+
+def ict_mix(x, lam, labeled_bs, out):
+    """out[:L] = x[:L]; out[L + m] = x[L + m] * (1 - lam[m]) + x[L + M + m] * lam[m] with M = lam.numel() and
+    x.shape[0] == L + 2M (ICT input of the student, bit-identical to the torch expression)."""
+    L = _l.load()
+    _l.require_gpu(x, lam, out)
+    M = lam.numel()
+    assert x.dtype == out.dtype == lam.dtype == torch.float32
+    assert x.is_contiguous() and out.is_contiguous() and lam.is_contiguous()
+    assert x.shape[0] == labeled_bs + 2 * M and out.shape[0] == labeled_bs + M
+    assert tuple(x.shape[1:]) == tuple(out.shape[1:])
+    n = x[0].numel()
+    _l.check(L.mis_ict_mix(_l.ptr(x), _l.ptr(out), _l.ptr(lam), labeled_bs, M, n, _l.stream_ptr()), "mis_ict_mix")
+
+
+def ict_tail(student, teacher0, teacher1, lam, label, labeled_bs, out, dlogits=None, cons_weight=0.0, state=None,
+             loss_scale=1.0):
+    """ICT loss tail: 0.5*(CE+Dice) on student[:L] + w * mean((softmax(student[L:]) - target)^2), target =
+    softmax(teacher0) * (1 - lam) + softmax(teacher1) * lam.  ``out`` (>= 5+C floats): the layout of loss_tail."""
+    L = _l.load()
+    B, C, D, H, W, S, sbs = _geom(student)
+    M = B - labeled_bs
+    B0, C0, _, _, _, S0, t0bs = _geom(teacher0)
+    B1, C1, _, _, _, S1, t1bs = _geom(teacher1)
+    assert B0 == B1 == M and C0 == C1 == C and S0 == S1 == S
+    _l.require_gpu(lam, label)
+    assert lam.dtype == torch.float32 and lam.is_contiguous() and lam.numel() == M
+    assert label.is_contiguous() and label.dtype in (torch.uint8, torch.int64) and label.numel() >= labeled_bs * S
+    lb = 1 if label.dtype == torch.uint8 else 8
+    dbs = _geom(dlogits)[6] if dlogits is not None else 0
+    ws = scratch(L.mis_ict_tail_workspace_bytes(B, C, S), "tail")
+    _l.check(L.mis_ict_tail(_l.ptr(student), sbs, _l.ptr(teacher0), t0bs, _l.ptr(teacher1), t1bs, _l.ptr(lam),
+                            _l.ptr(label), lb, labeled_bs, M, C, S, cons_weight, _l.ptr(state), loss_scale,
+                            _l.ptr(out), _l.ptr(dlogits), dbs, _l.ptr(ws), ws.numel(), _l.stream_ptr()),
+             "mis_ict_tail")
+
+
 def cross_teaching_tail(own, other, label, labeled_bs, out, dlogits=None, cons_weight=0.0, state=None,
                         pseudo_ce=False, teacher=None, mt_weight=0.0):
     """0.5*(CE+Dice) on the labeled half + w * Dice (``pseudo_ce``: cross-entropy, CPS) against the other network's

@@ -1030,12 +1030,14 @@ class HipNet(nn.Module):
         return mod._buffers[leaf]
 
     # ---- plans ----
-    def plan_for(self, shape5):
-        key = tuple(shape5)
+    def plan_for(self, shape5, slot=0):
+        """``slot`` > 0: a second static plan for the same input shape (its own activation and output buffers), for a
+        network that runs twice per step on inputs of one shape and whose first output is still read afterwards."""
+        key = tuple(shape5) if not slot else (tuple(shape5), int(slot))
         plan = self._plans.get(key)
         if plan is None:
             self._check_alias()
-            plan = self._new_plan(key)
+            plan = self._new_plan(tuple(shape5))
             self._build(plan)
             self._plans[key] = plan
         return plan
@@ -1070,11 +1072,11 @@ class HipNet(nn.Module):
             yield name, flat[off:off + n].view(shape)
 
     # raw (autograd-free) interface used by the fused training step
-    def forward_raw(self, x, no_backward=False):
+    def forward_raw(self, x, no_backward=False, slot=0):
         """``no_backward``: nobody will differentiate this pass (the EMA teacher, validation): ops may skip what only a
-        backward reads -- backward_raw() after such a pass fails loudly."""
+        backward reads -- backward_raw() after such a pass fails loudly.  ``slot``: see plan_for."""
         x5 = self._as5(x.contiguous())
-        plan = self.plan_for(x5.shape)
+        plan = self.plan_for(x5.shape, slot)
         ctx = self._ctx()
         ctx.no_backward = bool(no_backward)
         out = plan.forward(x5, ctx)

@@ -275,6 +275,105 @@ class UAMTTrainer(MeanTeacherTrainer):
         return d
 
 
+def ict_split(batch_size, labeled_bs):
+    """M = labeled_bs // 2, the number of mixed samples of an ICT step.  The reference splits the unlabeled part
+    volume[L:] at M into x0 and x1 and broadcasts [M]-shaped factors over both, which only works when the batch holds
+    exactly L + 2M samples (train_interpolation_consistency_training_2D.py:156-165): anything else is a ValueError."""
+    B, L = int(batch_size), int(labeled_bs)
+    if L < 2:
+        raise ValueError(f"ICT needs labeled_bs >= 2 (labeled_bs // 2 mixed samples); got labeled_bs={L}")
+    M = L // 2
+    if B - L != 2 * M:
+        raise ValueError(f"ICT needs batch_size - labeled_bs == 2 * (labeled_bs // 2) = {2 * M} unlabeled samples; "
+                         f"got batch_size={B}, labeled_bs={L}")
+    return M
+
+
+class ICTTrainer(MeanTeacherTrainer):
+    """Interpolation Consistency Training (reference code/train_interpolation_consistency_training_2D.py:150-190,
+    _3D.py:140-182, _2D_ViT.py:190-235).  With L = labeled_bs and M = L // 2 the unlabeled samples x0 = volume[L:L+M]
+    and x1 = volume[L+M:] are mixed with per-sample factors lam ~ Beta(ict_alpha, ict_alpha) drawn on the device; the
+    student sees cat([volume[:L], x0 * (1 - lam) + x1 * lam]) (L + M samples) and is pulled towards
+    softmax(T(x0)) * (1 - lam) + softmax(T(x1)) * lam.  The teacher runs two train-mode forwards (BatchNorm running
+    statistics updated twice per step), with no input noise.  SGD, poly LR, EMA and the consistency ramp are those of
+    the Mean-Teacher step; there is no ``iter_num < 1000`` gate."""
+
+    TEACHER_STREAMS = (2, 3)        # Philox dropout sub-streams of the two teacher passes (the student's is 1)
+
+    def __init__(self, model, ema_model, *, ict_alpha=0.2, **kw):
+        if not float(ict_alpha) > 0.0:
+            raise ValueError(f"ict_alpha must be > 0, got {ict_alpha}")
+        kw.pop("use_graph", None)   # replays go through the launch tape
+        kw.setdefault("cons_start_iter", 0)
+        super().__init__(model, ema_model, **kw)
+        self.ict_alpha = float(ict_alpha)
+        self.mix_factors = None     # [M] device tensor: the factors of the last step
+        self._mix_in = None
+
+    def _run(self, volume, label, mix_factors):
+        L = self.labeled_bs
+        M = ict_split(volume.shape[0], L)
+        if self.mix_factors is None or self.mix_factors.numel() != M:
+            self.mix_factors = torch.empty(M, dtype=torch.float32, device=volume.device)
+        if mix_factors is None:
+            ops.beta_sample(self.mix_factors, self.ict_alpha, self.state)
+        else:
+            self.mix_factors.copy_(mix_factors.reshape(-1))        # injected factors: parity tests only
+        shape = (L + M,) + tuple(volume.shape[1:])
+        if self._mix_in is None or tuple(self._mix_in.shape) != shape:
+            self._mix_in = torch.empty(shape, dtype=volume.dtype, device=volume.device)
+        ops.ict_mix(volume, self.mix_factors, L, self._mix_in)
+        x0, x1 = volume[L:L + M], volume[L + M:]
+        ema = self.ema_model
+
+        def teacher_passes():
+            # two forwards of one shape: the second uses a second plan so that the first one's logits survive it
+            ema.rng_stream = self.TEACHER_STREAMS[0]
+            t0 = ema.forward_raw(x0, no_backward=True)
+            ema.rng_stream = self.TEACHER_STREAMS[1]
+            t1 = ema.forward_raw(x1, no_backward=True, slot=1)
+            ema.rng_stream = self.TEACHER_STREAMS[0]
+            return t0, t1
+
+        if TWO_STREAM:
+            # the teacher passes read only the raw batch: they run on a side stream beside the student's forward
+            main = torch.cuda.current_stream()
+            if self._side is None:
+                self._side = _lib.side_stream("side")
+            _lib.wait_stream(self._side, main)
+            with torch.cuda.stream(self._side):
+                t0, t1 = teacher_passes()
+            s_logits = self.model.forward_raw(self._mix_in)
+            _lib.wait_stream(main, self._side)
+        else:
+            s_logits = self.model.forward_raw(self._mix_in)
+            t0, t1 = teacher_passes()
+        ops.ict_tail(s_logits, t0, t1, self.mix_factors, label[:L].contiguous(), L, self.out,
+                     dlogits=self.model.logits_grad_buffer(), state=self.state)
+        grad_scale = backward_and_sync(self.model, self.pg, self._bucketer)   # the step's only exchange
+        ops.sgd_ema_step(self.model.flat_param, self.model.flat_grad, self.momentum_buf,
+                         self.ema_model.flat_param, momentum=self.momentum, weight_decay=self.weight_decay,
+                         grad_scale=grad_scale, state=self.state)
+        h = self.hyper
+        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
+                         h["rampup"], h["ramp_div"], h["cons_start_iter"])
+
+    def step(self, volume_batch, label_batch, mix_factors=None):
+        """One ICT iteration on device tensors; ``mix_factors`` ([M] or [M,1,1,1(,1)]) replaces the device Beta draw
+        (parity tests).  Returns the device scalar buffer of MeanTeacherTrainer.step (no host sync)."""
+        M = ict_split(volume_batch.shape[0], self.labeled_bs)
+        if mix_factors is not None and mix_factors.numel() != M:
+            raise ValueError(f"mix_factors must hold labeled_bs // 2 = {M} values, got {mix_factors.numel()}")
+        if not self.model.training or not self.ema_model.training:
+            raise RuntimeError("ICT runs both networks in train mode (the reference never calls ema_model.eval())")
+        if self.use_tape and mix_factors is None:
+            self._tape_step(lambda v, l: self._run(v, l, None), (volume_batch, label_batch))
+        else:
+            self._run(volume_batch, label_batch, mix_factors)
+        self.iter_num += 1
+        return self.out
+
+
 class CrossTeachingTrainer(_TapedStep):
     """Cross teaching between a CNN and a Transformer (reference
     code/train_cross_teaching_between_cnn_transformer_2D.py:216-263): two students see the whole batch, each is

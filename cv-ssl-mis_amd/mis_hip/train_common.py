@@ -79,10 +79,12 @@ def make_loader(args, label_dtype, rank, world=1):
         from dataloaders.brats2019 import (BraTS2019, DeviceTwoStreamLoader3D, DeviceVolumePool, RandomRotFlipCrop,
                                            TwoStreamBatchSampler)
         db_train = BraTS2019(base_dir=args.root_path, split='train', num=None)
-        check_shards(args.labeled_num, len(db_train) - args.labeled_num, args.labeled_bs,
+        # train_interpolation_consistency_training_3D.py:114-115 bounds the unlabeled pool by --total_labeled_num
+        n_pool = min(len(db_train), getattr(args, "total_labeled_num", None) or len(db_train))
+        check_shards(args.labeled_num, n_pool - args.labeled_num, args.labeled_bs,
                      args.batch_size - args.labeled_bs, world)
         labeled = list(range(0, args.labeled_num))[rank::world]           # train_mean_teacher_3D.py:109-112;
-        unlabeled = list(range(args.labeled_num, len(db_train)))[rank::world]   # disjoint shard per rank (SURVEY s.8e)
+        unlabeled = list(range(args.labeled_num, n_pool))[rank::world]   # disjoint shard per rank (SURVEY s.8e)
         sampler = TwoStreamBatchSampler(labeled, unlabeled, args.batch_size, args.batch_size - args.labeled_bs)
         loader = DeviceTwoStreamLoader3D(DeviceVolumePool.from_dataset(db_train), sampler,
                                          RandomRotFlipCrop(args.patch_size), label_dtype=label_dtype)
@@ -430,9 +432,11 @@ def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=
 
 
 def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, log_every=1, trainer_cls=None,
-                 snapshot_fmt="../model/{}_{}_labeled/{}"):
+                 snapshot_fmt="../model/{}_{}_labeled/{}", trainer_kw=None):
     """Hot loop of train_mean_teacher_2D.py:196-312 / train_mean_teacher_3D.py:128-230 (and, with
-    ``trainer_cls=UAMTTrainer``, of train_uncertainty_aware_mean_teacher_{2D,3D}.py)."""
+    ``trainer_cls=UAMTTrainer``, of train_uncertainty_aware_mean_teacher_{2D,3D}.py; with ``trainer_cls=ICTTrainer``
+    and ``trainer_kw=dict(ict_alpha=...)``, of train_interpolation_consistency_training_{2D,3D,2D_ViT}.py).
+    ``trainer_kw``: extra keyword arguments of the trainer class."""
     from .step import MeanTeacherTrainer
     if trainer_cls is not None:
         MeanTeacherTrainer = trainer_cls
@@ -455,7 +459,8 @@ def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, lo
                                  cons_start_iter=cons_start_iter, seed=args.seed + rank,
                                  # captured replay of a step that contains an RCCL collective is not verified on
                                  # hardware: --hip_graph is honoured for single-GPU runs only
-                                 use_graph=bool(getattr(args, "hip_graph", 0)) and world == 1)
+                                 use_graph=bool(getattr(args, "hip_graph", 0)) and world == 1,
+                                 **(trainer_kw or {}))
     if rank == 0 and getattr(args, "hip_graph", 0) and world > 1:
         logging.info("--hip_graph ignored for world_size %d (single-GPU only)" % world)
     loader, source = make_loader(args, label_dtype, rank, world)

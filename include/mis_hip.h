@@ -353,6 +353,25 @@ int mis_uamt_tail(const float* student, long long s_bs, const float* teacher, lo
                   float loss_scale, float* out, float* dlogits, long long d_bs, void* workspace,
                   long long workspace_bytes, mis_stream_t stream);
 
+/* Interpolation Consistency Training (code/train_interpolation_consistency_training_2D.py:157-188, _3D.py:146-177,
+ * _2D_ViT.py:198-229).
+ * mis_beta_sample: lam[m] ~ Beta(alpha, alpha), m < M, on the device (replaces np.random.beta(ict_alpha, ict_alpha,
+ *   size=(L//2, 1, 1, 1)), :157-160).  Marsaglia-Tsang gamma draws in the log domain on Philox4x32-10 keyed by
+ *   (state->seed, state->iter_num, salt); at most 64 attempts per draw.  Every value is in [0, 1].
+ * mis_ict_mix: out[:L] = x[:L]; out[L+m] = x[L+m] * (1 - lam[m]) + x[L+M+m] * lam[m] (the batch_ux_mixed / cat of
+ *   :161-169), n floats per sample, x holds L + 2M samples; bit-identical to the three rounded fp32 torch operations.
+ * mis_ict_tail: 0.5*(CE+Dice)(student[:L], label) + w * mean((softmax(student[L:]) - target)^2) over M*C*S values,
+ *   target = softmax(teacher0) * (1 - lam) + softmax(teacher1) * lam (:170-188); w = state->cons_weight (gated by
+ *   state->cons_gate) when `state` is given, else `cons_weight`.  out (>= 5+C floats): loss, loss_ce, loss_dice,
+ *   consistency_loss, consistency_weight, C class-wise dice.  dlogits = loss_scale * dloss/dstudent (may be NULL). */
+int mis_beta_sample(float* lam, int M, double alpha, unsigned salt, const MisStepState* state, mis_stream_t stream);
+int mis_ict_mix(const float* x, float* out, const float* lam, int L, int M, long long n, mis_stream_t stream);
+long long mis_ict_tail_workspace_bytes(int B, int C, long long S);
+int mis_ict_tail(const float* student, long long s_bs, const float* teacher0, long long t0_bs, const float* teacher1,
+                 long long t1_bs, const float* lam, const void* label, int label_bytes, int L, int M, int C,
+                 long long S, float cons_weight, const MisStepState* state, float loss_scale, float* out,
+                 float* dlogits, long long d_bs, void* workspace, long long workspace_bytes, mis_stream_t stream);
+
 /* ---- stand-alone loss operators (drop-in utils.losses surface) ----------------------------------------
  * reference: losses.DiceLoss code/utils/losses.py:165-201; losses.softmax_mse_loss :74-91.
  * mis_dice_loss_fwd: probs [B][C][S], label [B][S]; out[0] = loss, out[1+c] = class-wise dice; the
