@@ -126,6 +126,11 @@ PROTOTYPES = {
     "mis_ict_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
     "mis_ict_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_f, c_p, c_p,
                            c_ll, c_p, c_ll, c_p]),
+    "mis_rot90": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_i, c_p]),
+    "mis_dct_tail_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i, c_i]),
+    "mis_dct_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_i, c_f, c_f, c_p, c_p,
+                           c_ll, c_p, c_ll, c_p, c_ll, c_p]),
+    "mis_grad_combine": (c_i, [c_p, c_p, c_ll, c_i, c_p]),
     "mis_cross_pseudo_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_i, c_p, c_p, c_ll,
                                     c_p, c_ll, c_p]),
     "mis_cross_pseudo_mt_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_f, c_p,

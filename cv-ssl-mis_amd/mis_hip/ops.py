@@ -803,6 +803,65 @@ def ict_tail(student, teacher0, teacher1, lam, label, labeled_bs, out, dlogits=N
              "mis_ict_tail")
 
 
+def _sched_args(sched, k):
+    if sched is None:
+        if int(k) < 0:
+            raise ValueError("rotation k < 0 reads sched[state.iter_num]: a schedule and a step state are needed")
+        return None, 0
+    _l.require_gpu(sched)
+    assert sched.dtype == torch.int32 and sched.is_contiguous() and sched.numel() > 0
+    return _l.ptr(sched), sched.numel()
+
+
+def rot90(x, out, k=-1, sched=None, state=None):
+    """out = torch.rot90(x, k, [2, 3]) for x [N, C, H, W] (free batch stride, dense planes: e.g. ``volume[L:]``),
+    bit-identical.  ``k`` < 0: read on the device, ``sched[state.iter_num]`` (deep co-training's rotation per iteration)."""
+    L = _l.load()
+    _l.require_gpu(x, out, state)
+    if x.dim() != 4 or out.dim() != 4 or x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise RuntimeError(f"rot90 takes fp32 [N,C,H,W] tensors, got {tuple(x.shape)} / {tuple(out.shape)}")
+    N, C, H, W = x.shape
+    assert x[0].is_contiguous() and out.is_contiguous()
+    want = (N, C, W, H) if int(k) >= 0 and int(k) % 2 else (N, C, H, W)
+    if tuple(out.shape) != want:
+        raise RuntimeError(f"rot90: output {tuple(out.shape)}, expected {want}")
+    sp, ns = _sched_args(sched, k)
+    in_bs = x.stride(0) if N > 1 else C * H * W
+    _l.check(L.mis_rot90(_l.ptr(x), in_bs, _l.ptr(out), C * H * W, N, C, H, W, sp, ns, _l.ptr(state), int(k),
+                         _l.stream_ptr()), "mis_rot90")
+
+
+def dct_tail(logits_a, logits_r, label, labeled_bs, out, dA=None, dR=None, k=-1, sched=None, state=None,
+             cons_weight=0.0, loss_scale=1.0):
+    """Deep co-training loss tail over pass A (the batch, [L+U,C,1,H,W]) and pass R (the rotated unlabeled part,
+    [U,C,1,H,W]).  ``out`` (>= 6+C floats): [loss, loss_ce, loss_dice, consistency_loss, consistency_weight, k,
+    class-wise dice...]; ``dA`` / ``dR``: the logits gradients of both passes (both or neither)."""
+    L = _l.load()
+    B, C, D, H, W, S, abs_ = _geom(logits_a)
+    U, Cr, Dr, Hr, Wr, _, rbs = _geom(logits_r)
+    assert D == Dr == 1 and Cr == C and (Hr, Wr) == (H, W) and U == B - labeled_bs
+    _l.require_gpu(label, state)
+    assert label.is_contiguous() and label.dtype in (torch.uint8, torch.int64) and label.numel() >= labeled_bs * S
+    lb = 1 if label.dtype == torch.uint8 else 8
+    dabs = _geom(dA)[6] if dA is not None else 0
+    drbs = _geom(dR)[6] if dR is not None else 0
+    sp, ns = _sched_args(sched, k)
+    ws = scratch(L.mis_dct_tail_workspace_bytes(labeled_bs, U, C, H, W), "tail")
+    _l.check(L.mis_dct_tail(_l.ptr(logits_a), abs_, _l.ptr(logits_r), rbs, _l.ptr(label), lb, labeled_bs, U, C, H, W,
+                            sp, ns, _l.ptr(state), int(k), cons_weight, loss_scale, _l.ptr(out), _l.ptr(dA), dabs,
+                            _l.ptr(dR), drbs, _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_dct_tail")
+
+
+def grad_combine(dst, src, accumulate):
+    """dst = src, or dst += src with ``accumulate`` (flat gradient buffers; a launch, so it lands on a launch tape)."""
+    L = _l.load()
+    _l.require_gpu(dst, src)
+    assert dst.dtype == src.dtype == torch.float32 and dst.is_contiguous() and src.is_contiguous()
+    assert dst.numel() == src.numel()
+    _l.check(L.mis_grad_combine(_l.ptr(dst), _l.ptr(src), dst.numel(), int(bool(accumulate)), _l.stream_ptr()),
+             "mis_grad_combine")
+
+
 def cross_teaching_tail(own, other, label, labeled_bs, out, dlogits=None, cons_weight=0.0, state=None,
                         pseudo_ce=False, teacher=None, mt_weight=0.0):
     """0.5*(CE+Dice) on the labeled half + w * Dice (``pseudo_ce``: cross-entropy, CPS) against the other network's

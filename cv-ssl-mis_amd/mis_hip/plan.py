@@ -1083,8 +1083,24 @@ class HipNet(nn.Module):
         self._last = (plan, ctx)
         return out
 
-    def backward_raw(self, dlogits5=None, on_progress=None):
+    def last_pass(self):
+        """Handle of the last forward_raw pass, for ``backward_raw(pass_=h)`` / ``logits_grad_buffer(h)``: a network
+        differentiated through two live passes of one step (deep co-training) runs them on two plans (another input shape
+        or ``slot``) and backpropagates each by its handle.  A later forward on the same plan invalidates the handle."""
         plan, ctx = self._last
+        return plan, ctx, plan.generation
+
+    def _pass(self, pass_):
+        if pass_ is None:
+            return self._last
+        plan, ctx, generation = pass_
+        if plan.generation != generation:
+            raise RuntimeError(f"backward of a pass whose plan {plan.in_shape} ran another forward since (forward "
+                               f"#{generation}, now #{plan.generation}): its activations are gone")
+        return plan, ctx
+
+    def backward_raw(self, dlogits5=None, on_progress=None, pass_=None):
+        plan, ctx = self._pass(pass_)
         if getattr(ctx, "no_backward", False):
             raise RuntimeError("backward_raw() after forward_raw(no_backward=True): that pass did not keep its activations")
         if on_progress is None:
@@ -1092,8 +1108,8 @@ class HipNet(nn.Module):
         else:
             plan.backward(dlogits5, ctx, on_progress)
 
-    def logits_grad_buffer(self):
-        return self._last[0].out.grad()
+    def logits_grad_buffer(self, pass_=None):
+        return self._pass(pass_)[0].out.grad()
 
     # nn.Module surface: logits = model(x); loss.backward() works through _NetFn
     def forward(self, x):

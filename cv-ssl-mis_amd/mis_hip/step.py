@@ -15,6 +15,7 @@ hipGraph (``use_graph=True``) and replayed; the RNG offset, learning rate, EMA a
 consistency weight live in a device-resident ``MisStepState`` so replays stay correct.
 """
 import os
+import random
 
 import torch
 
@@ -372,6 +373,124 @@ class ICTTrainer(MeanTeacherTrainer):
             self._run(volume_batch, label_batch, mix_factors)
         self.iter_num += 1
         return self.out
+
+
+def rotation_schedule(seed, n):
+    """The rotation counts of the reference's deep co-training: ``random.seed(seed)`` in the main process, then one
+    ``random.randrange(0, 4)`` per iteration (code/train_deep_co_training_2D.py:141, :248).  Nothing else of that process
+    draws from ``random`` (the augmentation's draws run in the DataLoader workers), so entry i is iteration i's k."""
+    r = random.Random(seed)
+    return [r.randrange(0, 4) for _ in range(int(n))]
+
+
+def dct_split(batch_size, labeled_bs, patch_size=None):
+    """U = batch_size - labeled_bs, the unlabeled samples of a deep co-training step.  ValueError unless
+    1 <= labeled_bs < batch_size (CE / Dice need a labeled sample, the consistency mean an unlabeled one) and, when given,
+    the patch is square: an odd k turns H x W into W x H, and the step runs on static plans of one shape."""
+    B, L = int(batch_size), int(labeled_bs)
+    if not 1 <= L < B:
+        raise ValueError(f"deep co-training needs 1 <= labeled_bs < batch_size; got batch_size={B}, labeled_bs={L}")
+    if patch_size is not None and (len(patch_size) != 2 or int(patch_size[0]) != int(patch_size[1])):
+        raise ValueError(f"deep co-training rotates by 90 degrees: the patch must be square, got {list(patch_size)}")
+    return B - L
+
+
+class DeepCoTrainingTrainer(_TapedStep):
+    """Deep co-training, rotation consistency (reference code/train_deep_co_training_2D.py:134-167,
+    _2D_ViT.py:172-205): ONE network, two train-mode forwards per step -- pass A on the batch, pass R on
+    ``rot90(volume[L:], k)`` -- and ``0.5 * (CE + Dice)(A[:L]) + w * 0.5 * (mean((Q.detach() - rot P)^2) +
+    mean((Q - (rot P).detach())^2))`` with P = softmax(A[L:]), Q = softmax(R), w = consistency * sigmoid_rampup(iter // 150)
+    (no ``iter_num < 1000`` gate).  Plain SGD (momentum 0.9, wd 1e-4), poly LR in the Mean-Teacher order; no EMA, no teacher.
+
+    k comes from ``rotation_schedule(seed, max_iterations)`` held on the device and read there at ``state.iter_num``, so a
+    replayed launch tape rotates by each iteration's own k.  The network is differentiated through both passes: they run
+    on two plans (R on ``slot=1``), each backward writes the flat gradient buffer, so R's gradient is stashed and added to
+    A's (``mis_grad_combine``) before the optimizer.  With a process group the summed buffer is exchanged ONCE, after the
+    second backward, by a blocking all-reduce: this trainer does not overlap the exchange with the backward."""
+
+    PASS_STREAMS = (1, 2)           # Philox dropout sub-streams of pass A and pass R
+
+    def __init__(self, model, *, labeled_bs, num_classes, base_lr=0.01, max_iterations=30000, consistency=0.1,
+                 consistency_rampup=200.0, seed=1337, iter_num=0, momentum=0.9, weight_decay=1e-4, process_group=None,
+                 use_tape=None, patch_size=None):
+        if patch_size is not None:
+            dct_split(labeled_bs + 1, labeled_bs, patch_size)
+        self.model = model
+        self.labeled_bs, self.num_classes = int(labeled_bs), num_classes
+        self.hyper = dict(base_lr=float(base_lr), max_iterations=float(max_iterations), ema_decay=0.0,
+                          consistency=float(consistency), rampup=float(consistency_rampup), ramp_div=150,
+                          cons_start_iter=0)
+        self.momentum, self.weight_decay = momentum, weight_decay
+        self.pg = process_group
+        self.use_tape = STEP_TAPE if use_tape is None else bool(use_tape)
+        self.state = ops.new_step_state()
+        h = self.hyper
+        ops.step_init(self.state, seed, iter_num, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
+                      h["rampup"], h["ramp_div"], h["cons_start_iter"])
+        model.step_state = self.state
+        model.rng_stream = self.PASS_STREAMS[0]
+        self.schedule = torch.tensor(rotation_schedule(seed, max(int(max_iterations), 1)), dtype=torch.int32,
+                                     device="cuda")
+        self.momentum_buf = torch.zeros_like(model.flat_param)
+        self._stash = torch.zeros_like(model.flat_grad)
+        self.out = torch.zeros(16, dtype=torch.float32, device="cuda")
+        self.iter_num = iter_num
+        self._rot_in = None
+
+    def _run(self, volume, label, rot_k):
+        L, m = self.labeled_bs, self.model
+        unl = volume[L:]
+        if self._rot_in is None or self._rot_in.shape != unl.shape:
+            self._rot_in = torch.empty_like(unl)            # square planes: one shape for every k
+        k = -1 if rot_k is None else int(rot_k)
+        ops.rot90(unl, self._rot_in, k=k, sched=self.schedule, state=self.state)
+        # A then R, one after the other on this stream: BatchNorm running statistics are updated twice, in the reference's
+        # order.  R runs on a plan of its own (slot 1), so A's activations and logits survive it.
+        m.rng_stream = self.PASS_STREAMS[0]
+        a = m.forward_raw(volume)
+        pa = m.last_pass()
+        m.rng_stream = self.PASS_STREAMS[1]
+        r = m.forward_raw(self._rot_in, slot=1)
+        pr = m.last_pass()
+        m.rng_stream = self.PASS_STREAMS[0]
+        ops.dct_tail(a, r, label[:L].contiguous(), L, self.out, dA=m.logits_grad_buffer(pa), dR=m.logits_grad_buffer(pr),
+                     k=k, sched=self.schedule, state=self.state)
+        # A backward writes (does not add to) the flat gradient buffer.  The stash copy is enqueued on this stream after R's
+        # backward has joined its weight-gradient side stream, and every side-stream section of A's backward starts with a
+        # wait for this stream (Plan.backward / ConvOp.bwd / LinearOp.bwd): no weight gradient of A lands before the copy.
+        m.backward_raw(pass_=pr)
+        ops.grad_combine(self._stash, m.flat_grad, accumulate=False)
+        m.backward_raw(pass_=pa)
+        ops.grad_combine(m.flat_grad, self._stash, accumulate=True)
+        grad_scale = _lib.tape_call(dist.sync_gradients, m.flat_grad, self.pg)     # the step's only exchange
+        ops.sgd_ema_step(m.flat_param, m.flat_grad, self.momentum_buf, None, momentum=self.momentum,
+                         weight_decay=self.weight_decay, grad_scale=grad_scale, state=self.state)
+        h = self.hyper
+        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"], h["rampup"],
+                         h["ramp_div"], h["cons_start_iter"])
+
+    def step(self, volume_batch, label_batch, rot_k=None):
+        """One iteration on device tensors [B, 1, H, W] / [B, H, W]; ``rot_k`` (0..3) replaces the scheduled rotation
+        (parity tests, eager).  Returns the device scalar buffer ``[loss, loss_ce, loss_dice, consistency_loss,
+        consistency_weight, k, ...]`` (no host sync)."""
+        if volume_batch.dim() != 4:
+            raise ValueError(f"deep co-training runs the 2-D networks on [B, C, H, W]; got {tuple(volume_batch.shape)}")
+        dct_split(volume_batch.shape[0], self.labeled_bs, tuple(volume_batch.shape[2:]))
+        if rot_k is not None and rot_k not in (0, 1, 2, 3):
+            raise ValueError(f"rot_k must be 0, 1, 2 or 3, got {rot_k}")
+        if not self.model.training:
+            raise RuntimeError("deep co-training runs both passes in train mode (the reference never calls .eval() there)")
+        if self.use_tape and rot_k is None:
+            self._tape_step(lambda v, l: self._run(v, l, None), (volume_batch, label_batch))
+        else:
+            self._run(volume_batch, label_batch, rot_k)
+        self.iter_num += 1
+        return self.out
+
+    def losses(self):
+        o = self.out.cpu()
+        return dict(loss=o[0].item(), loss_ce=o[1].item(), loss_dice=o[2].item(), consistency_loss=o[3].item(),
+                    consistency_weight=o[4].item(), rot_k=int(o[5].item()))
 
 
 class CrossTeachingTrainer(_TapedStep):

@@ -432,11 +432,13 @@ def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=
 
 
 def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, log_every=1, trainer_cls=None,
-                 snapshot_fmt="../model/{}_{}_labeled/{}", trainer_kw=None):
+                 snapshot_fmt="../model/{}_{}_labeled/{}", trainer_kw=None, single_model=False):
     """Hot loop of train_mean_teacher_2D.py:196-312 / train_mean_teacher_3D.py:128-230 (and, with
     ``trainer_cls=UAMTTrainer``, of train_uncertainty_aware_mean_teacher_{2D,3D}.py; with ``trainer_cls=ICTTrainer``
     and ``trainer_kw=dict(ict_alpha=...)``, of train_interpolation_consistency_training_{2D,3D,2D_ViT}.py).
-    ``trainer_kw``: extra keyword arguments of the trainer class."""
+    ``trainer_kw``: extra keyword arguments of the trainer class.  ``single_model=True``: no EMA teacher is built and
+    the trainer class takes the one network alone (``trainer_cls=DeepCoTrainingTrainer``:
+    train_deep_co_training_2D{,_ViT}.py:116-237)."""
     from .step import MeanTeacherTrainer
     if trainer_cls is not None:
         MeanTeacherTrainer = trainer_cls
@@ -445,22 +447,30 @@ def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, lo
     snapshot_path = open_snapshot(args, rank, snapshot_fmt)
 
     model = make_model()
-    ema_model = make_model()
-    for p in ema_model.parameters():       # create_model(ema=True): teacher params are detached
-        p.detach_()
+    ema_model = None if single_model else make_model()
+    if ema_model is not None:
+        for p in ema_model.parameters():   # create_model(ema=True): teacher params are detached
+            p.detach_()
     if world > 1:                          # every rank starts from rank 0's weights and running statistics
         broadcast_model_state(model, ema_model)
     model.train()
-    ema_model.train()
+    if ema_model is not None:
+        ema_model.train()
 
-    trainer = MeanTeacherTrainer(model, ema_model, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
-                                 base_lr=args.base_lr, max_iterations=args.max_iterations, ema_decay=args.ema_decay,
-                                 consistency=args.consistency, consistency_rampup=args.consistency_rampup,
-                                 cons_start_iter=cons_start_iter, seed=args.seed + rank,
-                                 # captured replay of a step that contains an RCCL collective is not verified on
-                                 # hardware: --hip_graph is honoured for single-GPU runs only
-                                 use_graph=bool(getattr(args, "hip_graph", 0)) and world == 1,
-                                 **(trainer_kw or {}))
+    if single_model:
+        trainer = MeanTeacherTrainer(model, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
+                                     base_lr=args.base_lr, max_iterations=args.max_iterations,
+                                     consistency=args.consistency, consistency_rampup=args.consistency_rampup,
+                                     seed=args.seed + rank, **(trainer_kw or {}))
+    else:
+        trainer = MeanTeacherTrainer(model, ema_model, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
+                                     base_lr=args.base_lr, max_iterations=args.max_iterations, ema_decay=args.ema_decay,
+                                     consistency=args.consistency, consistency_rampup=args.consistency_rampup,
+                                     cons_start_iter=cons_start_iter, seed=args.seed + rank,
+                                     # captured replay of a step that contains an RCCL collective is not verified on
+                                     # hardware: --hip_graph is honoured for single-GPU runs only
+                                     use_graph=bool(getattr(args, "hip_graph", 0)) and world == 1,
+                                     **(trainer_kw or {}))
     if rank == 0 and getattr(args, "hip_graph", 0) and world > 1:
         logging.info("--hip_graph ignored for world_size %d (single-GPU only)" % world)
     loader, source = make_loader(args, label_dtype, rank, world)

@@ -372,6 +372,31 @@ int mis_ict_tail(const float* student, long long s_bs, const float* teacher0, lo
                  long long S, float cons_weight, const MisStepState* state, float loss_scale, float* out,
                  float* dlogits, long long d_bs, void* workspace, long long workspace_bytes, mis_stream_t stream);
 
+/* Deep co-training, rotation consistency (code/train_deep_co_training_2D.py:136-161, _2D_ViT.py:174-199).
+ * k = k_override when >= 0, else sched[state->iter_num] (clamped to the n_sched entries): the rotation count
+ *   rot_times = random.randrange(0, 4) (:141), read on the device so that a replayed step rotates by its own iteration's k.
+ * mis_rot90: out[n][c] = torch.rot90(in[n][c], k, [2,3]) (:143), bit-identical.  in: batch stride in_bs (a view such as
+ *   volume[L:]), planes dense; out: [N][C][H'][W'], (H', W') = (W, H) for odd k.  H != W is MIS_ERR_ARG unless k_override
+ *   is even.
+ * mis_dct_tail: pass A logits [L+U][C][H][W] (the whole batch), pass R logits [U][C][H][W] (the rotated unlabeled part):
+ *   0.5*(CE+Dice)(A[:L], label) + w * 0.5*(mean((Q.detach() - rot(P))^2) + mean((Q - rot(P).detach())^2)),
+ *   P = softmax(A[L:]), Q = softmax(R), means over N = U*C*H*W values (:148-158); w = state->cons_weight (gated by
+ *   state->cons_gate) when `state` is given, else cons_weight.  out (>= 6+C floats): loss, loss_ce, loss_dice,
+ *   consistency_loss, consistency_weight, k, C class-wise dice.  dA = loss_scale * dloss/dA (labeled rows: CE + Dice;
+ *   unlabeled rows: w * rot^-1(rot P - Q) / N through P's softmax), dR = loss_scale * w * (Q - rot P) / N through Q's
+ *   softmax; both NULL or both given; every element written once, no atomics (bit-reproducible).
+ * mis_grad_combine: dst = src (accumulate 0) or dst += src (accumulate 1) over n floats -- the flat gradient buffer of
+ *   one backward stashed and added to the next one's: autograd's sum over the two forwards of loss.backward() (:160). */
+int mis_rot90(const float* in, long long in_bs, float* out, long long out_bs, int N, int C, int H, int W, const int* sched,
+              long long n_sched, const MisStepState* state, int k_override, mis_stream_t stream);
+long long mis_dct_tail_workspace_bytes(int L, int U, int C, int H, int W);
+int mis_dct_tail(const float* logits_a, long long a_bs, const float* logits_r, long long r_bs, const void* label,
+                 int label_bytes, int L, int U, int C, int H, int W, const int* sched, long long n_sched,
+                 const MisStepState* state, int k_override, float cons_weight, float loss_scale, float* out, float* dA,
+                 long long dA_bs, float* dR, long long dR_bs, void* workspace, long long workspace_bytes,
+                 mis_stream_t stream);
+int mis_grad_combine(float* dst, const float* src, long long n, int accumulate, mis_stream_t stream);
+
 /* ---- stand-alone loss operators (drop-in utils.losses surface) ----------------------------------------
  * reference: losses.DiceLoss code/utils/losses.py:165-201; losses.softmax_mse_loss :74-91.
  * mis_dice_loss_fwd: probs [B][C][S], label [B][S]; out[0] = loss, out[1+c] = class-wise dice; the
