@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void dct_final_kernel(const DFinalArgs f) {
     const float gate = a.st ? a.st->cons_gate : 1.f;
     const double wl = gate != 0.f ? (double)w : 0.0;
     const double ce = tot[0] / nlab;
-    const double mse = tot[1 + 3 * C] / nun;
+    const double mse = gate != 0.f ? tot[1 + 3 * C] / nun : 0.0;   // gated off: reads 0, like mis_loss_tail / mis_ict_tail
     double dice = 0.0;
     for (int c = 0; c < C; ++c) {
         const double I = tot[1 + 3 * c], Y = tot[2 + 3 * c], Z = tot[3 + 3 * c];
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void dct_final_kernel(const DFinalArgs f) {
     }
     dice /= C;
     f.out[0] = (float)(0.5 * (dice + ce) + wl * mse);
-    f.out[1] = (float)ce; f.out[2] = (float)dice; f.out[3] = (float)mse; f.out[4] = (float)wl;
+    f.out[1] = (float)ce; f.out[2] = (float)dice; f.out[3] = (float)mse; f.out[4] = w;
     f.out[5] = (float)dct_k(a.sched, a.n_sched, a.st, a.k_override);
     f.coef[0] = (float)(f.loss_scale * 0.5 / nlab);
     f.coef[1] = (float)(f.loss_scale * wl / nun);

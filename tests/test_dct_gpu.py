@@ -63,18 +63,11 @@ def test_rot90_non_square_even_k_only():
 
 
 def _torch_dct_loss(a, r, label, L, C, k, w):
-    """The reference's loss expression (train_deep_co_training_2D.py:148-158) by torch autograd in float64."""
-    from oracle.losses import dice_loss
-    a = a.detach().double().requires_grad_(True)
-    r = r.detach().double().requires_grad_(True)
-    soft, q = torch.softmax(a, 1), torch.softmax(r, 1)
-    ce = torch.nn.functional.cross_entropy(a[:L], label.long())
-    dice = dice_loss(soft[:L], label.unsqueeze(1), C)
-    rp = torch.rot90(soft[L:], k, [2, 3])
-    cons = 0.5 * (torch.mean((q.detach() - rp) ** 2) + torch.mean((q - rp.detach()) ** 2))
-    loss = 0.5 * (dice + ce) + w * cons
-    loss.backward()
-    return dict(loss=loss.item(), loss_ce=ce.item(), loss_dice=dice.item(), consistency_loss=cons.item()), a.grad, r.grad
+    """The reference's loss expression (train_deep_co_training_2D.py:148-158) in float64: the shared loss-tail oracle
+    (tests/loss_tail_oracle.py)."""
+    from loss_tail_oracle import dct_tail
+    out, da, dr = dct_tail(a, r, label, L, k, w)
+    return dict(loss=out[0].item(), loss_ce=out[1].item(), loss_dice=out[2].item(), consistency_loss=out[3].item()), da, dr
 
 
 @pytest.mark.parametrize("C", [2, 4])

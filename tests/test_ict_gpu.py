@@ -133,19 +133,11 @@ def test_ict_step_matches_reference_golden_and_oracle(name):
 # operators
 # ---------------------------------------------------------------------------------------------------------------------
 def _torch_ict_loss(s, t0, t1, lam, label, L, C, w):
-    """The reference's loss expression (train_interpolation_consistency_training_2D.py:168-184) by torch autograd."""
-    from oracle.losses import dice_loss
-    s = s.detach().double().requires_grad_(True)
-    bshape = (-1,) + (1,) * (s.dim() - 1)
-    lam = lam.double().reshape(bshape)
-    target = torch.softmax(t0.double(), 1) * (1.0 - lam) + torch.softmax(t1.double(), 1) * lam
-    soft = torch.softmax(s, 1)
-    ce = torch.nn.functional.cross_entropy(s[:L], label[:L].long())
-    dice = dice_loss(soft[:L], label[:L].unsqueeze(1), C)
-    cons = torch.mean((soft[L:] - target) ** 2)
-    loss = 0.5 * (dice + ce) + w * cons
-    loss.backward()
-    return dict(loss=loss.item(), loss_ce=ce.item(), loss_dice=dice.item(), consistency_loss=cons.item()), s.grad
+    """The reference's loss expression (train_interpolation_consistency_training_2D.py:168-184) in float64: the shared
+    loss-tail oracle (tests/loss_tail_oracle.py)."""
+    from loss_tail_oracle import ict_tail
+    out, grad = ict_tail(s, t0, t1, lam, label, L, w)
+    return dict(loss=out[0].item(), loss_ce=out[1].item(), loss_dice=out[2].item(), consistency_loss=out[3].item()), grad
 
 
 @pytest.mark.parametrize("C", [2, 4])

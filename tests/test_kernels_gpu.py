@@ -402,23 +402,10 @@ def test_upsample(shape, align):
 
 
 def _tail_reference(s, t, label, L, w, gate=True):
-    s = s.clone().requires_grad_(True)
-    C = s.shape[1]
-    ps = torch.softmax(s, dim=1)
-    pt = torch.softmax(t, dim=1)
-    ce = F.cross_entropy(s[:L], label[:L].long())
-    onehot = torch.stack([(label[:L] == c).float() for c in range(C)], dim=1)
-    dice = 0.0
-    for c in range(C):
-        i = (ps[:L, c] * onehot[:, c]).sum()
-        y = (onehot[:, c] * onehot[:, c]).sum()
-        z = (ps[:L, c] * ps[:L, c]).sum()
-        dice = dice + (1 - (2 * i + 1e-5) / (z + y + 1e-5))
-    dice = dice / C
-    cons = ((ps[L:] - pt) ** 2).mean() if gate else torch.zeros(())
-    loss = 0.5 * (dice + ce) + w * cons
-    loss.backward()
-    return loss.item(), ce.item(), dice.item(), float(cons), s.grad
+    """(loss, ce, dice, consistency, gradient) of the shared float64 loss-tail oracle (tests/loss_tail_oracle.py)."""
+    from loss_tail_oracle import mean_teacher_tail
+    out, grad = mean_teacher_tail(s, t, label, L, w, gate=1.0 if gate else 0.0)
+    return out[0].item(), out[1].item(), out[2].item(), out[3].item(), grad
 
 
 @pytest.mark.parametrize("C,shape,ldtype", [(4, (1, 32, 32), torch.uint8), (2, (8, 8, 8), torch.int64)])
