@@ -1,18 +1,27 @@
-"""The Mean-Teacher training step as one fused device-side sequence.
+"""The training steps, each one fused device-side sequence replacing a loop body of the reference.
 
-Replaces the loop body of the reference (code/train_mean_teacher_2D.py:202-236,
-code/train_mean_teacher_3D.py:134-166):
+Six methods share one skeleton (``_Step``); DESIGN.md has a section per method:
 
-    noise -> student forward (labeled+unlabeled) -> EMA-teacher forward (noised unlabeled)
-    -> softmax / CE / Dice / softmax-MSE consistency (+ dlogits)  [one fused loss tail]
-    -> student backward -> [RCCL all-reduce of the flat gradient bucket] -> fused SGD + EMA
-    -> poly-LR / EMA-alpha / consistency-weight schedule advanced on the device
+    MeanTeacherTrainer      student + EMA teacher on the noised unlabeled half (code/train_mean_teacher_{2D,3D}.py)
+    UAMTTrainer             + T = 8 MC-dropout teacher passes, the entropy of their mean masks the consistency term
+    ICTTrainer              student on mixed unlabeled samples, pulled towards the mix of two teacher predictions
+    DeepCoTrainingTrainer   one network, a pass on the batch and one on its rotated unlabeled half
+    CrossTeachingTrainer    two students teach each other through arg-max pseudo labels (``pseudo_ce``: CPS)
+    CnnMeetVitTrainer       cross teaching + an EMA teacher of the second student
 
-Nothing in the sequence allocates or synchronises with the host: scalars stay in a small device
-buffer (``trainer.out``) that the caller reads when it wants to log (the reference forces >= 3 + C
-host syncs per step).  Because of that the whole step can be captured once into a
-hipGraph (``use_graph=True``) and replayed; the RNG offset, learning rate, EMA alpha and the
-consistency weight live in a device-resident ``MisStepState`` so replays stay correct.
+The skeleton of a step:
+
+    inputs (noise / mix / rotation) -> forwards, the independent ones beside each other on a side stream (``_beside``)
+    -> one fused loss tail per student (losses + dlogits) -> backward(s) -> [RCCL all-reduce of the flat gradient bucket(s)]
+    -> fused SGD + EMA per student, then the poly-LR / EMA-alpha / consistency-weight schedule advanced on the device
+    (``_finish_step``)
+
+A trainer's ``_run`` is what is particular to its method: which inputs it builds, which forwards run, which tail is called.
+Nothing in the sequence allocates or synchronises with the host: scalars stay in a small device buffer (``trainer.out``,
+or ``out1`` / ``out2`` with two students) that the caller reads when it wants to log (the reference forces >= 3 + C host
+syncs per step).  The RNG offset, learning rate, EMA alpha and the consistency weight live in a
+device-resident ``MisStepState``, so a recorded step stays correct when it is replayed: from a launch tape (``_TapedStep``,
+every trainer but UA-MT), or, for the Mean-Teacher step, from a captured hipGraph (``use_graph=True``).
 """
 import os
 import random
@@ -22,7 +31,7 @@ import torch
 from . import dist, ops
 from . import lib as _lib
 
-# teacher forward (cross teaching: the second student) on a side stream, see _run: bit-identical training, the second
+# teacher forward (cross teaching: the second student) on a side stream, see _Step._beside: bit-identical training, the second
 # network's launches fill the CUs the first one's launch tails and small deep layers leave idle (MIS_TWO_STREAM=0: off)
 TWO_STREAM = os.environ.get("MIS_TWO_STREAM", "1") != "0"
 # the step as a launch tape (lib.LaunchTape): after two eager steps the trainer records one step's launches and replays them --
@@ -83,86 +92,203 @@ class _TapedStep:
         self._tape.replay()
 
 
-class MeanTeacherTrainer(_TapedStep):
-    def __init__(self, model, ema_model, *, labeled_bs, num_classes, base_lr=0.01, max_iterations=30000,
-                 ema_decay=0.99, consistency=0.1, consistency_rampup=200.0, cons_start_iter=0, seed=1337,
-                 iter_num=0, momentum=0.9, weight_decay=1e-4, process_group=None, use_graph=False, use_tape=None):
-        if model.flat_param.numel() != ema_model.flat_param.numel():
-            raise RuntimeError("student and teacher must be the same architecture")
-        self.model, self.ema_model = model, ema_model
+class _Step(_TapedStep):
+    """What every training step here is made of; a trainer adds its constructor signature, ``TRAIN_MODE`` (the message for a
+    network found in eval mode) and ``_run(volume, label, *inject)``, the step in its eager form -- also what is recorded."""
+
+    TRAIN_MODE = None
+    _side = None            # the side stream of _beside, created on first use
+    _ema_in = None          # the teacher's noised input (_noised)
+
+    def _setup(self, students, teachers, rng_streams, *, labeled_bs, num_classes, base_lr, max_iterations, consistency,
+               consistency_rampup, seed, iter_num, momentum, weight_decay, process_group, use_tape, ema_decay=0.0,
+               cons_start_iter=0, lr_post_increment=False):
+        """Step state and schedule, the networks bound to them, one momentum and one scalar buffer per student.
+        ``rng_streams``: the Philox dropout sub-stream of each network (students, then teachers): seed-reproducible, distinct."""
+        self._students, self._nets = tuple(students), tuple(students) + tuple(teachers)
         self.labeled_bs, self.num_classes = labeled_bs, num_classes
-        self.hyper = dict(base_lr=float(base_lr), max_iterations=float(max_iterations),
-                          ema_decay=float(ema_decay), consistency=float(consistency),
-                          rampup=float(consistency_rampup), ramp_div=150, cons_start_iter=int(cons_start_iter))
+        # the keyword arguments of ops.step_init / ops.step_advance, under their names
+        self.hyper = dict(base_lr=float(base_lr), max_iterations=float(max_iterations), ema_decay=float(ema_decay),
+                          consistency=float(consistency), rampup=float(consistency_rampup), ramp_div=150,
+                          cons_start_iter=int(cons_start_iter), lr_post_increment=bool(lr_post_increment))
         self.momentum, self.weight_decay = momentum, weight_decay
         self.pg = process_group
         self.world = dist.world_size(process_group)
+        self.use_tape = STEP_TAPE if use_tape is None else bool(use_tape)
         self.state = ops.new_step_state()
-        ops.step_init(self.state, seed, iter_num, self.hyper["base_lr"], self.hyper["max_iterations"],
-                      self.hyper["ema_decay"], self.hyper["consistency"], self.hyper["rampup"],
-                      self.hyper["ramp_div"], self.hyper["cons_start_iter"])
-        model.step_state = self.state
-        ema_model.step_state = self.state
-        model.rng_stream, ema_model.rng_stream = 1, 2   # seed-reproducible, distinct dropout streams
-        self.momentum_buf = torch.zeros_like(model.flat_param)
-        self.out = torch.zeros(16, dtype=torch.float32, device="cuda")
+        ops.step_init(self.state, seed, iter_num, **self.hyper)
+        for net, stream in zip(self._nets, rng_streams):
+            net.step_state, net.rng_stream = self.state, stream
+        names = (("momentum_buf", "out"),) if len(students) == 1 else (("mom1", "out1"), ("mom2", "out2"))
+        for net, (mom, out) in zip(students, names):
+            setattr(self, mom, torch.zeros_like(net.flat_param))
+            setattr(self, out, torch.zeros(16, dtype=torch.float32, device="cuda"))
         self.iter_num = iter_num
-        # a captured replay of a step that contains an RCCL collective is not verified on hardware: single-GPU only
-        self.use_graph = bool(use_graph) and self.world == 1
-        self.use_tape = (STEP_TAPE if use_tape is None else bool(use_tape)) and not self.use_graph
-        self._graph = None
-        self._static = None
-        self._ema_in = None
-        self._side = None
+
+    # ---- one iteration ----
+    def _step(self, volume, label, *inject):
+        """The body of every ``step()``.  ``inject``: the values a parity test passes in place of the step's device-side draws
+        (noise, mix factors, rotation); one that is not None keeps the step eager.  Returns the device scalar buffer(s)."""
+        if not all(net.training for net in self._nets):
+            raise RuntimeError(self.TRAIN_MODE)
+        if all(x is None for x in inject):
+            self._replay(volume, label, *inject)
+        else:
+            self._run(volume, label, *inject)
+        self.iter_num += 1
+        return self.out if len(self._students) == 1 else (self.out1, self.out2)
+
+    def _replay(self, volume, label, *none):
+        """A step on its own device-side draws: through the launch tape unless the trainer is eager."""
+        if self.use_tape:
+            self._tape_step(lambda v, l: self._run(v, l, *none), (volume, label))
+        else:
+            self._run(volume, label, *none)
+
+    # ---- the pieces of _run ----
+    def _scratch(self, name, like, shape=None):
+        """The input buffer ``self.<name>`` of ``like``'s shape (or ``shape``), dtype and device: allocated on first use and
+        again when the batch geometry changes."""
+        shape = tuple(like.shape if shape is None else shape)
+        buf = getattr(self, name)
+        if buf is None or tuple(buf.shape) != shape:
+            buf = torch.empty(shape, dtype=like.dtype, device=like.device)
+            setattr(self, name, buf)
+        return buf
+
+    def _noised(self, unl, noise):
+        """The teacher's input: the unlabeled half plus clipped Gaussian noise drawn on the device (``noise``: injected, parity
+        tests only)."""
+        ema_in = self._scratch("_ema_in", unl)
+        if noise is None:
+            ops.teacher_noise(unl, ema_in, self.state)
+        else:
+            torch.add(unl, noise, out=ema_in)
+        return ema_in
+
+    def _beside(self, side_fn, main_fn):
+        """Two independent pieces of work; returns ``(side_fn(), main_fn())``.  With TWO_STREAM ``side_fn`` is enqueued first, on
+        the side stream, between a fork (side waits for main) and a join (main waits for side), and fills the CUs that
+        ``main_fn``'s launch tails and small deep layers leave idle.  Without, ``main_fn`` then ``side_fn`` on the one stream.
+        Same kernels, same order per network, same reduction trees: bit-identical training either way."""
+        if not TWO_STREAM:
+            res = main_fn()
+            return side_fn(), res
+        main = torch.cuda.current_stream()
+        if self._side is None:
+            self._side = _lib.side_stream("side")
+        _lib.wait_stream(self._side, main)
+        with torch.cuda.stream(self._side):
+            side_res = side_fn()
+        res = main_fn()
+        _lib.wait_stream(main, self._side)
+        return side_res, res
+
+    def _backward_pair(self, side):
+        """The backward of both students, student ``side`` (0 / 1) beside the other one, with both exchanges in flight until
+        one wait at the end; returns the two 1/world scales.  With bucketers both are begun first (a host-side reset); the
+        collectives are ENQUEUED by this thread in program order -- the side student's buckets, then the other one's -- the same
+        on every rank.  The side student's bucketer is built with ``defer_tail``: its tail bucket goes out in ``finish``, so the
+        in-order RCCL stream does not hold the other student's early buckets behind the end of the side backward."""
+        nets, (b1, b2) = self._students, self._bucketers
+        main = 1 - side
+        if b1 is None:
+            self._beside(nets[side].backward_raw, nets[main].backward_raw)
+            return [_lib.tape_call(dist.sync_gradients, net.flat_grad, self.pg) for net in nets]
+        bs = (b1, b2)
+        _lib.tape_call(b1.begin)
+        _lib.tape_call(b2.begin)
+
+        def main_backward():
+            nets[main].backward_raw(on_progress=bs[main].advance)
+            if not TWO_STREAM:
+                # one stream: this backward ran first and is complete; what is left of its buckets goes out now, before the
+                # other student's backward, and travels beside it
+                _lib.tape_call(bs[main].advance, 0, True)
+
+        self._beside(lambda: nets[side].backward_raw(on_progress=bs[side].advance), main_backward)
+        return [_lib.tape_call(b1.finish), _lib.tape_call(b2.finish)]
+
+    def _finish_step(self, *updates):
+        """Fused SGD (+ EMA of the teacher) for every ``(student, momentum buffer, teacher parameters or None, grad scale)``, then
+        the schedule: iteration, learning rate, EMA alpha and consistency weight advance on the device."""
+        for net, mom, ema_param, grad_scale in updates:
+            ops.sgd_ema_step(net.flat_param, net.flat_grad, mom, ema_param, momentum=self.momentum,
+                             weight_decay=self.weight_decay, grad_scale=grad_scale, state=self.state)
+        ops.step_advance(self.state, **self.hyper)
+
+    def _pair_losses(self):
+        """Host copies of ``out1`` / ``out2`` and what every two-student step reports from them."""
+        a, b = self.out1.cpu(), self.out2.cpu()
+        return a, b, dict(loss=a[0].item() + b[0].item(), model1_loss=a[0].item(), model2_loss=b[0].item(),
+                          loss1_ce=a[1].item(), loss1_dice=a[2].item(), pseudo_supervision1=a[3].item(),
+                          loss2_ce=b[1].item(), loss2_dice=b[2].item(), pseudo_supervision2=b[3].item(),
+                          consistency_weight=a[4].item())
+
+
+class _TeacherStudentStep(_Step):
+    """One student and its EMA teacher: what the Mean-Teacher step, UA-MT and ICT have in common.  Dropout streams: student 1,
+    teacher 2."""
+
+    def __init__(self, model, ema_model, *, labeled_bs, num_classes, base_lr=0.01, max_iterations=30000,
+                 ema_decay=0.99, consistency=0.1, consistency_rampup=200.0, cons_start_iter=0, seed=1337,
+                 iter_num=0, momentum=0.9, weight_decay=1e-4, process_group=None, use_tape=None):
+        if model.flat_param.numel() != ema_model.flat_param.numel():
+            raise RuntimeError("student and teacher must be the same architecture")
+        self.model, self.ema_model = model, ema_model
+        self._setup((model,), (ema_model,), (1, 2), labeled_bs=labeled_bs, num_classes=num_classes, base_lr=base_lr,
+                    max_iterations=max_iterations, ema_decay=ema_decay, consistency=consistency,
+                    consistency_rampup=consistency_rampup, cons_start_iter=cons_start_iter, seed=seed, iter_num=iter_num,
+                    momentum=momentum, weight_decay=weight_decay, process_group=process_group, use_tape=use_tape)
         self._bucketer = make_bucketer(model, process_group)
 
-    # ---- the step (eager form; also what gets captured) ----
+    def _backward_and_finish(self):
+        grad_scale = backward_and_sync(self.model, self.pg, self._bucketer)   # the step's only exchange
+        self._finish_step((self.model, self.momentum_buf, self.ema_model.flat_param, grad_scale))
+
+    def losses(self):
+        """Host copy of the last step's scalars (one small D2H)."""
+        o = self.out.cpu()
+        return dict(loss=o[0].item(), loss_ce=o[1].item(), loss_dice=o[2].item(),
+                    consistency_loss=o[3].item(), consistency_weight=o[4].item())
+
+
+class MeanTeacherTrainer(_TeacherStudentStep):
+    """Mean Teacher (reference code/train_mean_teacher_2D.py:202-236, code/train_mean_teacher_3D.py:134-166): student forward
+    on the batch, EMA-teacher forward on the noised unlabeled half, softmax / CE / Dice / softmax-MSE consistency in one fused
+    loss tail.  ``use_graph=True`` (single GPU) captures the step once into a hipGraph and replays that instead of the tape."""
+
+    TRAIN_MODE = "Mean-Teacher step runs both networks in train mode (reference never calls .eval())"
+
+    def __init__(self, model, ema_model, *, use_graph=False, **kw):
+        super().__init__(model, ema_model, **kw)
+        # a captured replay of a step that contains an RCCL collective is not verified on hardware: single-GPU only
+        self.use_graph = bool(use_graph) and self.world == 1
+        self.use_tape = self.use_tape and not self.use_graph
+        self._graph = None
+        self._static = None
+
+    # ---- the step (eager form; also what gets recorded or captured) ----
     def _run(self, volume, label, noise):
         L = self.labeled_bs
-        unl = volume[L:]
-        if self._ema_in is None or self._ema_in.shape != unl.shape:
-            self._ema_in = torch.empty_like(unl)
-        if noise is None:
-            ops.teacher_noise(unl.contiguous(), self._ema_in, self.state)
-        else:
-            torch.add(unl, noise, out=self._ema_in)     # injected noise: parity tests only
-        if TWO_STREAM:
-            # the two forwards are independent: the teacher's (half the batch, no backward) runs on a side stream
-            # and fills the CUs the student's small deep layers leave idle
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = _lib.side_stream("side")
-            _lib.wait_stream(self._side, main)
-            with torch.cuda.stream(self._side):
-                t_logits = self.ema_model.forward_raw(self._ema_in, no_backward=True)
-            s_logits = self.model.forward_raw(volume)
-            _lib.wait_stream(main, self._side)
-        else:
-            s_logits = self.model.forward_raw(volume)
-            t_logits = self.ema_model.forward_raw(self._ema_in, no_backward=True)
+        ema_in = self._noised(volume[L:].contiguous(), noise)
+        # the two forwards are independent: the teacher's is half the batch and has no backward
+        t_logits, s_logits = self._beside(lambda: self.ema_model.forward_raw(ema_in, no_backward=True),
+                                          lambda: self.model.forward_raw(volume))
         ops.loss_tail(s_logits, t_logits, label[:L].contiguous(), L, self.out,
                       dlogits=self.model.logits_grad_buffer(), state=self.state)
-        grad_scale = backward_and_sync(self.model, self.pg, self._bucketer)   # the step's only exchange
-        ops.sgd_ema_step(self.model.flat_param, self.model.flat_grad, self.momentum_buf,
-                         self.ema_model.flat_param, momentum=self.momentum, weight_decay=self.weight_decay,
-                         grad_scale=grad_scale, state=self.state)
-        h = self.hyper
-        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
-                         h["rampup"], h["ramp_div"], h["cons_start_iter"])
+        self._backward_and_finish()
 
     def step(self, volume_batch, label_batch, noise=None):
         """One iteration on device tensors; returns the device scalar buffer
         ``[loss, loss_ce, loss_dice, consistency_loss, consistency_weight, ...]`` (no host sync)."""
-        if not self.model.training or not self.ema_model.training:
-            raise RuntimeError("Mean-Teacher step runs both networks in train mode (reference never calls .eval())")
-        if self.use_graph and noise is None:
-            self._step_graph(volume_batch, label_batch)
-        elif self.use_tape and noise is None and type(self) is MeanTeacherTrainer:
-            self._tape_step(lambda v, l: self._run(v, l, None), (volume_batch, label_batch))
+        return self._step(volume_batch, label_batch, noise)
+
+    def _replay(self, volume, label, noise):
+        if self.use_graph:
+            self._step_graph(volume, label)
         else:
-            self._run(volume_batch, label_batch, noise)
-        self.iter_num += 1
-        return self.out
+            super()._replay(volume, label, noise)
 
     # ---- hipGraph capture / replay ----
     def _step_graph(self, volume, label):
@@ -173,7 +299,6 @@ class MeanTeacherTrainer(_TapedStep):
             self._run(self._static[0], self._static[1], None)
             torch.cuda.synchronize()
             self._graph = torch.cuda.CUDAGraph()
-            self._pending_first = True
             with torch.cuda.graph(self._graph):
                 self._run(self._static[0], self._static[1], None)
             # capture does not execute: the warm-up above WAS this call's step
@@ -182,14 +307,8 @@ class MeanTeacherTrainer(_TapedStep):
         self._static[1].copy_(label)
         self._graph.replay()
 
-    def losses(self):
-        """Host copy of the last step's scalars (one small D2H)."""
-        o = self.out.cpu()
-        return dict(loss=o[0].item(), loss_ce=o[1].item(), loss_dice=o[2].item(),
-                    consistency_loss=o[3].item(), consistency_weight=o[4].item())
 
-
-class UAMTTrainer(MeanTeacherTrainer):
+class UAMTTrainer(_TeacherStudentStep):
     """Uncertainty-aware Mean Teacher (reference code/train_uncertainty_aware_mean_teacher_3D.py:134-189,
     code/train_uncertainty_aware_mean_teacher_2D.py:146-201): the Mean-Teacher step plus T = 8 MC-dropout
     teacher predictions (4 forwards on ``repeat(unlabeled, 2)`` with fresh noise), whose mean-probability
@@ -197,76 +316,49 @@ class UAMTTrainer(MeanTeacherTrainer):
     running statistics updated 5 times per step, as in the reference)."""
 
     T = 8
+    TRAIN_MODE = "UA-MT runs both networks in train mode (MC dropout needs the teacher's dropout)"
+    _rep_in = None
+    _mean_probs = None
 
-    def __init__(self, *args, **kw):
-        kw.pop("use_graph", None)
-        kw["use_tape"] = False          # (the MC passes cycle the teacher through RNG sub-streams set from Python: eager)
-        super().__init__(*args, **kw)
-        self._rep_in = None
-        self._mean_probs = None
+    def __init__(self, model, ema_model, *, use_graph=False, use_tape=None, **kw):
+        # eager only, whatever the caller asks for (run_training passes both switches to every trainer class): the MC passes
+        # cycle the teacher through RNG sub-streams set from Python, which a recorded step would not repeat
+        super().__init__(model, ema_model, use_tape=False, **kw)
 
-    def _run(self, volume, label, noise, mc_noise=None):
+    def _run(self, volume, label, noise, mc_noise):
         L = self.labeled_bs
         unl = volume[L:].contiguous()
         U = unl.shape[0]
-        if self._ema_in is None or self._ema_in.shape != unl.shape:
-            self._ema_in = torch.empty_like(unl)
-            self._rep_in = torch.empty((2 * U,) + tuple(unl.shape[1:]), dtype=unl.dtype, device=unl.device)
-        if noise is None:
-            ops.teacher_noise(unl, self._ema_in, self.state)
-        else:
-            torch.add(unl, noise, out=self._ema_in)
-        if self._mean_probs is None or self._mean_probs.shape[0] != U:
-            self._mean_probs = None
+        ema_in = self._noised(unl, noise)
+        rep_in = self._scratch("_rep_in", unl, (2 * U,) + tuple(unl.shape[1:]))
 
         def teacher_passes():
             self.ema_model.rng_stream = 2
-            t_logits = self.ema_model.forward_raw(self._ema_in, no_backward=True)
+            t_logits = self.ema_model.forward_raw(ema_in, no_backward=True)
             if self._mean_probs is None or self._mean_probs.shape != t_logits.shape:
                 self._mean_probs = torch.empty_like(t_logits)
             for i in range(self.T // 2):
                 for r in range(2):
-                    half = self._rep_in[r * U:(r + 1) * U]
+                    half = rep_in[r * U:(r + 1) * U]
                     if mc_noise is None:
                         ops.teacher_noise(unl, half, self.state, salt=0x7EAC4E5 + 1 + 2 * i + r)
                     else:
                         torch.add(unl, mc_noise[i][r * U:(r + 1) * U], out=half)
                 self.ema_model.rng_stream = 3 + i          # a fresh dropout stream per MC pass
-                mc_logits = self.ema_model.forward_raw(self._rep_in, no_backward=True)
+                mc_logits = self.ema_model.forward_raw(rep_in, no_backward=True)
                 ops.softmax_mean_accumulate(mc_logits, self._mean_probs, 2, 1.0 / self.T, first=(i == 0))
             self.ema_model.rng_stream = 2
             return t_logits
 
-        if TWO_STREAM:
-            # the five teacher forwards (one plain, four MC passes: sequential, they share the teacher's buffers) only meet
-            # the student in the loss tail: they run on a side stream beside the student's forward (bit-identical)
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = _lib.side_stream("side")
-            _lib.wait_stream(self._side, main)
-            with torch.cuda.stream(self._side):
-                t_logits = teacher_passes()
-            s_logits = self.model.forward_raw(volume)
-            _lib.wait_stream(main, self._side)
-        else:
-            s_logits = self.model.forward_raw(volume)
-            t_logits = teacher_passes()
+        # the five teacher forwards (one plain, four MC passes: sequential, they share the teacher's buffers) only meet the
+        # student in the loss tail
+        t_logits, s_logits = self._beside(teacher_passes, lambda: self.model.forward_raw(volume))
         ops.uamt_tail(s_logits, t_logits, self._mean_probs, label[:L].contiguous(), L, self.out,
                       self.hyper["max_iterations"], dlogits=self.model.logits_grad_buffer(), state=self.state)
-        grad_scale = backward_and_sync(self.model, self.pg, self._bucketer)
-        ops.sgd_ema_step(self.model.flat_param, self.model.flat_grad, self.momentum_buf,
-                         self.ema_model.flat_param, momentum=self.momentum, weight_decay=self.weight_decay,
-                         grad_scale=grad_scale, state=self.state)
-        h = self.hyper
-        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
-                         h["rampup"], h["ramp_div"], h["cons_start_iter"])
+        self._backward_and_finish()
 
     def step(self, volume_batch, label_batch, noise=None, mc_noise=None):
-        if not self.model.training or not self.ema_model.training:
-            raise RuntimeError("UA-MT runs both networks in train mode (MC dropout needs the teacher's dropout)")
-        self._run(volume_batch, label_batch, noise, mc_noise)
-        self.iter_num += 1
-        return self.out
+        return self._step(volume_batch, label_batch, noise, mc_noise)
 
     def losses(self):
         d = super().losses()
@@ -290,7 +382,7 @@ def ict_split(batch_size, labeled_bs):
     return M
 
 
-class ICTTrainer(MeanTeacherTrainer):
+class ICTTrainer(_TeacherStudentStep):
     """Interpolation Consistency Training (reference code/train_interpolation_consistency_training_2D.py:150-190,
     _3D.py:140-182, _2D_ViT.py:190-235).  With L = labeled_bs and M = L // 2 the unlabeled samples x0 = volume[L:L+M]
     and x1 = volume[L+M:] are mixed with per-sample factors lam ~ Beta(ict_alpha, ict_alpha) drawn on the device; the
@@ -300,16 +392,15 @@ class ICTTrainer(MeanTeacherTrainer):
     the Mean-Teacher step; there is no ``iter_num < 1000`` gate."""
 
     TEACHER_STREAMS = (2, 3)        # Philox dropout sub-streams of the two teacher passes (the student's is 1)
+    TRAIN_MODE = "ICT runs both networks in train mode (the reference never calls ema_model.eval())"
+    _mix_in = None
 
-    def __init__(self, model, ema_model, *, ict_alpha=0.2, **kw):
+    def __init__(self, model, ema_model, *, ict_alpha=0.2, use_graph=False, **kw):
         if not float(ict_alpha) > 0.0:
             raise ValueError(f"ict_alpha must be > 0, got {ict_alpha}")
-        kw.pop("use_graph", None)   # replays go through the launch tape
-        kw.setdefault("cons_start_iter", 0)
-        super().__init__(model, ema_model, **kw)
+        super().__init__(model, ema_model, **kw)      # (use_graph: accepted from run_training; replays go through the tape)
         self.ict_alpha = float(ict_alpha)
         self.mix_factors = None     # [M] device tensor: the factors of the last step
-        self._mix_in = None
 
     def _run(self, volume, label, mix_factors):
         L = self.labeled_bs
@@ -320,10 +411,8 @@ class ICTTrainer(MeanTeacherTrainer):
             ops.beta_sample(self.mix_factors, self.ict_alpha, self.state)
         else:
             self.mix_factors.copy_(mix_factors.reshape(-1))        # injected factors: parity tests only
-        shape = (L + M,) + tuple(volume.shape[1:])
-        if self._mix_in is None or tuple(self._mix_in.shape) != shape:
-            self._mix_in = torch.empty(shape, dtype=volume.dtype, device=volume.device)
-        ops.ict_mix(volume, self.mix_factors, L, self._mix_in)
+        mix_in = self._scratch("_mix_in", volume, (L + M,) + tuple(volume.shape[1:]))
+        ops.ict_mix(volume, self.mix_factors, L, mix_in)
         x0, x1 = volume[L:L + M], volume[L + M:]
         ema = self.ema_model
 
@@ -336,28 +425,11 @@ class ICTTrainer(MeanTeacherTrainer):
             ema.rng_stream = self.TEACHER_STREAMS[0]
             return t0, t1
 
-        if TWO_STREAM:
-            # the teacher passes read only the raw batch: they run on a side stream beside the student's forward
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = _lib.side_stream("side")
-            _lib.wait_stream(self._side, main)
-            with torch.cuda.stream(self._side):
-                t0, t1 = teacher_passes()
-            s_logits = self.model.forward_raw(self._mix_in)
-            _lib.wait_stream(main, self._side)
-        else:
-            s_logits = self.model.forward_raw(self._mix_in)
-            t0, t1 = teacher_passes()
+        # the teacher passes read only the raw batch
+        (t0, t1), s_logits = self._beside(teacher_passes, lambda: self.model.forward_raw(mix_in))
         ops.ict_tail(s_logits, t0, t1, self.mix_factors, label[:L].contiguous(), L, self.out,
                      dlogits=self.model.logits_grad_buffer(), state=self.state)
-        grad_scale = backward_and_sync(self.model, self.pg, self._bucketer)   # the step's only exchange
-        ops.sgd_ema_step(self.model.flat_param, self.model.flat_grad, self.momentum_buf,
-                         self.ema_model.flat_param, momentum=self.momentum, weight_decay=self.weight_decay,
-                         grad_scale=grad_scale, state=self.state)
-        h = self.hyper
-        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
-                         h["rampup"], h["ramp_div"], h["cons_start_iter"])
+        self._backward_and_finish()
 
     def step(self, volume_batch, label_batch, mix_factors=None):
         """One ICT iteration on device tensors; ``mix_factors`` ([M] or [M,1,1,1(,1)]) replaces the device Beta draw
@@ -365,14 +437,7 @@ class ICTTrainer(MeanTeacherTrainer):
         M = ict_split(volume_batch.shape[0], self.labeled_bs)
         if mix_factors is not None and mix_factors.numel() != M:
             raise ValueError(f"mix_factors must hold labeled_bs // 2 = {M} values, got {mix_factors.numel()}")
-        if not self.model.training or not self.ema_model.training:
-            raise RuntimeError("ICT runs both networks in train mode (the reference never calls ema_model.eval())")
-        if self.use_tape and mix_factors is None:
-            self._tape_step(lambda v, l: self._run(v, l, None), (volume_batch, label_batch))
-        else:
-            self._run(volume_batch, label_batch, mix_factors)
-        self.iter_num += 1
-        return self.out
+        return self._step(volume_batch, label_batch, mix_factors)
 
 
 def rotation_schedule(seed, n):
@@ -395,7 +460,7 @@ def dct_split(batch_size, labeled_bs, patch_size=None):
     return B - L
 
 
-class DeepCoTrainingTrainer(_TapedStep):
+class DeepCoTrainingTrainer(_Step):
     """Deep co-training, rotation consistency (reference code/train_deep_co_training_2D.py:134-167,
     _2D_ViT.py:172-205): ONE network, two train-mode forwards per step -- pass A on the batch, pass R on
     ``rot90(volume[L:], k)`` -- and ``0.5 * (CE + Dice)(A[:L]) + w * 0.5 * (mean((Q.detach() - rot P)^2) +
@@ -409,6 +474,8 @@ class DeepCoTrainingTrainer(_TapedStep):
     second backward, by a blocking all-reduce: this trainer does not overlap the exchange with the backward."""
 
     PASS_STREAMS = (1, 2)           # Philox dropout sub-streams of pass A and pass R
+    TRAIN_MODE = "deep co-training runs both passes in train mode (the reference never calls .eval() there)"
+    _rot_in = None
 
     def __init__(self, model, *, labeled_bs, num_classes, base_lr=0.01, max_iterations=30000, consistency=0.1,
                  consistency_rampup=200.0, seed=1337, iter_num=0, momentum=0.9, weight_decay=1e-4, process_group=None,
@@ -416,41 +483,26 @@ class DeepCoTrainingTrainer(_TapedStep):
         if patch_size is not None:
             dct_split(labeled_bs + 1, labeled_bs, patch_size)
         self.model = model
-        self.labeled_bs, self.num_classes = int(labeled_bs), num_classes
-        self.hyper = dict(base_lr=float(base_lr), max_iterations=float(max_iterations), ema_decay=0.0,
-                          consistency=float(consistency), rampup=float(consistency_rampup), ramp_div=150,
-                          cons_start_iter=0)
-        self.momentum, self.weight_decay = momentum, weight_decay
-        self.pg = process_group
-        self.use_tape = STEP_TAPE if use_tape is None else bool(use_tape)
-        self.state = ops.new_step_state()
-        h = self.hyper
-        ops.step_init(self.state, seed, iter_num, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
-                      h["rampup"], h["ramp_div"], h["cons_start_iter"])
-        model.step_state = self.state
-        model.rng_stream = self.PASS_STREAMS[0]
+        self._setup((model,), (), self.PASS_STREAMS[:1], labeled_bs=int(labeled_bs), num_classes=num_classes,
+                    base_lr=base_lr, max_iterations=max_iterations, consistency=consistency,
+                    consistency_rampup=consistency_rampup, seed=seed, iter_num=iter_num, momentum=momentum,
+                    weight_decay=weight_decay, process_group=process_group, use_tape=use_tape)
         self.schedule = torch.tensor(rotation_schedule(seed, max(int(max_iterations), 1)), dtype=torch.int32,
                                      device="cuda")
-        self.momentum_buf = torch.zeros_like(model.flat_param)
         self._stash = torch.zeros_like(model.flat_grad)
-        self.out = torch.zeros(16, dtype=torch.float32, device="cuda")
-        self.iter_num = iter_num
-        self._rot_in = None
 
     def _run(self, volume, label, rot_k):
         L, m = self.labeled_bs, self.model
-        unl = volume[L:]
-        if self._rot_in is None or self._rot_in.shape != unl.shape:
-            self._rot_in = torch.empty_like(unl)            # square planes: one shape for every k
+        rot_in = self._scratch("_rot_in", volume[L:])       # square planes: one shape for every k
         k = -1 if rot_k is None else int(rot_k)
-        ops.rot90(unl, self._rot_in, k=k, sched=self.schedule, state=self.state)
+        ops.rot90(volume[L:], rot_in, k=k, sched=self.schedule, state=self.state)
         # A then R, one after the other on this stream: BatchNorm running statistics are updated twice, in the reference's
         # order.  R runs on a plan of its own (slot 1), so A's activations and logits survive it.
         m.rng_stream = self.PASS_STREAMS[0]
         a = m.forward_raw(volume)
         pa = m.last_pass()
         m.rng_stream = self.PASS_STREAMS[1]
-        r = m.forward_raw(self._rot_in, slot=1)
+        r = m.forward_raw(rot_in, slot=1)
         pr = m.last_pass()
         m.rng_stream = self.PASS_STREAMS[0]
         ops.dct_tail(a, r, label[:L].contiguous(), L, self.out, dA=m.logits_grad_buffer(pa), dR=m.logits_grad_buffer(pr),
@@ -463,11 +515,7 @@ class DeepCoTrainingTrainer(_TapedStep):
         m.backward_raw(pass_=pa)
         ops.grad_combine(m.flat_grad, self._stash, accumulate=True)
         grad_scale = _lib.tape_call(dist.sync_gradients, m.flat_grad, self.pg)     # the step's only exchange
-        ops.sgd_ema_step(m.flat_param, m.flat_grad, self.momentum_buf, None, momentum=self.momentum,
-                         weight_decay=self.weight_decay, grad_scale=grad_scale, state=self.state)
-        h = self.hyper
-        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"], h["rampup"],
-                         h["ramp_div"], h["cons_start_iter"])
+        self._finish_step((m, self.momentum_buf, None, grad_scale))
 
     def step(self, volume_batch, label_batch, rot_k=None):
         """One iteration on device tensors [B, 1, H, W] / [B, H, W]; ``rot_k`` (0..3) replaces the scheduled rotation
@@ -478,14 +526,7 @@ class DeepCoTrainingTrainer(_TapedStep):
         dct_split(volume_batch.shape[0], self.labeled_bs, tuple(volume_batch.shape[2:]))
         if rot_k is not None and rot_k not in (0, 1, 2, 3):
             raise ValueError(f"rot_k must be 0, 1, 2 or 3, got {rot_k}")
-        if not self.model.training:
-            raise RuntimeError("deep co-training runs both passes in train mode (the reference never calls .eval() there)")
-        if self.use_tape and rot_k is None:
-            self._tape_step(lambda v, l: self._run(v, l, None), (volume_batch, label_batch))
-        else:
-            self._run(volume_batch, label_batch, rot_k)
-        self.iter_num += 1
-        return self.out
+        return self._step(volume_batch, label_batch, rot_k)
 
     def losses(self):
         o = self.out.cpu()
@@ -493,118 +534,47 @@ class DeepCoTrainingTrainer(_TapedStep):
                     consistency_weight=o[4].item(), rot_k=int(o[5].item()))
 
 
-class CrossTeachingTrainer(_TapedStep):
+class CrossTeachingTrainer(_Step):
     """Cross teaching between a CNN and a Transformer (reference
     code/train_cross_teaching_between_cnn_transformer_2D.py:216-263): two students see the whole batch, each is
     supervised on the labeled half and by the OTHER network's arg-max pseudo labels (Dice) on the unlabeled
     half; ``loss = model1_loss + model2_loss``, two SGD steps, no EMA, no noise.  The learning rate follows the
     post-increment rule of that script (:257-263)."""
 
+    TRAIN_MODE = "cross teaching trains both networks (train mode)"
+
     def __init__(self, model1, model2, *, labeled_bs, num_classes, base_lr=0.01, max_iterations=30000,
                  consistency=0.1, consistency_rampup=200.0, seed=1337, iter_num=0, momentum=0.9, weight_decay=1e-4,
                  process_group=None, pseudo_ce=False, use_tape=None):
-        self.use_tape = STEP_TAPE if use_tape is None else bool(use_tape)
         # pseudo_ce=True: cross pseudo supervision (code/train_cross_pseudo_supervision_{2D,3D}.py): the same step
         # with a cross-entropy pseudo-supervision term instead of Dice
         self.pseudo_ce = bool(pseudo_ce)
         self.model1, self.model2 = model1, model2
-        self.labeled_bs, self.num_classes = labeled_bs, num_classes
-        self.hyper = dict(base_lr=float(base_lr), max_iterations=float(max_iterations), ema_decay=0.0,
-                          consistency=float(consistency), rampup=float(consistency_rampup), ramp_div=150,
-                          cons_start_iter=0, lr_post_increment=True)
-        self.momentum, self.weight_decay = momentum, weight_decay
-        self.pg = process_group
-        self.state = ops.new_step_state()
-        h = self.hyper
-        ops.step_init(self.state, seed, iter_num, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
-                      h["rampup"], h["ramp_div"], h["cons_start_iter"], h["lr_post_increment"])
-        for i, m in enumerate((model1, model2)):
-            m.step_state = self.state
-            m.rng_stream = 1 + i
-        self.mom1 = torch.zeros_like(model1.flat_param)
-        self.mom2 = torch.zeros_like(model2.flat_param)
-        self.out1 = torch.zeros(16, dtype=torch.float32, device="cuda")
-        self.out2 = torch.zeros(16, dtype=torch.float32, device="cuda")
-        self.iter_num = iter_num
-        self._side = None
-        # model2's backward is enqueued first (side stream): its exposed tail bucket is issued by finish(), after model1's
-        # buckets, so that the in-order RCCL stream does not hold model1's early buckets behind the end of model2's backward
+        self._setup((model1, model2), (), (1, 2), labeled_bs=labeled_bs, num_classes=num_classes, base_lr=base_lr,
+                    max_iterations=max_iterations, consistency=consistency, consistency_rampup=consistency_rampup,
+                    lr_post_increment=True, seed=seed, iter_num=iter_num, momentum=momentum, weight_decay=weight_decay,
+                    process_group=process_group, use_tape=use_tape)
+        # model2 is the side-stream student (_backward_pair): its tail bucket is deferred
         self._bucketers = (make_bucketer(model1, process_group),
                            make_bucketer(model2, process_group, defer_tail=TWO_STREAM))
 
     def step(self, volume_batch, label_batch):
-        if not (self.model1.training and self.model2.training):
-            raise RuntimeError("cross teaching trains both networks (train mode)")
-        if self.use_tape:
-            self._tape_step(self._run, (volume_batch, label_batch))
-        else:
-            self._run(volume_batch, label_batch)
-        self.iter_num += 1
-        return self.out1, self.out2
+        return self._step(volume_batch, label_batch)
 
     def _run(self, volume_batch, label_batch):
         L = self.labeled_bs
         lab = label_batch[:L].contiguous()
-        if TWO_STREAM:
-            # the two students only meet in the loss tails: model2's forward and backward run on a side stream
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = _lib.side_stream("side")
-            _lib.wait_stream(self._side, main)
-            with torch.cuda.stream(self._side):
-                o2 = self.model2.forward_raw(volume_batch)
-            o1 = self.model1.forward_raw(volume_batch)
-            _lib.wait_stream(main, self._side)
-        else:
-            o1 = self.model1.forward_raw(volume_batch)
-            o2 = self.model2.forward_raw(volume_batch)
+        # the two students only meet in the loss tails: model2's forward and backward run beside model1's
+        o2, o1 = self._beside(lambda: self.model2.forward_raw(volume_batch), lambda: self.model1.forward_raw(volume_batch))
         ops.cross_teaching_tail(o1, o2, lab, L, self.out1, dlogits=self.model1.logits_grad_buffer(), state=self.state,
                                 pseudo_ce=self.pseudo_ce)
         ops.cross_teaching_tail(o2, o1, lab, L, self.out2, dlogits=self.model2.logits_grad_buffer(), state=self.state,
                                 pseudo_ce=self.pseudo_ce)
-        if TWO_STREAM and self._bucketers[0] is None:
-            _lib.wait_stream(self._side, main)
-            with torch.cuda.stream(self._side):
-                self.model2.backward_raw()
-            self.model1.backward_raw()
-            _lib.wait_stream(main, self._side)
-            scales = [_lib.tape_call(dist.sync_gradients, m.flat_grad, self.pg) for m in (self.model1, self.model2)]
-        elif self._bucketers[0] is not None:
-            # both students' buckets are in flight while the other student's backward runs; one wait at the end.  With
-            # TWO_STREAM the second student's backward runs on the side stream as on one GPU: its collectives are still
-            # ENQUEUED by this thread in program order (model2's buckets, then model1's), the same on every rank.
-            b1, b2 = self._bucketers
-            _lib.tape_call(b1.begin)
-            _lib.tape_call(b2.begin)
-            if TWO_STREAM:
-                _lib.wait_stream(self._side, main)
-                with torch.cuda.stream(self._side):
-                    self.model2.backward_raw(on_progress=b2.advance)
-                self.model1.backward_raw(on_progress=b1.advance)
-                _lib.wait_stream(main, self._side)
-                scales = [_lib.tape_call(b1.finish), _lib.tape_call(b2.finish)]      # b1's tail went out with its backward; b2's goes now
-            else:
-                self.model1.backward_raw(on_progress=b1.advance)
-                _lib.tape_call(b1.advance, 0, True)
-                self.model2.backward_raw(on_progress=b2.advance)
-                scales = [_lib.tape_call(b1.finish), _lib.tape_call(b2.finish)]
-        else:
-            self.model1.backward_raw()
-            self.model2.backward_raw()
-            scales = [_lib.tape_call(dist.sync_gradients, m.flat_grad, self.pg) for m in (self.model1, self.model2)]
-        for m, mom, scale in ((self.model1, self.mom1, scales[0]), (self.model2, self.mom2, scales[1])):
-            ops.sgd_ema_step(m.flat_param, m.flat_grad, mom, None, momentum=self.momentum,
-                             weight_decay=self.weight_decay, grad_scale=scale, state=self.state)
-        h = self.hyper
-        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"], h["rampup"],
-                         h["ramp_div"], h["cons_start_iter"], h["lr_post_increment"])
+        scales = self._backward_pair(side=1)
+        self._finish_step((self.model1, self.mom1, None, scales[0]), (self.model2, self.mom2, None, scales[1]))
 
     def losses(self):
-        a, b = self.out1.cpu(), self.out2.cpu()
-        return dict(loss=a[0].item() + b[0].item(), model1_loss=a[0].item(), model2_loss=b[0].item(),
-                    loss1_ce=a[1].item(), loss1_dice=a[2].item(), pseudo_supervision1=a[3].item(),
-                    loss2_ce=b[1].item(), loss2_dice=b[2].item(), pseudo_supervision2=b[3].item(),
-                    consistency_weight=a[4].item())
+        return self._pair_losses()[2]
 
 
 def linear_rampup(current, rampup_length):
@@ -613,7 +583,7 @@ def linear_rampup(current, rampup_length):
     return 1.0 if current >= rampup_length else current / rampup_length
 
 
-class CnnMeetVitTrainer(_TapedStep):
+class CnnMeetVitTrainer(_Step):
     """CNN student + Transformer student + EMA Transformer teacher (reference code/train_cnn_meet_vit_2D.py:293-352).
 
     ``model1`` (CNN) and ``model2`` (SwinUnet) see the whole batch and cross-teach through Dice on each other's
@@ -624,36 +594,20 @@ class CnnMeetVitTrainer(_TapedStep):
     before ``iter_num`` is incremented (:347-348).  The two ramp weights are host floats of ``iter_num`` (no host
     sync: ``iter_num`` is the trainer's own counter)."""
 
+    TRAIN_MODE = "train_cnn_meet_vit runs all three networks in train mode"
+
     def __init__(self, model1, model2, ema_model, *, labeled_bs, num_classes, base_lr=0.01, max_iterations=30000,
                  ema_decay=0.99, consistency=0.1, consistency_rampup=200.0, seed=1337, iter_num=0, momentum=0.9,
                  weight_decay=1e-4, process_group=None, use_tape=None):
         if model2.flat_param.numel() != ema_model.flat_param.numel():
             raise RuntimeError("the teacher is the EMA of model2: same architecture required")
-        # the two ramp weights are HOST floats of iter_num and arguments of the loss tails: the tape is recorded again whenever
-        # they change (every ramp_div = 150 iterations, and at iteration 1000)
-        self.use_tape = STEP_TAPE if use_tape is None else bool(use_tape)
         self._tape_weights = None
         self.model1, self.model2, self.ema_model = model1, model2, ema_model
-        self.labeled_bs, self.num_classes = labeled_bs, num_classes
-        self.hyper = dict(base_lr=float(base_lr), max_iterations=float(max_iterations), ema_decay=float(ema_decay),
-                          consistency=float(consistency), rampup=float(consistency_rampup), ramp_div=150,
-                          cons_start_iter=1000)
-        self.momentum, self.weight_decay = momentum, weight_decay
-        self.pg = process_group
-        self.state = ops.new_step_state()
-        h = self.hyper
-        ops.step_init(self.state, seed, iter_num, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"],
-                      h["rampup"], h["ramp_div"], h["cons_start_iter"])
-        for i, m in enumerate((model1, model2, ema_model)):
-            m.step_state = self.state
-            m.rng_stream = 1 + i
-        self.mom1 = torch.zeros_like(model1.flat_param)
-        self.mom2 = torch.zeros_like(model2.flat_param)
-        self.out1 = torch.zeros(16, dtype=torch.float32, device="cuda")
-        self.out2 = torch.zeros(16, dtype=torch.float32, device="cuda")
-        self.iter_num = iter_num
-        self._ema_in = None
-        self._side = None
+        self._setup((model1, model2), (ema_model,), (1, 2, 3), labeled_bs=labeled_bs, num_classes=num_classes,
+                    base_lr=base_lr, max_iterations=max_iterations, ema_decay=ema_decay, consistency=consistency,
+                    consistency_rampup=consistency_rampup, cons_start_iter=1000, seed=seed, iter_num=iter_num,
+                    momentum=momentum, weight_decay=weight_decay, process_group=process_group, use_tape=use_tape)
+        # model1 is the side-stream student (_backward_pair): its tail bucket is deferred
         self._bucketers = (make_bucketer(model1, process_group, defer_tail=TWO_STREAM),
                            make_bucketer(model2, process_group))
 
@@ -664,82 +618,48 @@ class CnnMeetVitTrainer(_TapedStep):
         return 7 * w, (w if self.iter_num >= h["cons_start_iter"] else 0.0)
 
     def step(self, volume_batch, label_batch, noise=None):
-        if not (self.model1.training and self.model2.training and self.ema_model.training):
-            raise RuntimeError("train_cnn_meet_vit runs all three networks in train mode")
-        if self.use_tape and noise is None:
+        return self._step(volume_batch, label_batch, noise)
+
+    def _replay(self, volume, label, noise):
+        # the two ramp weights are HOST floats of iter_num and arguments of the loss tails: the tape is recorded again whenever
+        # they change (every ramp_div = 150 iterations, and at iteration 1000)
+        if self.use_tape:
             w = self.weights()
             if self._tape is not None and w != self._tape_weights:
                 self._tape, self._tape_warm = None, self.TAPE_WARMUP       # plans and buffers are warm: record at once
             if self._tape is None and self._tape_warm >= self.TAPE_WARMUP:
                 self._tape_weights = w
-            self._tape_step(lambda v, l: self._run(v, l, None), (volume_batch, label_batch))
-        else:
-            self._run(volume_batch, label_batch, noise)
-        self.iter_num += 1
-        return self.out1, self.out2
+        super()._replay(volume, label, noise)
 
     def _run(self, volume_batch, label_batch, noise):
         L = self.labeled_bs
-        unl = volume_batch[L:].contiguous()
-        if self._ema_in is None or self._ema_in.shape != unl.shape:
-            self._ema_in = torch.empty_like(unl)
-        if noise is None:
-            ops.teacher_noise(unl, self._ema_in, self.state)
+        ema_in = self._noised(volume_batch[L:].contiguous(), noise)
+        fwd1 = lambda: self.model1.forward_raw(volume_batch)
+        fwd2 = lambda: self.model2.forward_raw(volume_batch)
+        teacher = lambda: self.ema_model.forward_raw(ema_in, no_backward=True)
+        if TWO_STREAM:
+            # three independent forwards: the CNN student and the (half-batch) teacher beside the Transformer student --
+            # roughly equal work; later the CNN's backward beside the Transformer's
+            (o1, t), o2 = self._beside(lambda: (fwd1(), teacher()), fwd2)
         else:
-            torch.add(unl, noise, out=self._ema_in)     # injected noise: parity tests only
-        two = TWO_STREAM
-        if two:
-            # three independent forwards: the CNN student and the (half-batch) teacher on a side stream beside the
-            # Transformer student -- roughly equal work; later the CNN's backward beside the Transformer's.  Bit-identical
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = _lib.side_stream("side")
-            _lib.wait_stream(self._side, main)
-            with torch.cuda.stream(self._side):
-                o1 = self.model1.forward_raw(volume_batch)
-                t = self.ema_model.forward_raw(self._ema_in, no_backward=True)
-            o2 = self.model2.forward_raw(volume_batch)
-            _lib.wait_stream(main, self._side)
-        else:
-            o1 = self.model1.forward_raw(volume_batch)
-            o2 = self.model2.forward_raw(volume_batch)
-            t = self.ema_model.forward_raw(self._ema_in, no_backward=True)
+            o1, o2, t = fwd1(), fwd2(), teacher()       # on one stream this step keeps the order of its networks
         lab = label_batch[:L].contiguous()
         w_cps, w_mt = self.weights()
         ops.cross_teaching_tail(o1, o2, lab, L, self.out1, dlogits=self.model1.logits_grad_buffer(),
                                 cons_weight=w_cps, teacher=t, mt_weight=w_mt)
         ops.cross_teaching_tail(o2, o1, lab, L, self.out2, dlogits=self.model2.logits_grad_buffer(),
                                 cons_weight=w_cps, teacher=t, mt_weight=w_mt)
-        b1, b2 = self._bucketers
-        if two:
-            # model1's backward is enqueued first, on the side stream: with bucketers its tail bucket is deferred to
-            # finish() (defer_tail), as for the side-stream student of cross teaching
-            _lib.wait_stream(self._side, main)
-            if b1 is not None:
-                _lib.tape_call(b1.begin)
-                _lib.tape_call(b2.begin)
-            with torch.cuda.stream(self._side):
-                self.model1.backward_raw(on_progress=None if b1 is None else b1.advance)
-            self.model2.backward_raw(on_progress=None if b2 is None else b2.advance)
-            _lib.wait_stream(main, self._side)
-            if b1 is not None:
-                scales = [_lib.tape_call(b1.finish), _lib.tape_call(b2.finish)]
-            else:
-                scales = [_lib.tape_call(dist.sync_gradients, m.flat_grad, self.pg) for m in (self.model1, self.model2)]
+        if TWO_STREAM:
+            scales = self._backward_pair(side=0)
         else:
-            scales = [backward_and_sync(self.model1, self.pg, b1), backward_and_sync(self.model2, self.pg, b2)]
-        for m, mom, ema, scale in ((self.model1, self.mom1, None, scales[0]),
-                                   (self.model2, self.mom2, self.ema_model.flat_param, scales[1])):
-            ops.sgd_ema_step(m.flat_param, m.flat_grad, mom, ema, momentum=self.momentum,
-                             weight_decay=self.weight_decay, grad_scale=scale, state=self.state)
-        h = self.hyper
-        ops.step_advance(self.state, h["base_lr"], h["max_iterations"], h["ema_decay"], h["consistency"], h["rampup"],
-                         h["ramp_div"], h["cons_start_iter"])
+            # on one stream each student's exchange is finished before the other's backward begins (cross teaching keeps
+            # both in flight instead): begin1, backward1, finish1, begin2, backward2, finish2
+            scales = [backward_and_sync(m, self.pg, b) for m, b in zip(self._students, self._bucketers)]
+        self._finish_step((self.model1, self.mom1, None, scales[0]),
+                          (self.model2, self.mom2, self.ema_model.flat_param, scales[1]))
 
     def losses(self):
-        a, b = self.out1.cpu(), self.out2.cpu()
-        return dict(loss=a[0].item() + b[0].item(), model1_loss=a[0].item(), model2_loss=b[0].item(),
-                    loss1_ce=a[1].item(), loss1_dice=a[2].item(), pseudo_supervision1=a[3].item(),
-                    consistency_loss1=a[5].item(), loss2_ce=b[1].item(), loss2_dice=b[2].item(),
-                    pseudo_supervision2=b[3].item(), consistency_loss2=b[5].item(),
-                    consistency_weight=a[4].item() / 7.0, mt_weight=a[6].item())
+        a, b, d = self._pair_losses()
+        d.update(consistency_loss1=a[5].item(), consistency_loss2=b[5].item(),
+                 consistency_weight=a[4].item() / 7.0, mt_weight=a[6].item())
+        return d

@@ -126,6 +126,58 @@ def test_teacher_on_side_stream_is_bit_identical(monkeypatch):
         assert all(torch.equal(a, b) for a, b in zip(o[3], outs[0][3]))
 
 
+@pytest.mark.parametrize("kind", ["uamt", "ict", "cross_dice", "cross_ce"])
+def test_fork_join_of_every_other_trainer_is_bit_identical(kind, monkeypatch):
+    """The other users of the side stream -- UA-MT (five teacher forwards), ICT (two teacher forwards), cross teaching and
+    cross pseudo supervision (the second student's forward AND backward) -- with MIS_TWO_STREAM off and on, eager: the
+    scalars of every one of four steps, every student's weights and momentum, the teacher's weights and buffers are
+    bit-identical."""
+    from mis_hip import step
+    from networks.net_factory import net_factory
+    from oracle import filler
+    from oracle.nets import OracleUNet2D
+    unet = (lambda: net_factory("unet", 1, 4)), filler.fill_state_dict(OracleUNet2D(1, 4).new_state())
+    two_students = kind.startswith("cross")
+    if two_students:
+        from config import lite_config
+        from networks.vision_transformer import SwinUnet
+        from oracle.swin import OracleSwinUnet
+        swin = (lambda: SwinUnet(lite_config(), num_classes=4)), filler.fill_state_dict(OracleSwinUnet(4).new_state())
+        recipes, shape = (unet, swin), (4, 1, 224, 224)
+    else:
+        recipes, shape = (unet, unet), (4, 1, 64, 64)
+    vol = filler.image(shape, "volume").cuda()
+    lab = filler.labels((shape[0],) + shape[2:], 4, torch.uint8).cuda()
+    res = []
+    for two in (False, True):
+        monkeypatch.setattr(step, "TWO_STREAM", two)
+        nets = []
+        for make, sd in recipes:
+            nets.append(make())
+            nets[-1].load_state_dict(sd)
+            nets[-1].train()
+        if two_students:
+            tr = step.CrossTeachingTrainer(nets[0], nets[1], labeled_bs=2, num_classes=4, seed=7, iter_num=998,
+                                           pseudo_ce=(kind == "cross_ce"), use_tape=False)
+            students, teachers, moms = nets, [], [tr.mom1, tr.mom2]
+        else:
+            cls = step.UAMTTrainer if kind == "uamt" else step.ICTTrainer
+            tr = cls(nets[0], nets[1], labeled_bs=2, num_classes=4, seed=7, iter_num=998, use_tape=False)
+            students, teachers, moms = nets[:1], nets[1:], [tr.momentum_buf]
+        got = []
+        for _ in range(4):
+            out = tr.step(vol, lab)
+            got += [o.clone() for o in (out if two_students else (out,))]
+        torch.cuda.synchronize()
+        assert tr._tape is None
+        got += [s.flat_param.clone() for s in students] + [m.clone() for m in moms]
+        got += [t.flat_param.clone() for t in teachers] + [b.clone() for t in teachers for _, b in t.named_buffers()]
+        res.append(got)
+    assert len(res[0]) == len(res[1]) >= 4 + 2
+    for a, b in zip(*res):
+        assert torch.equal(a, b)            # (a NaN anywhere fails too)
+
+
 @pytest.mark.parametrize("script,extra", [
     ("train_mean_teacher_2D.py", ["--patch_size", "64", "64", "--batch_size", "4", "--labeled_bs", "2"]),
     ("train_mean_teacher_3D.py", ["--patch_size", "32", "32", "32", "--batch_size", "2", "--labeled_bs", "1"]),
