@@ -131,6 +131,9 @@ PROTOTYPES = {
     "mis_dct_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_i, c_f, c_f, c_p, c_p,
                            c_ll, c_p, c_ll, c_p, c_ll, c_p]),
     "mis_grad_combine": (c_i, [c_p, c_p, c_ll, c_i, c_p]),
+    "mis_triple_view_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
+    "mis_triple_view_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_p, c_p, c_p,
+                                   c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p]),
     "mis_cross_pseudo_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_i, c_p, c_p, c_ll,
                                     c_p, c_ll, c_p]),
     "mis_cross_pseudo_mt_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_f, c_p,

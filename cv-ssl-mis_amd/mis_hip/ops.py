@@ -895,6 +895,37 @@ def cross_teaching_tail(own, other, label, labeled_bs, out, dlogits=None, cons_w
              "mis_cross_pseudo_tail")
 
 
+def triple_view_tail(z1, z2, z3, label, labeled_bs, outs, dlogits=None, cons_weight=0.0, state=None):
+    """Triple-view loss tail of three students' logits [B,C,D,H,W]: for each, 0.5*(CE+Dice) on the labeled half + w * Dice
+    against the arg-max pseudo labels of EACH of the other two on the unlabeled half (reference
+    code/train_tripleview_2D(demo).py:290-335).  ``outs``: three buffers of >= 6 floats, [loss_m, loss_ce, loss_dice,
+    pseudo_supervision_a, consistency_weight, pseudo_supervision_b]; ``dlogits``: three gradient buffers or None."""
+    L = _l.load()
+    B, C, D, H, W, S, bs1 = _geom(z1)
+    bss = [bs1]
+    for z in (z2, z3):
+        Bo, Co, _, _, _, So, bs = _geom(z)
+        assert (Bo, Co, So) == (B, C, S)
+        bss.append(bs)
+    assert len(outs) == 3 and all(o.dtype == torch.float32 and o.numel() >= 6 for o in outs)
+    _l.require_gpu(label, state, *outs)
+    assert label.is_contiguous() and label.dtype in (torch.uint8, torch.int64) and label.numel() >= labeled_bs * S
+    lb = 1 if label.dtype == torch.uint8 else 8
+    if dlogits is None:
+        dlogits, dbs = (None, None, None), (0, 0, 0)
+    else:
+        assert len(dlogits) == 3
+        dg = [_geom(d) for d in dlogits]
+        assert all((g[0], g[1], g[5]) == (B, C, S) for g in dg)
+        dbs = [g[6] for g in dg]
+    ws = scratch(L.mis_triple_view_tail_workspace_bytes(B, C, S), "tail")
+    _l.check(L.mis_triple_view_tail(_l.ptr(z1), bss[0], _l.ptr(z2), bss[1], _l.ptr(z3), bss[2], _l.ptr(label), lb, B,
+                                    labeled_bs, C, S, cons_weight, _l.ptr(state), _l.ptr(outs[0]), _l.ptr(outs[1]),
+                                    _l.ptr(outs[2]), _l.ptr(dlogits[0]), dbs[0], _l.ptr(dlogits[1]), dbs[1],
+                                    _l.ptr(dlogits[2]), dbs[2], _l.ptr(ws), ws.numel(), _l.stream_ptr()),
+             "mis_triple_view_tail")
+
+
 # ------------------------------------------------------------ optimizer / rng
 def sgd_ema_step(param, grad, momentum_buf, ema_param, lr=0.0, momentum=0.9, weight_decay=1e-4, ema_alpha=0.99,
                  grad_scale=1.0, state=None):

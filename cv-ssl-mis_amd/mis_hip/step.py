@@ -1,6 +1,6 @@
 """The training steps, each one fused device-side sequence replacing a loop body of the reference.
 
-Six methods share one skeleton (``_Step``); DESIGN.md has a section per method:
+Seven methods share one skeleton (``_Step``); DESIGN.md has a section per method:
 
     MeanTeacherTrainer      student + EMA teacher on the noised unlabeled half (code/train_mean_teacher_{2D,3D}.py)
     UAMTTrainer             + T = 8 MC-dropout teacher passes, the entropy of their mean masks the consistency term
@@ -8,6 +8,7 @@ Six methods share one skeleton (``_Step``); DESIGN.md has a section per method:
     DeepCoTrainingTrainer   one network, a pass on the batch and one on its rotated unlabeled half
     CrossTeachingTrainer    two students teach each other through arg-max pseudo labels (``pseudo_ce``: CPS)
     CnnMeetVitTrainer       cross teaching + an EMA teacher of the second student
+    TripleViewTrainer       three students, each taught by the arg-max pseudo labels of both others; one joint loss tail
 
 The skeleton of a step:
 
@@ -18,7 +19,7 @@ The skeleton of a step:
 
 A trainer's ``_run`` is what is particular to its method: which inputs it builds, which forwards run, which tail is called.
 Nothing in the sequence allocates or synchronises with the host: scalars stay in a small device buffer (``trainer.out``,
-or ``out1`` / ``out2`` with two students) that the caller reads when it wants to log (the reference forces >= 3 + C host
+or ``out1`` / ``out2`` (/ ``out3``) with two (three) students) that the caller reads when it wants to log (the reference forces >= 3 + C host
 syncs per step).  The RNG offset, learning rate, EMA alpha and the consistency weight live in a
 device-resident ``MisStepState``, so a recorded step stays correct when it is replayed: from a launch tape (``_TapedStep``,
 every trainer but UA-MT), or, for the Mean-Teacher step, from a captured hipGraph (``use_graph=True``).
@@ -119,7 +120,8 @@ class _Step(_TapedStep):
         ops.step_init(self.state, seed, iter_num, **self.hyper)
         for net, stream in zip(self._nets, rng_streams):
             net.step_state, net.rng_stream = self.state, stream
-        names = (("momentum_buf", "out"),) if len(students) == 1 else (("mom1", "out1"), ("mom2", "out2"))
+        names = ((("momentum_buf", "out"),) if len(students) == 1 else
+                 tuple((f"mom{i}", f"out{i}") for i in range(1, len(students) + 1)))
         for net, (mom, out) in zip(students, names):
             setattr(self, mom, torch.zeros_like(net.flat_param))
             setattr(self, out, torch.zeros(16, dtype=torch.float32, device="cuda"))
@@ -136,7 +138,9 @@ class _Step(_TapedStep):
         else:
             self._run(volume, label, *inject)
         self.iter_num += 1
-        return self.out if len(self._students) == 1 else (self.out1, self.out2)
+        if len(self._students) == 1:
+            return self.out
+        return tuple(getattr(self, f"out{i}") for i in range(1, len(self._students) + 1))
 
     def _replay(self, volume, label, *none):
         """A step on its own device-side draws: through the launch tape unless the trainer is eager."""
@@ -208,6 +212,12 @@ class _Step(_TapedStep):
 
         self._beside(lambda: nets[side].backward_raw(on_progress=bs[side].advance), main_backward)
         return [_lib.tape_call(b1.finish), _lib.tape_call(b2.finish)]
+
+    def _backward_beside(self, side, main):
+        """The backwards of the students ``side`` (indices into the students), one after another on the side stream, beside
+        those of the students ``main`` on the main stream.  No exchange is begun here: the caller follows with blocking ones."""
+        nets = self._students
+        self._beside(lambda: [nets[i].backward_raw() for i in side], lambda: [nets[i].backward_raw() for i in main])
 
     def _finish_step(self, *updates):
         """Fused SGD (+ EMA of the teacher) for every ``(student, momentum buffer, teacher parameters or None, grad scale)``, then
@@ -662,4 +672,73 @@ class CnnMeetVitTrainer(_Step):
         a, b, d = self._pair_losses()
         d.update(consistency_loss1=a[5].item(), consistency_loss2=b[5].item(),
                  consistency_weight=a[4].item() / 7.0, mt_weight=a[6].item())
+        return d
+
+
+def triple_split(batch_size, labeled_bs):
+    """U = batch_size - labeled_bs, the unlabeled samples of a triple-view step.  ValueError unless
+    1 <= labeled_bs < batch_size: CE / Dice need a labeled sample, the six pseudo-label terms an unlabeled one."""
+    B, L = int(batch_size), int(labeled_bs)
+    if not 1 <= L < B:
+        raise ValueError(f"triple-view training needs 1 <= labeled_bs < batch_size; got batch_size={B}, labeled_bs={L}")
+    return B - L
+
+
+class TripleViewTrainer(_Step):
+    """Triple-view training (reference code/train_tripleview_2D(demo).py:290-354): three students see the whole batch, each
+    is supervised on the labeled half and, on the unlabeled half, by the arg-max pseudo labels (Dice) of BOTH others;
+    ``loss = model1_loss + model2_loss + model3_loss``, three SGD steps, no EMA, no noise, no ``iter_num < 1000`` gate.  The
+    learning rate is computed before ``iter_num`` is incremented (:346-347).  The reference builds two ``net_factory``
+    networks and a SwinUnet; any three networks of one ``num_classes`` and input shape do.
+
+    One joint loss tail (``mis_triple_view_tail``) serves the three students: the pseudo labels are detached, so each
+    student's logits gradient is that of its own loss.  model3 runs on the main stream, model1 then model2 beside it on
+    the side stream, forward and backward.  With a process group the three flat gradient buffers are exchanged by three
+    blocking all-reduces after the backwards: this trainer does not overlap the exchange with the backward."""
+
+    TRAIN_MODE = "triple-view training trains all three networks (train mode)"
+
+    def __init__(self, model1, model2, model3, *, labeled_bs, num_classes, base_lr=0.01, max_iterations=30000,
+                 consistency=0.1, consistency_rampup=200.0, seed=1337, iter_num=0, momentum=0.9, weight_decay=1e-4,
+                 process_group=None, use_tape=None):
+        self.model1, self.model2, self.model3 = model1, model2, model3
+        self._setup((model1, model2, model3), (), (1, 2, 3), labeled_bs=int(labeled_bs), num_classes=num_classes,
+                    base_lr=base_lr, max_iterations=max_iterations, consistency=consistency,
+                    consistency_rampup=consistency_rampup, lr_post_increment=True, seed=seed, iter_num=iter_num,
+                    momentum=momentum, weight_decay=weight_decay, process_group=process_group, use_tape=use_tape)
+
+    def step(self, volume_batch, label_batch):
+        """One iteration on device tensors [B, 1, H, W] / [B, H, W]; returns the three device scalar buffers ``[loss_m,
+        loss_ce, loss_dice, pseudo_supervision_a, consistency_weight, pseudo_supervision_b, ...]`` (no host sync)."""
+        if volume_batch.dim() != 4 or label_batch.dim() != 3:
+            raise ValueError(f"triple-view training runs the 2-D networks on [B, C, H, W] / [B, H, W]; got "
+                             f"{tuple(volume_batch.shape)} / {tuple(label_batch.shape)}")
+        triple_split(volume_batch.shape[0], self.labeled_bs)
+        return self._step(volume_batch, label_batch)
+
+    def _run(self, volume_batch, label_batch):
+        L = self.labeled_bs
+        nets = self._students
+        fwd = [lambda net=net: net.forward_raw(volume_batch) for net in nets]
+        if TWO_STREAM:
+            # the students only meet in the loss tail: model1 then model2 beside model3
+            (o1, o2), o3 = self._beside(lambda: (fwd[0](), fwd[1]()), fwd[2])
+        else:
+            o1, o2, o3 = fwd[0](), fwd[1](), fwd[2]()       # on one stream this step keeps the order of its networks
+        ops.triple_view_tail(o1, o2, o3, label_batch[:L].contiguous(), L, (self.out1, self.out2, self.out3),
+                             dlogits=[net.logits_grad_buffer() for net in nets], state=self.state)
+        self._backward_beside(side=(0, 1), main=(2,))
+        scales = [_lib.tape_call(dist.sync_gradients, net.flat_grad, self.pg) for net in nets]
+        self._finish_step(*((net, mom, None, scale)
+                            for net, mom, scale in zip(nets, (self.mom1, self.mom2, self.mom3), scales)))
+
+    def losses(self):
+        """Host copies of the last step's scalars (three small D2H)."""
+        d = {}
+        for m, out in enumerate((self.out1, self.out2, self.out3), start=1):
+            o = out.cpu()
+            d.update({f"model{m}_loss": o[0].item(), f"loss{m}_ce": o[1].item(), f"loss{m}_dice": o[2].item(),
+                      f"pseudo_supervision{m}a": o[3].item(), f"pseudo_supervision{m}b": o[5].item(),
+                      "consistency_weight": o[4].item()})
+        d["loss"] = d["model1_loss"] + d["model2_loss"] + d["model3_loss"]
         return d

@@ -431,6 +431,67 @@ def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=
     return "Training Finished!"
 
 
+def run_triple_view(args, make_models, log_every=1, label_dtype=torch.uint8, snapshot_fmt="../model/{}_{}/{}"):
+    """Hot loop of train_tripleview_2D(demo).py:283-491: three students (``make_models``: three factories), no teacher.  The
+    same scalars and log line as the reference (:356-362), all three models validated every 200 iterations (:379-471), the
+    periodic checkpoints every 3000 (:473-484)."""
+    from .step import TripleViewTrainer, triple_split
+    triple_split(args.batch_size, args.labeled_bs)
+    rank, world, _ = setup_distributed()
+    seed_everything(args)
+    snapshot_path = open_snapshot(args, rank, snapshot_fmt)
+    models = [make() for make in make_models]
+    if world > 1:
+        broadcast_model_state(*models)
+    for m in models:
+        m.train()
+    trainer = TripleViewTrainer(*models, labeled_bs=args.labeled_bs, num_classes=args.num_classes, base_lr=args.base_lr,
+                                max_iterations=args.max_iterations, consistency=args.consistency,
+                                consistency_rampup=args.consistency_rampup, seed=args.seed + rank)
+    loader, source = make_loader(args, label_dtype, rank, world)
+    if rank == 0:
+        logging.info("{} iterations per epoch ({})".format(len(loader), source))
+    scalars = ScalarLog(snapshot_path, enabled=(rank == 0))
+    validator = Validator(args, snapshot_path, scalars, rank, world, process_group=trainer.pg)
+    val_models = [('model%d_' % i, 'model%d_' % i, 'best_model%d' % i, m) for i, m in enumerate(models, start=1)]
+    iter_num, t0 = 0, time.time()
+    max_epoch = args.max_iterations // len(loader) + 1
+    for _epoch in range(max_epoch):
+        for sampled_batch in loader:
+            # lr_ as the reference logs it: computed before iter_num is incremented (:346-347)
+            lr_ = args.base_lr * (1.0 - iter_num / args.max_iterations) ** 0.9
+            trainer.step(sampled_batch["image"], sampled_batch["label"])
+            iter_num += 1
+            if rank == 0 and iter_num % log_every == 0:
+                s = trainer.losses()
+                scalars.add_scalar('lr', lr_, iter_num)
+                scalars.add_scalar('consistency_weight/consistency_weight', s["consistency_weight"], iter_num)
+                for i in (1, 2, 3):
+                    scalars.add_scalar('loss/model%d_loss' % i, s["model%d_loss" % i], iter_num)
+                logging.info('iteration %d : model1 loss : %f model2 loss : %f : model3 loss: %f' %
+                             (iter_num, s["model1_loss"], s["model2_loss"], s["model3_loss"]))
+            validator(iter_num, val_models)      # every rank: the validation cases are sharded over the ranks
+            if rank == 0 and iter_num % 3000 == 0:
+                for i, m in enumerate(models, start=1):
+                    path = os.path.join(snapshot_path, 'model%d_iter_%d.pth' % (i, iter_num))
+                    torch.save(m.state_dict(), path)
+                    logging.info("save model%d to %s" % (i, path))
+            if iter_num >= args.max_iterations:
+                break
+        if iter_num >= args.max_iterations:
+            break
+    torch.cuda.synchronize()
+    if rank == 0:
+        dt = time.time() - t0
+        logging.info("%d iterations in %.2f s (%.1f samples/s over %d GPU(s))" %
+                     (iter_num, dt, iter_num * args.batch_size * world / dt, world))
+        validator.finish(val_models)
+        scalars.close()
+    if world > 1:
+        torch.distributed.destroy_process_group()
+    return "Training Finished!"
+
+
 def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, log_every=1, trainer_cls=None,
                  snapshot_fmt="../model/{}_{}_labeled/{}", trainer_kw=None, single_model=False):
     """Hot loop of train_mean_teacher_2D.py:196-312 / train_mean_teacher_3D.py:128-230 (and, with

@@ -397,6 +397,23 @@ int mis_dct_tail(const float* logits_a, long long a_bs, const float* logits_r, l
                  mis_stream_t stream);
 int mis_grad_combine(float* dst, const float* src, long long n, int accumulate, mis_stream_t stream);
 
+/* Triple-view training (code/train_tripleview_2D(demo).py:290-335): three students, one loss tail.
+ * With p_m = softmax(z_m), pseudo_j = argmax(z_j[L:]) (detached, first maximum wins; :307-312) and (a, b) the other two
+ * students in ascending index:
+ *   loss_m = 0.5*(CE + Dice)(z_m[:L], label)                                   (:299-304)
+ *          + w * Dice(p_m[L:], pseudo_a) + w * Dice(p_m[L:], pseudo_b)         (:314-334)
+ * w = state->cons_weight when `state` is given, else cons_weight; there is no gate.  z1..z3: [B][C][S] with their own
+ * batch strides, C in {2, 3, 4}; L == 0 and L == B are allowed (the missing half contributes exactly 0).
+ * out_m (>= 6 floats): loss_m, loss_ce, loss_dice, pseudo_supervision_a, consistency_weight, pseudo_supervision_b.
+ * d_m = d loss_m / d z_m (the pseudo labels carry no gradient); all three given or all three NULL (forward only).
+ * Three launches for the three students: every logit is read once per pass. */
+long long mis_triple_view_tail_workspace_bytes(int B, int C, long long S);
+int mis_triple_view_tail(const float* z1, long long z1_bs, const float* z2, long long z2_bs, const float* z3,
+                         long long z3_bs, const void* label, int label_bytes, int B, int L, int C, long long S,
+                         float cons_weight, const MisStepState* state, float* out1, float* out2, float* out3, float* d1,
+                         long long d1_bs, float* d2, long long d2_bs, float* d3, long long d3_bs, void* workspace,
+                         long long workspace_bytes, mis_stream_t stream);
+
 /* ---- stand-alone loss operators (drop-in utils.losses surface) ----------------------------------------
  * reference: losses.DiceLoss code/utils/losses.py:165-201; losses.softmax_mse_loss :74-91.
  * mis_dice_loss_fwd: probs [B][C][S], label [B][S]; out[0] = loss, out[1+c] = class-wise dice; the
