@@ -15,9 +15,7 @@
 // and out is [W][H] for odd k.  For odd k that is a transpose: the source of an output tile is a tile of the input
 // whose rows are the output's columns, so both kernels below stage a tile in LDS (rows padded by one float: 64
 // four-byte banks) and read and write global memory row by row.
-#include "common.h"
-
-#define MIS_MAXC 8
+#include "tail.h"
 
 namespace {
 
@@ -87,21 +85,6 @@ __global__ __launch_bounds__(256) void rot90_kernel(const float* __restrict__ in
 // ---------------------------------------------------------------------------------------------------------------------
 // loss tail
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int load_label(const void* lab, int bytes, long long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(lab)[i]
-                      : (int)reinterpret_cast<const long long*>(lab)[i];
-}
-
-__device__ __forceinline__ void softmax_c(const float* z, int C, float* p, float& lse) {
-    float mx = z[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float sum = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-    lse = mx + logf(sum);
-}
-
 struct DArgs {
     const float* a; long long a_bs;      // pass A logits [L + U][C][H][W]
     const float* r; long long r_bs;      // pass R logits [U][C][H][W] (square when k is odd)
@@ -126,21 +109,13 @@ __global__ __launch_bounds__(256) void dct_lab1_kernel(const DArgs a, float* __r
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.a + (long long)b * a.a_bs + u * 4;
         float z[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, S, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float p[C], lse;
-            softmax_c(z[j], C, p, lse);
-            const int y = load_label(a.label, a.label_bytes, (long long)b * S + u * 4 + j);
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if (c == y) { v[0] += lse - z[j][c]; v[1 + 3 * c] += p[c]; v[2 + 3 * c] += 1.f; }
-                v[3 + 3 * c] += p[c] * p[c];
-            }
+            mis_tail_softmax<C>(z[j], p, lse);
+            const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * S + u * 4 + j);
+            mis_tail_labeled_sums<C>(z[j], p, lse, y, v[0], v + 1);
         }
     }
     mis_block_sum<NPL>(v, red);
@@ -163,29 +138,15 @@ __global__ __launch_bounds__(256) void dct_lab2_kernel(const DArgs a, const floa
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.a + (long long)b * a.a_bs + u * 4;
         float z[4][C], o[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, S, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float p[C], g[C], lse;
-            softmax_c(z[j], C, p, lse);
-            const int y = load_label(a.label, a.label_bytes, (long long)b * S + u * 4 + j);
-            float dot = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                g[c] = bc[c] * p[c] + (c == y ? ac[c] : 0.f);
-                dot += g[c] * p[c];
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) o[j][c] = p[c] * (g[c] - dot) + kce * (p[c] - (c == y ? 1.f : 0.f));
+            float p[C], lse;
+            mis_tail_softmax<C>(z[j], p, lse);
+            const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * S + u * 4 + j);
+            mis_tail_labeled_grad<C>(p, y, kce, ac, bc, o[j]);
         }
-        float* __restrict__ ob = da + (long long)b * da_bs + u * 4;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            *reinterpret_cast<float4*>(ob + (long long)c * S) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
+        mis_tail_store4<C>(da + (long long)b * da_bs + u * 4, S, o);
     }
 }
 
@@ -235,8 +196,8 @@ __global__ __launch_bounds__(256) void dct_cons_kernel(const DArgs a, int tiles_
         const long long off = (long long)(ti + i) * W + tj + col;
 #pragma unroll
         for (int c = 0; c < C; ++c) { zr[c] = rb[(long long)c * S + off]; za[c] = t[c][si][sj]; }
-        softmax_c(zr, C, Q, lse);
-        softmax_c(za, C, P, lse);
+        mis_tail_softmax<C>(zr, Q, lse);
+        mis_tail_softmax<C>(za, P, lse);
         if (!GRAD) {
 #pragma unroll
             for (int c = 0; c < C; ++c) { const float d = Q[c] - P[c]; acc += d * d; }
@@ -279,6 +240,10 @@ __global__ __launch_bounds__(256) void dct_cons_kernel(const DArgs a, int tiles_
             if (col < aw) ob[(long long)c * S + (long long)(ar0 + r) * W + ac0 + col] = t[c][r][col];
 }
 
+// the two forms of the consistency kernel under names that MIS_DISPATCH_C can instantiate with the class count alone
+template <int C> constexpr auto dct_cons_sum = dct_cons_kernel<C, false>;
+template <int C> constexpr auto dct_cons_grad = dct_cons_kernel<C, true>;
+
 // out[0]=loss out[1]=loss_ce out[2]=loss_dice out[3]=consistency_loss out[4]=consistency_weight out[5]=k
 // out[6..6+C) = class-wise dice score
 // coef[0]=ce scale, coef[1]=consistency scale, coef[2+2c]=a_c, coef[3+2c]=b_c   (see dct_lab2_kernel)
@@ -289,27 +254,12 @@ struct DFinalArgs {
 };
 
 __global__ __launch_bounds__(256) void dct_final_kernel(const DFinalArgs f) {
-    __shared__ double red[4];
     __shared__ double tot[NPL + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C = f.a.C;
-    for (int i = 0; i < 2 + 3 * C; ++i) {       // 1 + 3C labeled sums, then the squared-error sum
-        double s = 0.0;
-        if (i < 1 + 3 * C) {
-            for (int b = threadIdx.x; b < f.blocks_l; b += 256) s += f.part_l[(long long)b * NPL + i];
-        } else {
-            for (int b = threadIdx.x; b < f.blocks_c; b += 256) s += f.part_c[b];
-        }
-        s = mis_wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[i] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    __syncthreads();
+    mis_tail_reduce_parts(f.part_l, f.blocks_l, NPL, 1 + 3 * C, tot);      // 1 + 3C labeled sums,
+    mis_tail_reduce_parts(f.part_c, f.blocks_c, 1, 1, tot + 1 + 3 * C);    // then the squared-error sum
     if (threadIdx.x != 0) return;
     const DArgs& a = f.a;
-    const double smooth = 1e-5;
     const double S = (double)a.H * (double)a.W;
     const double nlab = (double)a.L * S;
     const double nun = (double)a.U * (double)C * S;
@@ -320,13 +270,12 @@ __global__ __launch_bounds__(256) void dct_final_kernel(const DFinalArgs f) {
     const double mse = gate != 0.f ? tot[1 + 3 * C] / nun : 0.0;   // gated off: reads 0, like mis_loss_tail / mis_ict_tail
     double dice = 0.0;
     for (int c = 0; c < C; ++c) {
-        const double I = tot[1 + 3 * c], Y = tot[2 + 3 * c], Z = tot[3 + 3 * c];
-        const double num = 2.0 * I + smooth, den = Z + Y + smooth;
-        const double dl = 1.0 - num / den;
+        double dl, ac, bc;
+        mis_tail_dice_coef(tot[1 + 3 * c], tot[2 + 3 * c], tot[3 + 3 * c], 0.5 * f.loss_scale, C, dl, ac, bc);
         dice += dl;
         f.out[6 + c] = (float)(1.0 - dl);
-        f.coef[2 + 2 * c] = (float)(f.loss_scale * (-1.0 / C) / den);
-        f.coef[3 + 2 * c] = (float)(f.loss_scale * (1.0 / C) * num / (den * den));
+        f.coef[2 + 2 * c] = (float)ac;
+        f.coef[3 + 2 * c] = (float)bc;
     }
     dice /= C;
     f.out[0] = (float)(0.5 * (dice + ce) + wl * mse);
@@ -336,12 +285,7 @@ __global__ __launch_bounds__(256) void dct_final_kernel(const DFinalArgs f) {
     f.coef[1] = (float)(f.loss_scale * wl / nun);
 }
 
-int lab_blocks(long long L, long long S) {
-    long long b = mis_cdiv(L * (S >> 2), 256 * 4);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+int lab_blocks(long long L, long long S) { return mis_tail_blocks(L * (S >> 2)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // gradient sum over the flat buffer
@@ -363,8 +307,6 @@ __global__ __launch_bounds__(256) void grad_combine1_kernel(float* __restrict__ 
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
         dst[i] = accumulate ? dst[i] + src[i] : src[i];
 }
-
-bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -407,9 +349,9 @@ extern "C" int mis_dct_tail(const float* logits_a, long long a_bs, const float* 
     if ((dA == nullptr) != (dR == nullptr)) return MIS_ERR_ARG;
     if (C != 2 && C != 3 && C != 4) return MIS_ERR_UNSUPPORTED;
     const long long S = (long long)H * W;
-    if (S % 4 || a_bs % 4 || !a16(logits_a)) return MIS_ERR_UNSUPPORTED;
+    if (S % 4 || a_bs % 4 || !mis_aligned16(logits_a)) return MIS_ERR_UNSUPPORTED;
     if (a_bs < (long long)C * S || r_bs < (long long)C * S) return MIS_ERR_ARG;
-    if (dA && (dA_bs % 4 || !a16(dA) || dA_bs < (long long)C * S || dR_bs < (long long)C * S)) return MIS_ERR_UNSUPPORTED;
+    if (dA && (dA_bs % 4 || !mis_aligned16(dA) || dA_bs < (long long)C * S || dR_bs < (long long)C * S)) return MIS_ERR_UNSUPPORTED;
     if (workspace_bytes < mis_dct_tail_workspace_bytes(L, U, C, H, W)) return MIS_ERR_WORKSPACE;
     DArgs a{logits_a, a_bs, logits_r, r_bs, label, label_bytes, L, U, C, H, W, sched, n_sched, state, k_override};
     const int nbl = lab_blocks(L, S);
@@ -420,32 +362,20 @@ extern "C" int mis_dct_tail(const float* logits_a, long long a_bs, const float* 
     float* coef = part_c + nbc;
     const float* ccoef = coef;
     float* no_f = nullptr;
-#define MIS_D1(CC)                                                                                              \
-    case CC:                                                                                                    \
-        hipLaunchKernelGGL(dct_lab1_kernel<CC>, dim3(nbl), dim3(256), 0, stream, a, part_l);                    \
-        hipLaunchKernelGGL((dct_cons_kernel<CC, false>), dim3(nbc), dim3(256), 0, stream, a, tx, ty, ccoef,     \
-                           part_c, no_f, 0LL, no_f, 0LL);                                                       \
-        break;
-    switch (C) { MIS_D1(2) MIS_D1(3) MIS_D1(4) }
-#undef MIS_D1
+    MIS_DISPATCH_C(C, dct_lab1_kernel, nbl, stream, a, part_l)
+    MIS_DISPATCH_C(C, dct_cons_sum, nbc, stream, a, tx, ty, ccoef, part_c, no_f, 0LL, no_f, 0LL)
     DFinalArgs f{part_l, nbl, part_c, nbc, a, cons_weight, loss_scale, out, coef};
     hipLaunchKernelGGL(dct_final_kernel, dim3(1), dim3(256), 0, stream, f);
     if (dA) {
-#define MIS_D2(CC)                                                                                              \
-    case CC:                                                                                                    \
-        hipLaunchKernelGGL(dct_lab2_kernel<CC>, dim3(nbl), dim3(256), 0, stream, a, ccoef, dA, dA_bs);          \
-        hipLaunchKernelGGL((dct_cons_kernel<CC, true>), dim3(nbc), dim3(256), 0, stream, a, tx, ty, ccoef,      \
-                           no_f, dA, dA_bs, dR, dR_bs);                                                         \
-        break;
-        switch (C) { MIS_D2(2) MIS_D2(3) MIS_D2(4) }
-#undef MIS_D2
+        MIS_DISPATCH_C(C, dct_lab2_kernel, nbl, stream, a, ccoef, dA, dA_bs)
+        MIS_DISPATCH_C(C, dct_cons_grad, nbc, stream, a, tx, ty, ccoef, no_f, dA, dA_bs, dR, dR_bs)
     }
     return mis_launch_status();
 }
 
 extern "C" int mis_grad_combine(float* dst, const float* src, long long n, int accumulate, hipStream_t stream) {
     if (!dst || !src || n <= 0) return MIS_ERR_ARG;
-    const bool vec = n % 4 == 0 && a16(dst) && a16(src);
+    const bool vec = n % 4 == 0 && mis_aligned16(dst) && mis_aligned16(src);
     long long nb = mis_cdiv(vec ? n >> 2 : n, 256);
     if (nb > 4096) nb = 4096;
     if (vec)

@@ -12,9 +12,7 @@
 // The tail has the two-pass structure of loss_tail.hip: pass 1 -> fixed-order partial sums per workgroup (double in
 // the last stage), one-workgroup finalize -> scalars and gradient coefficients, pass 2 -> dlogits.  The mixed
 // target is formed in registers from the two teacher logit tensors and never materialised.
-#include "common.h"
-
-#define MIS_MAXC 8
+#include "tail.h"
 
 namespace {
 
@@ -112,21 +110,6 @@ __global__ __launch_bounds__(256) void ict_mix1_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------------
 // loss tail
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int load_label(const void* lab, int bytes, long long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(lab)[i]
-                      : (int)reinterpret_cast<const long long*>(lab)[i];
-}
-
-__device__ __forceinline__ void softmax_c(const float* z, int C, float* p, float& lse) {
-    float mx = z[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float sum = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-    lse = mx + logf(sum);
-}
-
 struct IArgs {
     const float* s; long long s_bs;      // student logits [L + M][C][S]
     const float* t0; long long t0_bs;    // teacher logits of x0 [M][C][S]
@@ -143,19 +126,14 @@ __device__ __forceinline__ void mixed_target(const IArgs& a, int m, long long u,
     const float* __restrict__ b0 = a.t0 + (long long)m * a.t0_bs + u * 4;
     const float* __restrict__ b1 = a.t1 + (long long)m * a.t1_bs + u * 4;
     float z0[4][C], z1[4][C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float4 v0 = *reinterpret_cast<const float4*>(b0 + (long long)c * a.S);
-        const float4 v1 = *reinterpret_cast<const float4*>(b1 + (long long)c * a.S);
-        z0[0][c] = v0.x; z0[1][c] = v0.y; z0[2][c] = v0.z; z0[3][c] = v0.w;
-        z1[0][c] = v1.x; z1[1][c] = v1.y; z1[2][c] = v1.z; z1[3][c] = v1.w;
-    }
+    mis_tail_load4<C>(b0, a.S, z0);
+    mis_tail_load4<C>(b1, a.S, z1);
     const float l = a.lam[m];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float p0[C], p1[C], lse;
-        softmax_c(z0[j], C, p0, lse);
-        softmax_c(z1[j], C, p1, lse);
+        mis_tail_softmax<C>(z0[j], p0, lse);
+        mis_tail_softmax<C>(z1[j], p1, lse);
 #pragma unroll
         for (int c = 0; c < C; ++c) q[j][c] = mix1(p0[c], p1[c], l);
     }
@@ -176,22 +154,14 @@ __global__ __launch_bounds__(256) void ict_pass1_kernel(const IArgs a, float* __
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.s + (long long)b * a.s_bs + u * 4;
         float z[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * a.S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, a.S, z);
         if (b < a.L) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float p[C], lse;
-                softmax_c(z[j], C, p, lse);
-                const int y = load_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    if (c == y) { v[0] += lse - z[j][c]; v[2 + 3 * c] += p[c]; v[2 + 3 * c + 1] += 1.f; }
-                    v[2 + 3 * c + 2] += p[c] * p[c];
-                }
+                mis_tail_softmax<C>(z[j], p, lse);
+                const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
+                mis_tail_labeled_sums<C>(z[j], p, lse, y, v[0], v + 2);
             }
         } else {
             float q[4][C];
@@ -199,7 +169,7 @@ __global__ __launch_bounds__(256) void ict_pass1_kernel(const IArgs a, float* __
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float p[C], lse;
-                softmax_c(z[j], C, p, lse);
+                mis_tail_softmax<C>(z[j], p, lse);
 #pragma unroll
                 for (int c = 0; c < C; ++c) { const float d = p[c] - q[j][c]; v[1] += d * d; }
             }
@@ -222,21 +192,9 @@ struct IFinalArgs {
 };
 
 __global__ __launch_bounds__(256) void ict_final_kernel(const IFinalArgs a) {
-    __shared__ double red[4];
     __shared__ double tot[NPART];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = 0; i < 2 + 3 * a.C; ++i) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < a.blocks; b += 256) s += a.part[(long long)b * NPART + i];
-        s = mis_wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[i] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    __syncthreads();
+    mis_tail_reduce_parts(a.part, a.blocks, NPART, 2 + 3 * a.C, tot);
     if (threadIdx.x != 0) return;
-    const double smooth = 1e-5;
     const double nlab = (double)a.L * (double)a.S;
     const double nun = (double)a.M * (double)a.C * (double)a.S;
     const float w = a.st ? a.st->cons_weight : a.cons_weight;
@@ -245,13 +203,12 @@ __global__ __launch_bounds__(256) void ict_final_kernel(const IFinalArgs a) {
     const double mse = (a.M > 0 && gate != 0.f) ? tot[1] / nun : 0.0;
     double dice = 0.0;
     for (int c = 0; c < a.C; ++c) {
-        const double I = tot[2 + 3 * c], Y = tot[3 + 3 * c], Z = tot[4 + 3 * c];
-        const double num = 2.0 * I + smooth, den = Z + Y + smooth;
-        const double dl = 1.0 - num / den;
+        double dl, ac, bc;
+        mis_tail_dice_coef(tot[2 + 3 * c], tot[3 + 3 * c], tot[4 + 3 * c], 0.5 * a.loss_scale, a.C, dl, ac, bc);
         dice += dl;
         a.out[5 + c] = (float)(1.0 - dl);
-        a.coef[2 + 2 * c] = (float)(a.loss_scale * (-1.0 / a.C) / den);
-        a.coef[3 + 2 * c] = (float)(a.loss_scale * (1.0 / a.C) * num / (den * den));
+        a.coef[2 + 2 * c] = (float)ac;
+        a.coef[3 + 2 * c] = (float)bc;
     }
     dice = a.L > 0 ? dice / a.C : 0.0;
     a.out[0] = (float)(0.5 * (dice + ce) + (double)w * mse);
@@ -274,18 +231,15 @@ __global__ __launch_bounds__(256) void ict_pass2_kernel(const IArgs a, const flo
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.s + (long long)b * a.s_bs + u * 4;
         float z[4][C], o[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * a.S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, a.S, z);
         if (b < a.L) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float p[C], g[C], lse;
-                softmax_c(z[j], C, p, lse);
-                const int y = load_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
-                float dot = 0.f;
+                float p[C], lse;
+                mis_tail_softmax<C>(z[j], p, lse);
+                const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
+                // not mis_tail_labeled_grad: its fmaf would fuse a product that this file, built without contraction, rounds
+                float g[C], dot = 0.f;
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     g[c] = bc[c] * p[c] + (c == y ? ac[c] : 0.f);
@@ -301,7 +255,7 @@ __global__ __launch_bounds__(256) void ict_pass2_kernel(const IArgs a, const flo
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float p[C], g[C], lse;
-                softmax_c(z[j], C, p, lse);
+                mis_tail_softmax<C>(z[j], p, lse);
                 float dot = 0.f;
 #pragma unroll
                 for (int c = 0; c < C; ++c) { g[c] = kmse * (p[c] - q[j][c]); dot += g[c] * p[c]; }
@@ -309,21 +263,11 @@ __global__ __launch_bounds__(256) void ict_pass2_kernel(const IArgs a, const flo
                 for (int c = 0; c < C; ++c) o[j][c] = p[c] * (g[c] - dot);
             }
         }
-        float* __restrict__ ob = ds + (long long)b * ds_bs + u * 4;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            *reinterpret_cast<float4*>(ob + (long long)c * a.S) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
+        mis_tail_store4<C>(ds + (long long)b * ds_bs + u * 4, a.S, o);
     }
 }
 
-int nblocks(long long B, long long S) {
-    long long b = mis_cdiv(B * (S >> 2), 256 * 4);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int nblocks(long long B, long long S) { return mis_tail_blocks(B * (S >> 2)); }
 
 }  // namespace
 
@@ -338,7 +282,7 @@ extern "C" int mis_beta_sample(float* lam, int M, double alpha, unsigned salt, c
 extern "C" int mis_ict_mix(const float* x, float* out, const float* lam, int L, int M, long long n,
                            hipStream_t stream) {
     if (!x || !out || !lam || L < 0 || M <= 0 || n <= 0) return MIS_ERR_ARG;
-    const bool vec = n % 4 == 0 && a16(x) && a16(out);
+    const bool vec = n % 4 == 0 && mis_aligned16(x) && mis_aligned16(out);
     const long long work = (long long)(L + M) * (vec ? n >> 2 : n);
     long long nb = mis_cdiv(work, 256);
     if (nb > 4096) nb = 4096;
@@ -365,28 +309,19 @@ extern "C" int mis_ict_tail(const float* student, long long s_bs, const float* t
     if (M > 0 && (!teacher0 || !teacher1 || !lam)) return MIS_ERR_ARG;
     if (label_bytes != 1 && label_bytes != 8) return MIS_ERR_ARG;
     if (C != 2 && C != 3 && C != 4) return MIS_ERR_UNSUPPORTED;
-    if (S % 4 || s_bs % 4 || !a16(student)) return MIS_ERR_UNSUPPORTED;
+    if (S % 4 || s_bs % 4 || !mis_aligned16(student)) return MIS_ERR_UNSUPPORTED;
     if (s_bs < (long long)C * S) return MIS_ERR_ARG;
-    if (M > 0 && (t0_bs % 4 || t1_bs % 4 || !a16(teacher0) || !a16(teacher1))) return MIS_ERR_UNSUPPORTED;
+    if (M > 0 && (t0_bs % 4 || t1_bs % 4 || !mis_aligned16(teacher0) || !mis_aligned16(teacher1))) return MIS_ERR_UNSUPPORTED;
     if (M > 0 && (t0_bs < (long long)C * S || t1_bs < (long long)C * S)) return MIS_ERR_ARG;
-    if (dlogits && (d_bs % 4 || !a16(dlogits) || d_bs < (long long)C * S)) return MIS_ERR_UNSUPPORTED;
+    if (dlogits && (d_bs % 4 || !mis_aligned16(dlogits) || d_bs < (long long)C * S)) return MIS_ERR_UNSUPPORTED;
     if (workspace_bytes < mis_ict_tail_workspace_bytes(L + M, C, S)) return MIS_ERR_WORKSPACE;
     IArgs a{student, s_bs, teacher0, t0_bs, teacher1, t1_bs, lam, label, label_bytes, L, M, C, S};
     const int nb = nblocks(L + M, S);
     float* part = reinterpret_cast<float*>(workspace);
     float* coef = part + (long long)nb * NPART;
-#define MIS_I1(CC) case CC: hipLaunchKernelGGL(ict_pass1_kernel<CC>, dim3(nb), dim3(256), 0, stream, a, part); break;
-    switch (C) { MIS_I1(2) MIS_I1(3) MIS_I1(4) }
-#undef MIS_I1
+    MIS_DISPATCH_C(C, ict_pass1_kernel, nb, stream, a, part)
     IFinalArgs f{part, nb, C, L, M, S, cons_weight, state, loss_scale, out, coef};
     hipLaunchKernelGGL(ict_final_kernel, dim3(1), dim3(256), 0, stream, f);
-    if (dlogits) {
-#define MIS_I2(CC)                                                                                       \
-    case CC:                                                                                             \
-        hipLaunchKernelGGL(ict_pass2_kernel<CC>, dim3(nb), dim3(256), 0, stream, a, coef, dlogits, d_bs); \
-        break;
-        switch (C) { MIS_I2(2) MIS_I2(3) MIS_I2(4) }
-#undef MIS_I2
-    }
+    if (dlogits) MIS_DISPATCH_C(C, ict_pass2_kernel, nb, stream, a, coef, dlogits, d_bs)
     return mis_launch_status();
 }

@@ -17,9 +17,7 @@
 // a one-workgroup finalize turns them into the four scalars and the per-class
 // Dice coefficients; pass 2 re-reads the logits and writes dlogits.  The
 // softmax tensors are never materialised in HBM.
-#include "common.h"
-
-#define MIS_MAXC 8
+#include "tail.h"
 
 namespace {
 
@@ -32,22 +30,6 @@ struct TailArgs {
     long long S;
     int blocks;                          // pass-1 grid size
 };
-
-__device__ __forceinline__ int load_label(const void* lab, int bytes, long long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(lab)[i]
-                      : (int)reinterpret_cast<const long long*>(lab)[i];
-}
-
-// softmax over C values held in registers
-__device__ __forceinline__ void softmax_c(const float* z, int C, float* p, float& mx, float& lse) {
-    mx = z[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float sum = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-    lse = mx + logf(sum);
-}
 
 // partial layout per block: [0]=ce_sum, [1]=mse_sum, [2+3c+0]=I_c, [2+3c+1]=Y_c, [2+3c+2]=Z_c
 constexpr int NPART = 2 + 3 * MIS_MAXC;
@@ -65,36 +47,24 @@ __global__ __launch_bounds__(256) void tail_pass1_kernel(const TailArgs a, float
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.s + (long long)b * a.s_bs + u * 4;
         float z[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * a.S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, a.S, z);
         if (b < a.L) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float p[C], mx, lse;
-                softmax_c(z[j], C, p, mx, lse);
-                const int y = load_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    if (c == y) { v[0] += lse - z[j][c]; v[2 + 3 * c] += p[c]; v[2 + 3 * c + 1] += 1.f; }
-                    v[2 + 3 * c + 2] += p[c] * p[c];
-                }
+                float p[C], lse;
+                mis_tail_softmax<C>(z[j], p, lse);
+                const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
+                mis_tail_labeled_sums<C>(z[j], p, lse, y, v[0], v + 2);
             }
         } else {
             const float* __restrict__ tb = a.t + (long long)(b - a.L) * a.t_bs + u * 4;
             float zt[4][C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float4 q = *reinterpret_cast<const float4*>(tb + (long long)c * a.S);
-                zt[0][c] = q.x; zt[1][c] = q.y; zt[2][c] = q.z; zt[3][c] = q.w;
-            }
+            mis_tail_load4<C>(tb, a.S, zt);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float p[C], q[C], mx, lse;
-                softmax_c(z[j], C, p, mx, lse);
-                softmax_c(zt[j], C, q, mx, lse);
+                float p[C], q[C], lse;
+                mis_tail_softmax<C>(z[j], p, lse);
+                mis_tail_softmax<C>(zt[j], q, lse);
 #pragma unroll
                 for (int c = 0; c < C; ++c) { const float d = p[c] - q[c]; v[1] += d * d; }
             }
@@ -117,21 +87,9 @@ struct FinalArgs {
 };
 
 __global__ __launch_bounds__(256) void tail_final_kernel(const FinalArgs a) {
-    __shared__ double red[4];
     __shared__ double tot[NPART];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = 0; i < 2 + 3 * a.C; ++i) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < a.blocks; b += 256) s += a.part[(long long)b * NPART + i];
-        s = mis_wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[i] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    __syncthreads();
+    mis_tail_reduce_parts(a.part, a.blocks, NPART, 2 + 3 * a.C, tot);
     if (threadIdx.x != 0) return;
-    const double smooth = 1e-5;
     const double nlab = (double)a.L * (double)a.S;
     const double nun = (double)a.Bu * (double)a.C * (double)a.S;
     const float w = a.st ? a.st->cons_weight : a.cons_weight;
@@ -140,14 +98,12 @@ __global__ __launch_bounds__(256) void tail_final_kernel(const FinalArgs a) {
     const double mse = (a.Bu > 0 && gate != 0.f) ? tot[1] / nun : 0.0;
     double dice = 0.0;
     for (int c = 0; c < a.C; ++c) {
-        const double I = tot[2 + 3 * c], Y = tot[3 + 3 * c], Z = tot[4 + 3 * c];
-        const double num = 2.0 * I + smooth, den = Z + Y + smooth;
-        const double dl = 1.0 - num / den;
+        double dl, ac, bc;   // d(0.5 * dice_mean)/dp_c = a_c*[y==c] + b_c*p_c
+        mis_tail_dice_coef(tot[2 + 3 * c], tot[3 + 3 * c], tot[4 + 3 * c], 0.5 * a.loss_scale, a.C, dl, ac, bc);
         dice += dl;
         a.out[5 + c] = (float)(1.0 - dl);
-        // d(0.5 * dice_mean)/dp_c = a_c*[y==c] + b_c*p_c
-        a.coef[2 + 2 * c] = (float)(a.loss_scale * (-1.0 / a.C) / den);
-        a.coef[3 + 2 * c] = (float)(a.loss_scale * (1.0 / a.C) * num / (den * den));
+        a.coef[2 + 2 * c] = (float)ac;
+        a.coef[3 + 2 * c] = (float)bc;
     }
     dice = a.L > 0 ? dice / a.C : 0.0;
     const double loss = 0.5 * (dice + ce) + (double)w * mse;
@@ -172,40 +128,24 @@ __global__ __launch_bounds__(256) void tail_pass2_kernel(const TailArgs a, const
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.s + (long long)b * a.s_bs + u * 4;
         float z[4][C], o[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * a.S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, a.S, z);
         if (b < a.L) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float p[C], g[C], mx, lse;
-                softmax_c(z[j], C, p, mx, lse);
-                const int y = load_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
-                float dot = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    g[c] = bc[c] * p[c] + (c == y ? ac[c] : 0.f);
-                    dot += g[c] * p[c];
-                }
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    o[j][c] = p[c] * (g[c] - dot) + kce * (p[c] - (c == y ? 1.f : 0.f));
+                float p[C], lse;
+                mis_tail_softmax<C>(z[j], p, lse);
+                const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
+                mis_tail_labeled_grad<C>(p, y, kce, ac, bc, o[j]);
             }
         } else {
             const float* __restrict__ tb = a.t + (long long)(b - a.L) * a.t_bs + u * 4;
             float zt[4][C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float4 q = *reinterpret_cast<const float4*>(tb + (long long)c * a.S);
-                zt[0][c] = q.x; zt[1][c] = q.y; zt[2][c] = q.z; zt[3][c] = q.w;
-            }
+            mis_tail_load4<C>(tb, a.S, zt);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float p[C], q[C], g[C], mx, lse;
-                softmax_c(z[j], C, p, mx, lse);
-                softmax_c(zt[j], C, q, mx, lse);
+                float p[C], q[C], g[C], lse;
+                mis_tail_softmax<C>(z[j], p, lse);
+                mis_tail_softmax<C>(zt[j], q, lse);
                 float dot = 0.f;
 #pragma unroll
                 for (int c = 0; c < C; ++c) { g[c] = kmse * (p[c] - q[c]); dot += g[c] * p[c]; }
@@ -213,19 +153,11 @@ __global__ __launch_bounds__(256) void tail_pass2_kernel(const TailArgs a, const
                 for (int c = 0; c < C; ++c) o[j][c] = p[c] * (g[c] - dot);
             }
         }
-        float* __restrict__ ob = ds + (long long)b * ds_bs + u * 4;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            *reinterpret_cast<float4*>(ob + (long long)c * a.S) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
+        mis_tail_store4<C>(ds + (long long)b * ds_bs + u * 4, a.S, o);
     }
 }
 
-int pass1_blocks(long long B, long long S) {
-    long long b = mis_cdiv(B * (S >> 2), 256 * 4);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+int pass1_blocks(long long B, long long S) { return mis_tail_blocks(B * (S >> 2)); }
 
 }  // namespace
 
@@ -245,30 +177,17 @@ extern "C" int mis_loss_tail(const float* student, long long s_bs, const float* 
     if (B > L && !teacher) return MIS_ERR_ARG;
     if (label_bytes != 1 && label_bytes != 8) return MIS_ERR_ARG;
     if (C != 2 && C != 3 && C != 4) return MIS_ERR_UNSUPPORTED;
-    if (S % 4 != 0 || s_bs % 4 != 0 || ((uintptr_t)student & 15)) return MIS_ERR_UNSUPPORTED;
-    if (teacher && (t_bs % 4 != 0 || ((uintptr_t)teacher & 15))) return MIS_ERR_UNSUPPORTED;
-    if (dlogits && (d_bs % 4 != 0 || ((uintptr_t)dlogits & 15))) return MIS_ERR_UNSUPPORTED;
+    if (S % 4 != 0 || s_bs % 4 != 0 || !mis_aligned16(student)) return MIS_ERR_UNSUPPORTED;
+    if (teacher && (t_bs % 4 != 0 || !mis_aligned16(teacher))) return MIS_ERR_UNSUPPORTED;
+    if (dlogits && (d_bs % 4 != 0 || !mis_aligned16(dlogits))) return MIS_ERR_UNSUPPORTED;
     if (workspace_bytes < mis_loss_tail_workspace_bytes(B, C, S)) return MIS_ERR_WORKSPACE;
     TailArgs a{student, s_bs, teacher, t_bs, label, label_bytes, B, L, C, S, pass1_blocks(B, S)};
     float* part = reinterpret_cast<float*>(workspace);
     float* coef = part + (long long)a.blocks * NPART;
-#define MIS_TAIL_C(CC)                                                                                      \
-    case CC:                                                                                                \
-        hipLaunchKernelGGL(tail_pass1_kernel<CC>, dim3(a.blocks), dim3(256), 0, stream, a, part);           \
-        break;
-    switch (C) { MIS_TAIL_C(2) MIS_TAIL_C(3) MIS_TAIL_C(4) }
-#undef MIS_TAIL_C
+    MIS_DISPATCH_C(C, tail_pass1_kernel, a.blocks, stream, a, part)
     FinalArgs f{part, a.blocks, C, L, B - L, S, cons_weight, state, loss_scale, out, coef};
     hipLaunchKernelGGL(tail_final_kernel, dim3(1), dim3(256), 0, stream, f);
-    if (dlogits) {
-#define MIS_TAIL_C(CC)                                                                                      \
-    case CC:                                                                                                \
-        hipLaunchKernelGGL(tail_pass2_kernel<CC>, dim3(a.blocks), dim3(256), 0, stream, a, coef, dlogits,   \
-                           d_bs);                                                                           \
-        break;
-        switch (C) { MIS_TAIL_C(2) MIS_TAIL_C(3) MIS_TAIL_C(4) }
-#undef MIS_TAIL_C
-    }
+    if (dlogits) MIS_DISPATCH_C(C, tail_pass2_kernel, a.blocks, stream, a, coef, dlogits, d_bs)
     return mis_launch_status();
 }
 
@@ -306,25 +225,20 @@ __global__ __launch_bounds__(256) void cross_pass1_kernel(const CrossArgs a, flo
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int b = (int)(i / a.S);
         const long long sidx = i - (long long)b * a.S;
-        float z[C], p[C], mx, lse;
+        float z[C], p[C], lse;
 #pragma unroll
         for (int c = 0; c < C; ++c) z[c] = a.s[(long long)b * a.s_bs + (long long)c * a.S + sidx];
-        softmax_c(z, C, p, mx, lse);
+        mis_tail_softmax<C>(z, p, lse);
         int y;
-        int base;
         if (b < a.L) {
-            y = load_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
-            base = 2;
+            y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
         } else {
-            float best = a.o[(long long)b * a.o_bs + sidx];
-            y = 0;
+            float zo[C];
 #pragma unroll
-            for (int c = 1; c < C; ++c) {
-                const float t = a.o[(long long)b * a.o_bs + (long long)c * a.S + sidx];
-                if (t > best) { best = t; y = c; }
-            }
-            base = 2 + 3 * MIS_MAXC;
+            for (int c = 0; c < C; ++c) zo[c] = a.o[(long long)b * a.o_bs + (long long)c * a.S + sidx];
+            y = mis_tail_argmax<C>(zo);
         }
+        // not mis_tail_labeled_sums: through it the pseudo-labeled half compiles to other fp32 code (its CE term is conditional)
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const bool hit = c == y;
@@ -340,14 +254,13 @@ __global__ __launch_bounds__(256) void cross_pass1_kernel(const CrossArgs a, flo
             }
         }
         if (b >= a.L && a.t) {
-            float zt[C], q[C], mt, lt;
+            float zt[C], q[C], lt;
 #pragma unroll
             for (int c = 0; c < C; ++c) zt[c] = a.t[(long long)(b - a.L) * a.t_bs + (long long)c * a.S + sidx];
-            softmax_c(zt, C, q, mt, lt);
+            mis_tail_softmax<C>(zt, q, lt);
 #pragma unroll
             for (int c = 0; c < C; ++c) v[1] += (p[c] - q[c]) * (p[c] - q[c]);
         }
-        (void)base;
     }
     mis_block_sum<NPARTX>(v, red);
     if (threadIdx.x == 0)
@@ -363,21 +276,9 @@ struct CrossFinalArgs {
 };
 
 __global__ __launch_bounds__(256) void cross_final_kernel(const CrossFinalArgs a) {
-    __shared__ double red[4];
     __shared__ double tot[NPARTX];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = 0; i < NPARTX; ++i) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < a.blocks; b += 256) s += a.part[(long long)b * NPARTX + i];
-        s = mis_wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[i] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    __syncthreads();
+    mis_tail_reduce_parts(a.part, a.blocks, NPARTX, NPARTX, tot);
     if (threadIdx.x != 0) return;
-    const double smooth = 1e-5;
     const float w = a.st ? a.st->cons_weight : a.cons_weight;
     const double nlab = (double)a.L * (double)a.S;
     const double ce = a.L > 0 ? tot[0] / nlab : 0.0;
@@ -385,12 +286,12 @@ __global__ __launch_bounds__(256) void cross_final_kernel(const CrossFinalArgs a
     for (int c = 0; c < a.C; ++c) {
         for (int half = 0; half < 2; ++half) {
             const int o = 2 + half * 3 * MIS_MAXC + 3 * c;
-            const double I = tot[o], Y = tot[o + 1], Z = tot[o + 2];
-            const double num = 2.0 * I + smooth, den = Z + Y + smooth;
             const double scale = half == 0 ? 0.5 : (double)w;          // d loss / d dice_mean
-            (half == 0 ? dice_l : dice_u) += 1.0 - num / den;
-            a.coef[1 + half * 2 * a.C + 2 * c] = (float)(scale * (-2.0 / den) / a.C);
-            a.coef[2 + half * 2 * a.C + 2 * c] = (float)(scale * (2.0 * num / (den * den)) / a.C);
+            double dl, ac, bc;
+            mis_tail_dice_coef(tot[o], tot[o + 1], tot[o + 2], scale, a.C, dl, ac, bc);
+            (half == 0 ? dice_l : dice_u) += dl;
+            a.coef[1 + half * 2 * a.C + 2 * c] = (float)ac;
+            a.coef[2 + half * 2 * a.C + 2 * c] = (float)bc;
         }
     }
     dice_l = a.L > 0 ? dice_l / a.C : 0.0;
@@ -419,33 +320,31 @@ __global__ __launch_bounds__(256) void cross_pass2_kernel(const CrossArgs a, con
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int b = (int)(i / a.S);
         const long long sidx = i - (long long)b * a.S;
-        float z[C], p[C], g[C], mx, lse;
+        float z[C], p[C], g[C], lse;
 #pragma unroll
         for (int c = 0; c < C; ++c) z[c] = a.s[(long long)b * a.s_bs + (long long)c * a.S + sidx];
-        softmax_c(z, C, p, mx, lse);
+        mis_tail_softmax<C>(z, p, lse);
         int y;
         const bool lab = b < a.L;
         if (lab) {
-            y = load_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
+            y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
         } else {
-            float best = a.o[(long long)b * a.o_bs + sidx];
-            y = 0;
+            float zo[C];
 #pragma unroll
-            for (int c = 1; c < C; ++c) {
-                const float t = a.o[(long long)b * a.o_bs + (long long)c * a.S + sidx];
-                if (t > best) { best = t; y = c; }
-            }
+            for (int c = 0; c < C; ++c) zo[c] = a.o[(long long)b * a.o_bs + (long long)c * a.S + sidx];
+            y = mis_tail_argmax<C>(zo);
         }
         const int off = lab ? 0 : 2 * C;
         float q[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) q[c] = p[c];
         if (!lab && a.t) {
-            float zt[C], mt, lt;
+            float zt[C], lt;
 #pragma unroll
             for (int c = 0; c < C; ++c) zt[c] = a.t[(long long)(b - a.L) * a.t_bs + (long long)c * a.S + sidx];
-            softmax_c(zt, C, q, mt, lt);
+            mis_tail_softmax<C>(zt, q, lt);
         }
+        // not mis_tail_labeled_grad: one expression serves the labeled, the pseudo-labeled and the teacher term
         float dot = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
@@ -463,12 +362,7 @@ __global__ __launch_bounds__(256) void cross_pass2_kernel(const CrossArgs a, con
     }
 }
 
-int cross_blocks(long long B, long long S) {
-    long long b = mis_cdiv(B * S, 256 * 4);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+int cross_blocks(long long B, long long S) { return mis_tail_blocks(B * S); }
 
 }  // namespace
 
@@ -502,20 +396,10 @@ extern "C" int mis_cross_pseudo_mt_tail(const float* own, long long s_bs, const 
                 B > L ? teacher : nullptr, t_bs};
     float* part = reinterpret_cast<float*>(workspace);
     float* coef = part + (long long)a.blocks * NPARTX;
-    switch (C) {
-        case 2: hipLaunchKernelGGL(cross_pass1_kernel<2>, dim3(a.blocks), dim3(256), 0, stream, a, part); break;
-        case 3: hipLaunchKernelGGL(cross_pass1_kernel<3>, dim3(a.blocks), dim3(256), 0, stream, a, part); break;
-        case 4: hipLaunchKernelGGL(cross_pass1_kernel<4>, dim3(a.blocks), dim3(256), 0, stream, a, part); break;
-    }
+    MIS_DISPATCH_C(C, cross_pass1_kernel, a.blocks, stream, a, part)
     CrossFinalArgs f{part, a.blocks, C, L, B - L, S, cons_weight, state, out, coef, a.pseudo_ce, a.t ? 1 : 0, mt_weight};
     hipLaunchKernelGGL(cross_final_kernel, dim3(1), dim3(256), 0, stream, f);
-    if (dlogits) {
-        switch (C) {
-            case 2: hipLaunchKernelGGL(cross_pass2_kernel<2>, dim3(a.blocks), dim3(256), 0, stream, a, coef, dlogits, d_bs); break;
-            case 3: hipLaunchKernelGGL(cross_pass2_kernel<3>, dim3(a.blocks), dim3(256), 0, stream, a, coef, dlogits, d_bs); break;
-            case 4: hipLaunchKernelGGL(cross_pass2_kernel<4>, dim3(a.blocks), dim3(256), 0, stream, a, coef, dlogits, d_bs); break;
-        }
-    }
+    if (dlogits) MIS_DISPATCH_C(C, cross_pass2_kernel, a.blocks, stream, a, coef, dlogits, d_bs)
     return mis_launch_status();
 }
 

@@ -6,16 +6,9 @@
 //   losses.DiceLoss(n_classes)(probs, target)          code/utils/losses.py:165-201
 //   losses.softmax_mse_loss(input_logits, target_logits)   code/utils/losses.py:74-91
 //   update_ema_variables(model, ema_model, alpha, step)     code/train_mean_teacher_2D.py:124-128
-#include "common.h"
-
-#define MIS_MAXC 8
+#include "tail.h"
 
 namespace {
-
-__device__ __forceinline__ int load_label(const void* lab, int bytes, long long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(lab)[i]
-                      : (int)reinterpret_cast<const long long*>(lab)[i];
-}
 
 constexpr int NP3 = 3 * MIS_MAXC;
 
@@ -31,7 +24,7 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int b = (int)(i / S);
         const long long s = i - (long long)b * S;
-        const int y = load_label(label, label_bytes, i);
+        const int y = mis_tail_label(label, label_bytes, i);
         const float* __restrict__ pb = p + (long long)b * p_bs + s;
 #pragma unroll
         for (int c = 0; c < MIS_MAXC; ++c) {
@@ -51,19 +44,8 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
 // dLoss/dp_c = a_c*[y==c] + b_c*p_c
 __global__ __launch_bounds__(256) void dice_final_kernel(const float* __restrict__ part, int blocks, int C,
                                                          const float* __restrict__ weight, float* out, float* coef) {
-    __shared__ double red[4];
     __shared__ double tot[NP3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = 0; i < 3 * C; ++i) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < blocks; b += 256) s += part[(long long)b * NP3 + i];
-        s = mis_wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[i] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    __syncthreads();
+    mis_tail_reduce_parts(part, blocks, NP3, 3 * C, tot);
     if (threadIdx.x != 0) return;
     double loss = 0.0;
     for (int c = 0; c < C; ++c) {
@@ -88,7 +70,7 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int b = (int)(i / S);
         const long long s = i - (long long)b * S;
-        const int y = load_label(label, label_bytes, i);
+        const int y = mis_tail_label(label, label_bytes, i);
         for (int c = 0; c < C; ++c) {
             const float pc = p[(long long)b * p_bs + (long long)c * S + s];
             dp[(long long)b * d_bs + (long long)c * S + s] = g * (coef[2 * c + 1] * pc + (c == y ? coef[2 * c] : 0.f));

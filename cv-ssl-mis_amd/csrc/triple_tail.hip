@@ -12,7 +12,7 @@
 // the gradient coefficients; pass 2 reads the logits again and writes the three gradients.  What the students share
 // is summed once: the labeled class counts Y_c, the pseudo-label counts Y_{j,c} of each peer, and the unlabeled
 // Z_{m,c} = sum p_m,c^2 that both pseudo terms of student m divide by.
-#include "common.h"
+#include "tail.h"
 
 namespace {
 
@@ -45,36 +45,6 @@ __host__ __device__ constexpr int np_of(int C) { return 3 + 19 * C; }
 // coefficient layout per student, NK(C) = 1 + 5C floats (see pass 2):
 //   [0] ce scale; labeled a_c at 1 + c, b_c at 1 + C + c; pseudo a_{k,c} at 1 + 2C + k*C + c, b_c at 1 + 4C + c
 __host__ __device__ constexpr int nk_of(int C) { return 1 + 5 * C; }
-
-__device__ __forceinline__ int tv_label(const void* lab, int bytes, long long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(lab)[i]
-                      : (int)reinterpret_cast<const long long*>(lab)[i];
-}
-
-template <int C>
-__device__ __forceinline__ void tv_softmax(const float (&z)[C], float (&p)[C], float& lse) {
-    float mx = z[0];
-#pragma unroll
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-    lse = mx + logf(sum);
-}
-
-// first maximum wins, as torch.argmax (softmax is monotone: the arg-max of the logits)
-template <int C>
-__device__ __forceinline__ int tv_argmax(const float (&z)[C]) {
-    float best = z[0];
-    int y = 0;
-#pragma unroll
-    for (int c = 1; c < C; ++c)
-        if (z[c] > best) { best = z[c]; y = c; }
-    return y;
-}
 
 // mis_block_sum (the same tree, the same bits) with a scheduling fence after every eight values: left alone, the scheduler
 // interleaves the 6 x NV independent cross-lane steps of up to 79 values and runs the kernel out of registers.
@@ -114,13 +84,14 @@ __global__ __launch_bounds__(256) void triple_pass1_kernel(const TripleArgs a, f
         for (int m = 0; m < 3; ++m) {
 #pragma unroll
             for (int c = 0; c < C; ++c) z[m][c] = a.z[m][(long long)b * a.zbs[m] + (long long)c * a.S + sidx];
-            tv_softmax<C>(z[m], p[m], lse[m]);
+            mis_tail_softmax<C>(z[m], p[m], lse[m]);
         }
         if (b < a.L) {
-            const int y = tv_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
+            const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                // selects, not branches: the accumulators stay in registers on one straight-line path
+                // selects, not branches: the accumulators stay in registers on one straight-line path (and Y_c is shared
+                // by the three students), so not the branching mis_tail_labeled_sums
                 const float hit = c == y ? 1.f : 0.f;
                 v[TV_LY(C) + c] += hit;
 #pragma unroll
@@ -134,7 +105,7 @@ __global__ __launch_bounds__(256) void triple_pass1_kernel(const TripleArgs a, f
             float hot[3][C];
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const int y = tv_argmax<C>(z[j]);
+                const int y = mis_tail_argmax<C>(z[j]);
 #pragma unroll
                 for (int c = 0; c < C; ++c) hot[j][c] = y == c ? 1.f : 0.f;
             }
@@ -167,22 +138,10 @@ constexpr int TV_MAXNP = np_of(4);
 
 // out_m: [0] loss_m, [1] ce, [2] dice, [3] pseudo_supervision_a, [4] w, [5] pseudo_supervision_b
 __global__ __launch_bounds__(256) void triple_final_kernel(const TripleFinalArgs a) {
-    __shared__ double red[4];
     __shared__ double tot[TV_MAXNP];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C = a.C, NP = np_of(C);
-    for (int i = 0; i < NP; ++i) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < a.blocks; b += 256) s += a.part[(long long)b * NP + i];
-        s = mis_wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[i] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    __syncthreads();
+    mis_tail_reduce_parts(a.part, a.blocks, NP, NP, tot);
     if (threadIdx.x != 0) return;
-    const double smooth = 1e-5;
     const float w = a.st ? a.st->cons_weight : a.cons_weight;
     const double nlab = (double)a.L * (double)a.S;
     for (int m = 0; m < 3; ++m) {
@@ -191,19 +150,18 @@ __global__ __launch_bounds__(256) void triple_final_kernel(const TripleFinalArgs
         double dice_l = 0.0, dice_u[2] = {0.0, 0.0};
         for (int c = 0; c < C; ++c) {
             // d(scale * dice_mean)/dp_c = a_c * [y == c] + b_c * p_c
-            const double I = tot[TV_LI(C) + m * C + c], Y = tot[TV_LY(C) + c], Z = tot[TV_LZ(C) + m * C + c];
-            const double num = 2.0 * I + smooth, den = Z + Y + smooth;
-            dice_l += 1.0 - num / den;
-            coef[1 + c] = (float)(0.5 * (-2.0 / den) / C);
-            coef[1 + C + c] = (float)(0.5 * (2.0 * num / (den * den)) / C);
-            const double Zu = tot[TV_UZ(C) + m * C + c];
+            double dl, ac, bc;
+            mis_tail_dice_coef(tot[TV_LI(C) + m * C + c], tot[TV_LY(C) + c], tot[TV_LZ(C) + m * C + c], 0.5, C, dl, ac, bc);
+            dice_l += dl;
+            coef[1 + c] = (float)ac;
+            coef[1 + C + c] = (float)bc;
             double bu = 0.0;
             for (int k = 0; k < 2; ++k) {
-                const double Iu = tot[TV_UI(C) + (2 * m + k) * C + c], Yu = tot[TV_UY(C) + peer_of(m, k) * C + c];
-                const double nu = 2.0 * Iu + smooth, du = Zu + Yu + smooth;
-                dice_u[k] += 1.0 - nu / du;
-                coef[1 + 2 * C + k * C + c] = (float)((double)w * (-2.0 / du) / C);
-                bu += (double)w * (2.0 * nu / (du * du)) / C;
+                mis_tail_dice_coef(tot[TV_UI(C) + (2 * m + k) * C + c], tot[TV_UY(C) + peer_of(m, k) * C + c],
+                                   tot[TV_UZ(C) + m * C + c], (double)w, C, dl, ac, bc);
+                dice_u[k] += dl;
+                coef[1 + 2 * C + k * C + c] = (float)ac;
+                bu += bc;
             }
             coef[1 + 4 * C + c] = (float)bu;
         }
@@ -232,19 +190,20 @@ __global__ __launch_bounds__(256) void triple_pass2_kernel(const TripleArgs a, c
         for (int m = 0; m < 3; ++m) {
 #pragma unroll
             for (int c = 0; c < C; ++c) z[m][c] = a.z[m][(long long)b * a.zbs[m] + (long long)c * a.S + sidx];
-            tv_softmax<C>(z[m], p[m], lse);
+            mis_tail_softmax<C>(z[m], p[m], lse);
         }
         const bool lab = b < a.L;
         int y[3] = {0, 0, 0};
         if (lab) {
-            y[0] = tv_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
+            y[0] = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + sidx);
         } else {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) y[j] = tv_argmax<C>(z[j]);
+            for (int j = 0; j < 3; ++j) y[j] = mis_tail_argmax<C>(z[j]);
         }
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
             const float* __restrict__ k = coef + m * NK;
+            // not mis_tail_labeled_grad: g takes the labeled or the two pseudo-label terms, then one shared tail
             float g[C], dot = 0.f;
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -266,12 +225,7 @@ __global__ __launch_bounds__(256) void triple_pass2_kernel(const TripleArgs a, c
     }
 }
 
-int triple_blocks(long long B, long long S) {
-    long long b = mis_cdiv(B * S, 256 * 4);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+int triple_blocks(long long B, long long S) { return mis_tail_blocks(B * S); }
 
 }  // namespace
 
@@ -302,20 +256,12 @@ extern "C" int mis_triple_view_tail(const float* z1, long long z1_bs, const floa
     const int blocks = triple_blocks(B, S);
     float* part = reinterpret_cast<float*>(workspace);
     float* coef = part + (long long)blocks * np_of(C);
-    switch (C) {
-        case 2: hipLaunchKernelGGL(triple_pass1_kernel<2>, dim3(blocks), dim3(256), 0, stream, a, part); break;
-        case 3: hipLaunchKernelGGL(triple_pass1_kernel<3>, dim3(blocks), dim3(256), 0, stream, a, part); break;
-        case 4: hipLaunchKernelGGL(triple_pass1_kernel<4>, dim3(blocks), dim3(256), 0, stream, a, part); break;
-    }
+    MIS_DISPATCH_C(C, triple_pass1_kernel, blocks, stream, a, part)
     const TripleFinalArgs f{part, blocks, C, L, B - L, S, cons_weight, state, {out1, out2, out3}, coef};
     hipLaunchKernelGGL(triple_final_kernel, dim3(1), dim3(256), 0, stream, f);
     if (nd) {
         const TripleGradArgs d{{d1, d2, d3}, {d1_bs, d2_bs, d3_bs}};
-        switch (C) {
-            case 2: hipLaunchKernelGGL(triple_pass2_kernel<2>, dim3(blocks), dim3(256), 0, stream, a, coef, d); break;
-            case 3: hipLaunchKernelGGL(triple_pass2_kernel<3>, dim3(blocks), dim3(256), 0, stream, a, coef, d); break;
-            case 4: hipLaunchKernelGGL(triple_pass2_kernel<4>, dim3(blocks), dim3(256), 0, stream, a, coef, d); break;
-        }
+        MIS_DISPATCH_C(C, triple_pass2_kernel, blocks, stream, a, coef, d)
     }
     return mis_launch_status();
 }

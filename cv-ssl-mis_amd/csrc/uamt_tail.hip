@@ -15,26 +15,9 @@
 // tree, double in the last stage), one-workgroup finalize -> scalars and gradient coefficients, pass 2 ->
 // dlogits.  The T softmax tensors and the uncertainty map are never materialised: each MC pass is folded
 // into one running mean-probability buffer as soon as its logits exist.
-#include "common.h"
-
-#define MIS_MAXC 8
+#include "tail.h"
 
 namespace {
-
-__device__ __forceinline__ int load_label(const void* lab, int bytes, long long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(lab)[i]
-                      : (int)reinterpret_cast<const long long*>(lab)[i];
-}
-
-__device__ __forceinline__ void softmax_c(const float* z, int C, float* p, float& lse) {
-    float mx = z[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float sum = 0.f;
-    for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-    lse = mx + logf(sum);
-}
 
 // acc[u][c][s] = (first ? 0 : acc) + scale * sum_r softmax(logits[r*U + u])[c][s]     (R repeats in the batch)
 template <int C>
@@ -53,15 +36,11 @@ __global__ __launch_bounds__(256) void softmax_mean_kernel(const float* __restri
         for (int r = 0; r < R; ++r) {
             const float* __restrict__ lb = logits + (long long)(r * U + u) * l_bs + q * 4;
             float z[4][C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float4 v = *reinterpret_cast<const float4*>(lb + (long long)c * S);
-                z[0][c] = v.x; z[1][c] = v.y; z[2][c] = v.z; z[3][c] = v.w;
-            }
+            mis_tail_load4<C>(lb, S, z);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float p[C], lse;
-                softmax_c(z[j], C, p, lse);
+                mis_tail_softmax<C>(z[j], p, lse);
 #pragma unroll
                 for (int c = 0; c < C; ++c) m[j][c] += p[c];
             }
@@ -125,40 +104,27 @@ __global__ __launch_bounds__(256) void uamt_pass1_kernel(const UArgs a, float* _
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.s + (long long)b * a.s_bs + u * 4;
         float z[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * a.S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, a.S, z);
         if (b < a.L) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float p[C], lse;
-                softmax_c(z[j], C, p, lse);
-                const int y = load_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    if (c == y) { v[0] += lse - z[j][c]; v[3 + 3 * c] += p[c]; v[3 + 3 * c + 1] += 1.f; }
-                    v[3 + 3 * c + 2] += p[c] * p[c];
-                }
+                mis_tail_softmax<C>(z[j], p, lse);
+                const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
+                mis_tail_labeled_sums<C>(z[j], p, lse, y, v[0], v + 3);
             }
         } else {
             const float* __restrict__ tb = a.t + (long long)(b - a.L) * a.t_bs + u * 4;
             const float* __restrict__ mb = a.pm + (long long)(b - a.L) * a.pm_bs + u * 4;
             float zt[4][C], pm[4][C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float4 q = *reinterpret_cast<const float4*>(tb + (long long)c * a.S);
-                zt[0][c] = q.x; zt[1][c] = q.y; zt[2][c] = q.z; zt[3][c] = q.w;
-                const float4 m = *reinterpret_cast<const float4*>(mb + (long long)c * a.S);
-                pm[0][c] = m.x; pm[1][c] = m.y; pm[2][c] = m.z; pm[3][c] = m.w;
-            }
+            mis_tail_load4<C>(tb, a.S, zt);
+            mis_tail_load4<C>(mb, a.S, pm);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (entropy_c(pm[j], C) < thr) {
                     float p[C], q[C], lse;
-                    softmax_c(z[j], C, p, lse);
-                    softmax_c(zt[j], C, q, lse);
+                    mis_tail_softmax<C>(z[j], p, lse);
+                    mis_tail_softmax<C>(zt[j], q, lse);
 #pragma unroll
                     for (int c = 0; c < C; ++c) { const float d = p[c] - q[c]; v[1] += d * d; }
                     v[2] += 1.f;
@@ -183,21 +149,9 @@ struct UFinalArgs {
 };
 
 __global__ __launch_bounds__(256) void uamt_final_kernel(const UFinalArgs a, const UArgs ua) {
-    __shared__ double red[4];
     __shared__ double tot[NPART];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = 0; i < 3 + 3 * a.C; ++i) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < a.blocks; b += 256) s += a.part[(long long)b * NPART + i];
-        s = mis_wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[i] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    __syncthreads();
+    mis_tail_reduce_parts(a.part, a.blocks, NPART, 3 + 3 * a.C, tot);
     if (threadIdx.x != 0) return;
-    const double smooth = 1e-5;
     const double nlab = (double)a.L * (double)a.S;
     const float w = a.st ? a.st->cons_weight : a.cons_weight;
     const double ce = a.L > 0 ? tot[0] / nlab : 0.0;
@@ -206,13 +160,12 @@ __global__ __launch_bounds__(256) void uamt_final_kernel(const UFinalArgs a, con
     const double cons = tot[1] / den;
     double dice = 0.0;
     for (int c = 0; c < a.C; ++c) {
-        const double I = tot[3 + 3 * c], Y = tot[4 + 3 * c], Z = tot[5 + 3 * c];
-        const double num = 2.0 * I + smooth, dn = Z + Y + smooth;
-        const double dl = 1.0 - num / dn;
+        double dl, ac, bc;
+        mis_tail_dice_coef(tot[3 + 3 * c], tot[4 + 3 * c], tot[5 + 3 * c], 0.5 * a.loss_scale, a.C, dl, ac, bc);
         dice += dl;
         a.out[5 + c] = (float)(1.0 - dl);
-        a.coef[2 + 2 * c] = (float)(a.loss_scale * (-1.0 / a.C) / dn);
-        a.coef[3 + 2 * c] = (float)(a.loss_scale * (1.0 / a.C) * num / (dn * dn));
+        a.coef[2 + 2 * c] = (float)ac;
+        a.coef[3 + 2 * c] = (float)bc;
     }
     dice = a.L > 0 ? dice / a.C : 0.0;
     a.out[0] = (float)(0.5 * (dice + ce) + (double)w * cons);
@@ -240,44 +193,27 @@ __global__ __launch_bounds__(256) void uamt_pass2_kernel(const UArgs a, const fl
         const long long u = i - (long long)b * units;
         const float* __restrict__ sb = a.s + (long long)b * a.s_bs + u * 4;
         float z[4][C], o[4][C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 q = *reinterpret_cast<const float4*>(sb + (long long)c * a.S);
-            z[0][c] = q.x; z[1][c] = q.y; z[2][c] = q.z; z[3][c] = q.w;
-        }
+        mis_tail_load4<C>(sb, a.S, z);
         if (b < a.L) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float p[C], g[C], lse;
-                softmax_c(z[j], C, p, lse);
-                const int y = load_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
-                float dot = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    g[c] = bc[c] * p[c] + (c == y ? ac[c] : 0.f);
-                    dot += g[c] * p[c];
-                }
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    o[j][c] = p[c] * (g[c] - dot) + kce * (p[c] - (c == y ? 1.f : 0.f));
+                float p[C], lse;
+                mis_tail_softmax<C>(z[j], p, lse);
+                const int y = mis_tail_label(a.label, a.label_bytes, (long long)b * a.S + u * 4 + j);
+                mis_tail_labeled_grad<C>(p, y, kce, ac, bc, o[j]);
             }
         } else {
             const float* __restrict__ tb = a.t + (long long)(b - a.L) * a.t_bs + u * 4;
             const float* __restrict__ mb = a.pm + (long long)(b - a.L) * a.pm_bs + u * 4;
             float zt[4][C], pm[4][C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float4 q = *reinterpret_cast<const float4*>(tb + (long long)c * a.S);
-                zt[0][c] = q.x; zt[1][c] = q.y; zt[2][c] = q.z; zt[3][c] = q.w;
-                const float4 m = *reinterpret_cast<const float4*>(mb + (long long)c * a.S);
-                pm[0][c] = m.x; pm[1][c] = m.y; pm[2][c] = m.z; pm[3][c] = m.w;
-            }
+            mis_tail_load4<C>(tb, a.S, zt);
+            mis_tail_load4<C>(mb, a.S, pm);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool keep = entropy_c(pm[j], C) < thr;
                 float p[C], q[C], g[C], lse;
-                softmax_c(z[j], C, p, lse);
-                softmax_c(zt[j], C, q, lse);
+                mis_tail_softmax<C>(z[j], p, lse);
+                mis_tail_softmax<C>(zt[j], q, lse);
                 float dot = 0.f;
 #pragma unroll
                 for (int c = 0; c < C; ++c) { g[c] = keep ? kmse * (p[c] - q[c]) : 0.f; dot += g[c] * p[c]; }
@@ -285,21 +221,11 @@ __global__ __launch_bounds__(256) void uamt_pass2_kernel(const UArgs a, const fl
                 for (int c = 0; c < C; ++c) o[j][c] = p[c] * (g[c] - dot);
             }
         }
-        float* __restrict__ ob = ds + (long long)b * ds_bs + u * 4;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            *reinterpret_cast<float4*>(ob + (long long)c * a.S) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
+        mis_tail_store4<C>(ds + (long long)b * ds_bs + u * 4, a.S, o);
     }
 }
 
-int nblocks(long long B, long long S) {
-    long long b = mis_cdiv(B * (S >> 2), 256 * 4);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int nblocks(long long B, long long S) { return mis_tail_blocks(B * (S >> 2)); }
 
 }  // namespace
 
@@ -307,16 +233,10 @@ extern "C" int mis_softmax_mean_accumulate(const float* logits, long long l_bs, 
                                            int R, int C, long long S, float scale, int first, hipStream_t stream) {
     if (!logits || !acc || U <= 0 || R <= 0 || C <= 0 || S <= 0) return MIS_ERR_ARG;
     if (C != 2 && C != 3 && C != 4) return MIS_ERR_UNSUPPORTED;
-    if (S % 4 || l_bs % 4 || a_bs % 4 || !a16(logits) || !a16(acc)) return MIS_ERR_UNSUPPORTED;
+    if (S % 4 || l_bs % 4 || a_bs % 4 || !mis_aligned16(logits) || !mis_aligned16(acc)) return MIS_ERR_UNSUPPORTED;
     if (l_bs < (long long)C * S || a_bs < (long long)C * S) return MIS_ERR_ARG;
     const int nb = nblocks(U, S);
-#define MIS_SM_C(CC)                                                                                            \
-    case CC:                                                                                                    \
-        hipLaunchKernelGGL(softmax_mean_kernel<CC>, dim3(nb), dim3(256), 0, stream, logits, l_bs, acc, a_bs, U, \
-                           R, S, scale, first);                                                                 \
-        break;
-    switch (C) { MIS_SM_C(2) MIS_SM_C(3) MIS_SM_C(4) }
-#undef MIS_SM_C
+    MIS_DISPATCH_C(C, softmax_mean_kernel, nb, stream, logits, l_bs, acc, a_bs, U, R, S, scale, first)
     return mis_launch_status();
 }
 
@@ -337,27 +257,18 @@ extern "C" int mis_uamt_tail(const float* student, long long s_bs, const float* 
     if (L > 0 && !label) return MIS_ERR_ARG;
     if (label_bytes != 1 && label_bytes != 8) return MIS_ERR_ARG;
     if (C != 2 && C != 3 && C != 4) return MIS_ERR_UNSUPPORTED;
-    if (S % 4 || s_bs % 4 || t_bs % 4 || mp_bs % 4 || !a16(student) || !a16(teacher) || !a16(mean_probs))
+    if (S % 4 || s_bs % 4 || t_bs % 4 || mp_bs % 4 || !mis_aligned16(student) || !mis_aligned16(teacher) || !mis_aligned16(mean_probs))
         return MIS_ERR_UNSUPPORTED;
-    if (dlogits && (d_bs % 4 || !a16(dlogits))) return MIS_ERR_UNSUPPORTED;
+    if (dlogits && (d_bs % 4 || !mis_aligned16(dlogits))) return MIS_ERR_UNSUPPORTED;
     if (workspace_bytes < mis_uamt_tail_workspace_bytes(B, C, S)) return MIS_ERR_WORKSPACE;
     UArgs a{student, s_bs, teacher, t_bs, mean_probs, mp_bs, label, label_bytes, B, L, C, S, state, max_iterations,
             iter_num};
     const int nb = nblocks(B, S);
     float* part = reinterpret_cast<float*>(workspace);
     float* coef = part + (long long)nb * NPART;
-#define MIS_U1(CC) case CC: hipLaunchKernelGGL(uamt_pass1_kernel<CC>, dim3(nb), dim3(256), 0, stream, a, part); break;
-    switch (C) { MIS_U1(2) MIS_U1(3) MIS_U1(4) }
-#undef MIS_U1
+    MIS_DISPATCH_C(C, uamt_pass1_kernel, nb, stream, a, part)
     UFinalArgs f{part, nb, C, L, S, cons_weight, state, loss_scale, 0.f, out, coef};
     hipLaunchKernelGGL(uamt_final_kernel, dim3(1), dim3(256), 0, stream, f, a);
-    if (dlogits) {
-#define MIS_U2(CC)                                                                                        \
-    case CC:                                                                                              \
-        hipLaunchKernelGGL(uamt_pass2_kernel<CC>, dim3(nb), dim3(256), 0, stream, a, coef, dlogits, d_bs); \
-        break;
-        switch (C) { MIS_U2(2) MIS_U2(3) MIS_U2(4) }
-#undef MIS_U2
-    }
+    if (dlogits) MIS_DISPATCH_C(C, uamt_pass2_kernel, nb, stream, a, coef, dlogits, d_bs)
     return mis_launch_status();
 }
