@@ -10,7 +10,7 @@
 // variance, inverted dropout.
 //
 // HBM-bound.  Statistics are a two-stage fixed-order tree (float4 loads, wave
-// shuffles, double in the last stage) -> deterministic, no atomics.  The apply
+// shuffles, double in both stages and in between) -> deterministic, no atomics.  The apply
 // pass fuses scale/shift, activation and the Philox dropout mask in one
 // read+write; the mask is never stored (backward regenerates it from
 // (seed, offset, salt, element index)).
@@ -133,9 +133,12 @@ __device__ __forceinline__ void block_sum2_d(double (&v)[2], double* red) {
 // ---------------- statistics ----------------
 // grid = (P, nchunks, G); partial[(g*nchunks + k)*P + p] = (sum, sumsq)
 // The stand-alone pass (layers whose producer is not a conv with fused statistics, and every GroupNorm) accumulates in
-// double, as torch's CPU kernels do (at::acc_type<float>): the pass is HBM-bound, the fp64 adds are free
+// double, as torch's CPU kernels do (at::acc_type<float>): the pass is HBM-bound, the fp64 adds are free.
+// T2 = double2 (mis_norm_stats): the partials stay in double up to the final stage -- rounded to float, ss/E - m*m loses
+// (mean/std)^2 ulps of the variance (rstd off by 2e-5 at mean/std 32).  T2 = float2: mis_channel_sum, which sums only.
+template <typename T2>
 __global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restrict__ x, Geo g,
-                                                            float2* __restrict__ part) {
+                                                            T2* __restrict__ part) {
     __shared__ double red[8];
     const int p = blockIdx.x, k = blockIdx.y, grp = blockIdx.z;
     const int n = g.per_sample ? grp / g.C : k;
@@ -151,45 +154,72 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restr
         v[1] += ((double)q.x * q.x + (double)q.y * q.y) + ((double)q.z * q.z + (double)q.w * q.w);
     }
     block_sum2_d(v, red);
-    if (threadIdx.x == 0) part[((long long)grp * g.nchunks + k) * g.P + p] = make_float2((float)v[0], (float)v[1]);
+    if (threadIdx.x == 0) {
+        T2 o;
+        o.x = (decltype(o.x))v[0]; o.y = (decltype(o.y))v[1];
+        part[((long long)grp * g.nchunks + k) * g.P + p] = o;
+    }
 }
 
 // one 256-thread block per group (the fused conv statistics leave thousands of partials per channel)
-__global__ __launch_bounds__(256) void stats_final_kernel(const float2* __restrict__ part, Geo g, float eps,
+// T2 = float2: the conv epilogues' per-tile partials (mis_norm_stats_finalize); double2: stats_partial_kernel's.
+// With double partials the kernel also carries the sums of the partials rounded to fp32.  One-pass ss/E - m*m from sums
+// rounded at 2^-24 is off by that rounding times 1 + m*m/var: where this factor is at most 4 (|mean| <= 1.7 std: what a
+// convolution's output looks like) the rounded sums are within fp32 noise and they are what is used -- the arithmetic the
+// golden fixtures and the parity bounds of the step-level tests were measured with, and a bias gradient in front of a
+// GroupNorm moves by 4e-5 of the largest gradient when a group mean moves by one ulp.  Beyond it (an offset of several std:
+// rstd off by 2e-5 at mean/std 32) the double sums are used.
+template <typename T2>
+__global__ __launch_bounds__(256) void stats_final_kernel(const T2* __restrict__ part, Geo g, float eps,
                                                           float* __restrict__ mean, float* __restrict__ rstd,
                                                           float* running_mean, float* running_var,
                                                           long long* num_batches, float momentum, int tpg) {
     // tpg = threads per group: 64 (four groups per block) or 256 (one group per block)
-    __shared__ double red[8];
+    constexpr bool WIDE = std::is_same<T2, double2>::value;
+    __shared__ double red[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = tpg == 256 ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
     const int t = tpg == 256 ? (int)threadIdx.x : lane;
     const int np = g.nchunks * g.P;
-    double s = 0.0, ss = 0.0;
+    double s = 0.0, ss = 0.0, sf = 0.0, ssf = 0.0;      // sf, ssf (WIDE only): the same sums of the partials rounded to fp32
     if (grp < g.G) {
-        const float2* __restrict__ pg = part + (long long)grp * np;
+        const T2* __restrict__ pg = part + (long long)grp * np;
         int i = t;
         for (; i + 3 * tpg < np; i += 4 * tpg) {   // four independent loads in flight
-            const float2 q0 = pg[i], q1 = pg[i + tpg], q2 = pg[i + 2 * tpg], q3 = pg[i + 3 * tpg];
+            const T2 q0 = pg[i], q1 = pg[i + tpg], q2 = pg[i + 2 * tpg], q3 = pg[i + 3 * tpg];
             s += q0.x; ss += q0.y; s += q1.x; ss += q1.y; s += q2.x; ss += q2.y; s += q3.x; ss += q3.y;
+            if constexpr (WIDE) {
+                sf += (float)q0.x; ssf += (float)q0.y; sf += (float)q1.x; ssf += (float)q1.y;
+                sf += (float)q2.x; ssf += (float)q2.y; sf += (float)q3.x; ssf += (float)q3.y;
+            }
         }
         for (; i < np; i += tpg) {
-            const float2 q = pg[i];
+            const T2 q = pg[i];
             s += q.x; ss += q.y;
+            if constexpr (WIDE) { sf += (float)q.x; ssf += (float)q.y; }
         }
     }
     s = mis_wave_sum_d(s); ss = mis_wave_sum_d(ss);
+    if constexpr (WIDE) { sf = mis_wave_sum_d(sf); ssf = mis_wave_sum_d(ssf); }
     if (tpg == 256) {
-        if (lane == 0) { red[wave] = s; red[4 + wave] = ss; }
+        if (lane == 0) { red[wave] = s; red[4 + wave] = ss; red[8 + wave] = sf; red[12 + wave] = ssf; }
         __syncthreads();
         s = ((red[0] + red[1]) + red[2]) + red[3];
         ss = ((red[4] + red[5]) + red[6]) + red[7];
+        sf = ((red[8] + red[9]) + red[10]) + red[11];
+        ssf = ((red[12] + red[13]) + red[14]) + red[15];
     }
     if (grp < g.G && t == 0) {
         const double E = (double)g.nchunks * (double)g.S;
-        const double m = s / E;
+        double m = s / E;
         double var = ss / E - m * m;
         if (var < 0.0) var = 0.0;
+        if constexpr (WIDE) {
+            const double mf = sf / E;
+            double vf = ssf / E - mf * mf;
+            if (vf < 0.0) vf = 0.0;
+            if (mf * mf <= 3.0 * vf) { m = mf; var = vf; }
+        }
         mean[grp] = (float)m;
         rstd[grp] = (float)(1.0 / sqrt(var + (double)eps));
         if (running_mean && !g.per_sample) {
@@ -201,10 +231,11 @@ __global__ __launch_bounds__(256) void stats_final_kernel(const float2* __restri
     }
 }
 
-void launch_stats_final(const float2* part, const Geo& g, float eps, float* mean, float* rstd, float* running_mean,
+template <typename T2>
+void launch_stats_final(const T2* part, const Geo& g, float eps, float* mean, float* rstd, float* running_mean,
                         float* running_var, long long* num_batches, float momentum, hipStream_t stream) {
     const int tpg = g.nchunks * g.P > 256 ? 256 : 64;
-    hipLaunchKernelGGL(stats_final_kernel, dim3(tpg == 256 ? g.G : (g.G + 3) / 4), dim3(256), 0, stream, part, g, eps,
+    hipLaunchKernelGGL(stats_final_kernel<T2>, dim3(tpg == 256 ? g.G : (g.G + 3) / 4), dim3(256), 0, stream, part, g, eps,
                        mean, rstd, running_mean, running_var, num_batches, momentum, tpg);
 }
 
@@ -687,8 +718,10 @@ int check_geo(const void* x, int N, int C, long long S, long long x_bs) {
 extern "C" long long mis_norm_workspace_bytes(int N, int C, long long S, int per_sample) {
     if (N <= 0 || C <= 0 || S <= 0) return MIS_ERR_ARG;
     const Geo g = make_geo(N, C, S, (long long)C * S, per_sample);
-    // partials + per-group (s1/E, s2/E)
-    return ((long long)g.G * g.nchunks * g.P + g.G) * (long long)sizeof(float2);
+    // the backward's float2 partials + per-group (s1/E, s2/E), or the statistics pass's double2 partials
+    const long long np = (long long)g.G * g.nchunks * g.P;
+    const long long bwd = (np + g.G) * (long long)sizeof(float2), stats = np * (long long)sizeof(double2);
+    return stats > bwd ? stats : bwd;
 }
 
 extern "C" int mis_norm_stats(const float* x, long long x_bs, int N, int C, long long S, int per_sample, float eps,
@@ -707,10 +740,11 @@ extern "C" int mis_norm_stats(const float* x, long long x_bs, int N, int C, long
     int st = check_geo(x, N, C, S, x_bs);
     if (st) return st;
     if (!mean || !rstd || !workspace) return MIS_ERR_ARG;
+    if (!aligned16(workspace)) return MIS_ERR_UNSUPPORTED;
     const Geo g = make_geo(N, C, S, x_bs, per_sample);
     if (workspace_bytes < mis_norm_workspace_bytes(N, C, S, per_sample)) return MIS_ERR_WORKSPACE;
-    float2* part = reinterpret_cast<float2*>(workspace);
-    hipLaunchKernelGGL(stats_partial_kernel, dim3(g.P, g.nchunks, g.G), dim3(256), 0, stream, x, g, part);
+    double2* part = reinterpret_cast<double2*>(workspace);
+    hipLaunchKernelGGL(stats_partial_kernel<double2>, dim3(g.P, g.nchunks, g.G), dim3(256), 0, stream, x, g, part);
     launch_stats_final(part, g, eps, mean, rstd, running_mean, running_var, num_batches_tracked, momentum, stream);
     return mis_launch_status();
 }
@@ -741,7 +775,7 @@ extern "C" int mis_channel_sum(const float* x, long long x_bs, int N, int C, lon
     const Geo g = make_geo(N, C, S, x_bs, 0);
     if (workspace_bytes < mis_norm_workspace_bytes(N, C, S, 0)) return MIS_ERR_WORKSPACE;
     float2* part = reinterpret_cast<float2*>(workspace);
-    hipLaunchKernelGGL(stats_partial_kernel, dim3(g.P, g.nchunks, g.G), dim3(256), 0, stream, x, g, part);
+    hipLaunchKernelGGL(stats_partial_kernel<float2>, dim3(g.P, g.nchunks, g.G), dim3(256), 0, stream, x, g, part);
     hipLaunchKernelGGL(channel_sum_final_kernel, dim3((g.G + 3) / 4), dim3(256), 0, stream, part, g, out,
                        accumulate);
     return mis_launch_status();

@@ -173,7 +173,9 @@ int mis_channel_sum(const float* x, long long x_bs, int N, int C, long long S, f
  * with `momentum` and the unbiased variance when running_* != NULL); per_sample = 1: per (n,c) over S
  * (InstanceNorm).  mean/rstd: G floats, G = C or N*C.  slope: 0.01 LeakyReLU, 0 ReLU.
  * Dropout mask = Philox(seed, offset, drop_salt, logical element index) from `state`, or an explicit
- * scale mask (0 or 1/(1-p), contiguous [N][C][S]) for parity tests; never stored. */
+ * scale mask (0 or 1/(1-p), contiguous [N][C][S]) for parity tests; never stored.
+ * mis_norm_workspace_bytes covers both users of the workspace: the double (sum, sumsq) partials of mis_norm_stats
+ * (16-byte aligned workspace) and the float partials + per-group sums of the backward entry points. */
 long long mis_norm_workspace_bytes(int N, int C, long long S, int per_sample);
 int mis_norm_stats(const float* x, long long x_bs, int N, int C, long long S, int per_sample, float eps,
                    float* mean, float* rstd, float* running_mean, float* running_var,
