@@ -253,11 +253,16 @@ PROTOTYPES = {
     "mis_sum_rowcycle": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_p]),
     "mis_augment2d": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "mis_crop_rotflip3d": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
+    # validation metrics
+    "mis_surface_metrics_workspace_bytes": (c_ll, [c_i, c_i, c_i]),
+    "mis_surface_metrics": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_ll, c_p]),
+    "mis_sq_edt": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_ll, c_p]),
 }
 
 STEP_STATE_BYTES = 40  # sizeof(MisStepState)
 AUG2D_BYTES = 88       # sizeof(MisAug2D)
 CROP3D_BYTES = 48      # sizeof(MisCrop3D)
+SURFACE_RECORD_WORDS = 12   # 8-byte fields of mis_surface_metrics' result record
 
 
 class StreamPtr(ctypes.c_void_p):

@@ -979,3 +979,51 @@ def argmax_channels(x, out):
     B, C, D, H, W, S, xbs = _geom(x)
     assert out.dtype == torch.uint8 and out.numel() == B * S
     _l.check(L.mis_argmax_channels(_l.ptr(x), xbs, _l.ptr(out), B, C, S, _l.stream_ptr()), "mis_argmax_channels")
+
+
+# ---------------------------------------------------------------- validation metrics
+def _label_geom(*maps):
+    """(ndim, D, H, W) of uint8 label maps of one shape, [D, H, W] or [H, W]; the wrapper refuses anything it would have to copy."""
+    _l.require_gpu(*maps)
+    first = maps[0]
+    for t in maps:
+        if t.dtype != torch.uint8:
+            raise RuntimeError(f"label maps must be uint8, got {t.dtype}")
+        if not t.is_contiguous():
+            raise RuntimeError("label maps must be contiguous")
+        if t.shape != first.shape:
+            raise RuntimeError(f"label maps differ in shape: {tuple(first.shape)} vs {tuple(t.shape)}")
+    if first.dim() not in (2, 3) or first.numel() == 0:
+        raise RuntimeError(f"expected a non-empty [D,H,W] or [H,W] label map, got {tuple(first.shape)}")
+    D, H, W = (1,) * (3 - first.dim()) + tuple(first.shape)
+    return first.dim(), D, H, W
+
+
+def _surface_workspace(L, D, H, W):
+    nbytes = L.mis_surface_metrics_workspace_bytes(D, H, W)
+    if nbytes < 0:
+        _l.check(nbytes, "mis_surface_metrics_workspace_bytes")
+    return scratch(nbytes, "surface_metrics"), nbytes
+
+
+def surface_metrics(pred_u8, gt_u8, cls):
+    """The result record of ``mis_surface_metrics`` (int64 [12] on the device; fields in include/mis_hip.h) for the masks
+    ``pred == cls`` / ``gt == cls`` (``cls = -1``: label > 0).  Nothing is synchronised: the caller reads the record when it wants
+    it (utils.metrics.device_scores)."""
+    L = _l.load()
+    ndim, D, H, W = _label_geom(pred_u8, gt_u8)
+    ws, nbytes = _surface_workspace(L, D, H, W)
+    out = torch.empty(_l.SURFACE_RECORD_WORDS, dtype=torch.int64, device=pred_u8.device)
+    _l.check(L.mis_surface_metrics(_l.ptr(pred_u8), _l.ptr(gt_u8), int(cls), ndim, D, H, W, _l.ptr(out), _l.ptr(ws), nbytes,
+                                   _l.stream_ptr()), "mis_surface_metrics")
+    return out
+
+
+def sq_edt(seeds_u8):
+    """Exact squared Euclidean distance (int32) of every voxel to the nearest non-zero voxel of ``seeds_u8``."""
+    L = _l.load()
+    ndim, D, H, W = _label_geom(seeds_u8)
+    ws, nbytes = _surface_workspace(L, D, H, W)
+    out = torch.empty(seeds_u8.shape, dtype=torch.int32, device=seeds_u8.device)
+    _l.check(L.mis_sq_edt(_l.ptr(seeds_u8), ndim, D, H, W, _l.ptr(out), _l.ptr(ws), nbytes, _l.stream_ptr()), "mis_sq_edt")
+    return out

@@ -8,9 +8,11 @@ Here the whole evaluation of a volume stays on the device and is batched: the vo
 windows go through the network per forward (``windows_per_launch``; eval-mode normalisation makes windows
 independent, so batching does not change any number), ``mis_softmax_mean_accumulate`` turns a batch of logits into
 probabilities in one launch, the score / hit-count volumes are resident, and the arg-max is ``mis_argmax_channels`` --
-one device->host copy per volume instead of one per patch.  ``cal_metric`` (reference :82-88) uses the medpy-free
-metrics of utils/metrics.py; ``test_all_case`` (:91-118) reads the cases through dataloaders.dataset.read_case
-(.h5 via h5py when installed, else .npz).
+one device->host copy per volume instead of one per patch.  ``cal_metric`` (reference :82-88) is the medpy-free host
+scoring of utils/metrics.py; ``test_all_case`` (:91-118) reads the cases through dataloaders.dataset.read_case (.h5 via
+h5py when installed, else .npz) and scores on the device: the label map never comes back, the ground truth is uploaded
+once per case and every class is one ``mis_surface_metrics`` call whose 96-byte record gives the very dice / hd95 of the
+host functions (``MIS_DEVICE_METRICS=0`` scores with ``cal_metric`` instead).
 """
 import itertools
 import math
@@ -38,7 +40,8 @@ def _centre_padding(shape, patch_size):
     return pads
 
 
-def test_single_case(net, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_launch=4):
+def single_case_device(net, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_launch=4):
+    """The label map of ``test_single_case`` as a contiguous uint8 device tensor (no download)."""
     shape = tuple(image.shape)
     pads = _centre_padding(shape, patch_size)
     vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).cuda()
@@ -71,9 +74,13 @@ def test_single_case(net, image, stride_xy, stride_z, patch_size, num_classes=1,
             ops.argmax_channels(scores.unsqueeze(0), labels)
     finally:
         net.train(was_training)
-    label_map = labels.view(padded).cpu().numpy().astype(np.int64)
     crop = tuple(slice(lo, lo + extent) for (lo, _), extent in zip(pads, shape))
-    return label_map[crop]
+    return labels.view(padded)[crop].contiguous()
+
+
+def test_single_case(net, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_launch=4):
+    return single_case_device(net, image, stride_xy, stride_z, patch_size, num_classes,
+                              windows_per_launch).cpu().numpy().astype(np.int64)
 
 
 def cal_metric(gt, pred):
@@ -81,6 +88,14 @@ def cal_metric(gt, pred):
     if pred.sum() == 0 or gt.sum() == 0:
         return np.zeros(2)
     return np.array([metric.dc(pred, gt), metric.hd95(pred, gt)])
+
+
+def device_cal_metric(scores):
+    """``cal_metric`` from a ``utils.metrics.SurfaceScores``: the same rule, decided from the counts."""
+    c = scores.counts
+    if c["a"] == 0 or c["b"] == 0:
+        return np.zeros(2)
+    return np.array([scores.dc, scores.hd95])
 
 
 def test_all_case(net, base_dir, test_list="full_test.list", num_classes=4, patch_size=(48, 160, 160), stride_xy=32,
@@ -95,9 +110,16 @@ def test_all_case(net, base_dir, test_list="full_test.list", num_classes=4, patc
     total = np.zeros((num_classes - 1, 2))
     for case in mine:
         image, label = read_case("{}/data/{}".format(base_dir, case))
-        prediction = test_single_case(net, image, stride_xy, stride_z, patch_size, num_classes=num_classes)
+        gt = metric.device_label_map(label) if metric.device_metrics_enabled() else None
+        if gt is None:
+            prediction = test_single_case(net, image, stride_xy, stride_z, patch_size, num_classes=num_classes)
+            for c in range(1, num_classes):
+                total[c - 1] += cal_metric(label == c, prediction == c)
+            continue
+        prediction = single_case_device(net, image, stride_xy, stride_z, patch_size, num_classes=num_classes)
+        scores = [metric.device_scores(prediction, gt, c) for c in range(1, num_classes)]   # launched before the first read
         for c in range(1, num_classes):
-            total[c - 1] += cal_metric(label == c, prediction == c)
+            total[c - 1] += device_cal_metric(scores[c - 1])
     if shard is not None:
         return total, len(mine)
     return total / len(cases)

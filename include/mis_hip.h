@@ -839,6 +839,33 @@ long long mis_conv1x1_wgrad_workspace_bytes(int N, int M, int Nc, long long S);
 int mis_conv1x1_wgrad(const float* a, long long a_bs, const float* b, long long b_bs, float* dw, long long ldw, int N, int M, int Nc,
                       long long S, int accumulate, float* workspace, long long workspace_bytes, mis_stream_t stream);
 
+/* ---- validation metrics: surface distances of two label maps, scored on the device ------------------------
+ * reference: the medpy calls of the scoring functions -- dc / hd95 of calculate_metric_percase code/val_2D.py:7-15 and
+ *            cal_metric code/val_3D.py:82-88 (bound here: val_2D.test_single_volume, val_3D.test_all_case);
+ *            dc / ravd / hd95 / asd code/test_3D_util.py:147-152 and dc / asd / hd code/test_CNNVIT.py:33-39 (the record
+ *            holds what they need; the inference drop-ins of this tree still call the host functions).
+ *            utils/metrics.py restates all of them on numpy/scipy and stays the oracle.
+ * pred, gt: uint8 label maps of one shape, [D][H][W] (ndim 3) or [H][W] (ndim 2, D == 1); masks A = (pred == cls),
+ * B = (gt == cls), cls = -1: label > 0.  A surface voxel is a mask voxel with a face neighbour (6 / 4 of them) outside
+ * the mask or outside the array (binary_erosion, connectivity 1, border_value 0: a 3-D array with D == 1 is all surface).
+ * mis_surface_metrics writes a record of 12 8-byte fields to `out`:
+ *   [0..4]  int64  |A|, |B|, |A & B|, |dA|, |dB|
+ *   [5],[6] int64  largest squared distance from dA to dB, from dB to dA               (-1 when a mask is empty)
+ *   [7],[8] double sum of sqrt(squared distance) over dA (to dB), over dB (to dA), fixed order
+ *   [9],[10] int64 squared distances at the sorted positions lo = floor(0.95 * (n - 1)) and min(lo + 1, n - 1) of the
+ *                  union of both directions, n = |dA| + |dB| (numpy's linear 95th percentile lies between them; -1 when unset)
+ *   [11]    int64  1 when both masks are non-empty (the distance fields are set), else 0
+ * Distances are exact: a separable squared Euclidean distance transform in int32 and a histogram over squared distances
+ * (integer atomics only), so the record is run-to-run identical.  Unit voxel spacing.
+ * mis_sq_edt: the transform alone, out[v] = squared distance to the nearest non-zero voxel of seeds (INT32_MAX when
+ * there is none).  Both take workspace >= mis_surface_metrics_workspace_bytes(D, H, W) (cleared inside, on `stream`), never
+ * synchronise or allocate; an extent above 1024 or ndim outside {2, 3} is MIS_ERR_UNSUPPORTED. */
+long long mis_surface_metrics_workspace_bytes(int D, int H, int W);
+int mis_surface_metrics(const unsigned char* pred, const unsigned char* gt, int cls, int ndim, int D, int H, int W,
+                        void* out, void* workspace, long long workspace_bytes, mis_stream_t stream);
+int mis_sq_edt(const unsigned char* seeds_u8, int ndim, int D, int H, int W, int* out_i32, void* workspace,
+               long long workspace_bytes, mis_stream_t stream);
+
 /* Test support (never on the product path): fills the LDS of every CU with NaNs so that a kernel reading LDS it did not write
  * fails deterministically instead of depending on the previous launch.  sink: any device float (or NULL). */
 int mis_debug_poison_lds(float* sink, mis_stream_t stream);
