@@ -142,6 +142,8 @@ PROTOTYPES = {
     "mis_dice_loss_fwd": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_ll, c_p]),
     "mis_dice_loss_bwd": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_ll, c_p]),
     "mis_softmax_mse": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_p]),
+    "mis_patch_nce_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
+    "mis_patch_nce": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_f, c_f, c_p, c_p, c_ll, c_p, c_ll, c_p]),
     "mis_ema_update": (c_i, [c_p, c_p, c_ll, c_f, c_p]),
     "mis_sgd_ema_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
     "mis_teacher_noise": (c_i, [c_p, c_p, c_ll, c_f, c_f, c_u, c_p, c_p]),

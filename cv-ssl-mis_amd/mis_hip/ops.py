@@ -926,6 +926,56 @@ def triple_view_tail(z1, z2, z3, label, labeled_bs, outs, dlogits=None, cons_wei
              "mis_triple_view_tail")
 
 
+PATCH_NCE_DIMS = (16, 32)     # feature dims mis_patch_nce is built for (the reference's projector and classifier heads)
+
+
+def _geom_features(t):
+    """(B, d, N, batch_stride) of a fp32 feature view [B, d, *spatial]: dense in (d, spatial), free batch stride."""
+    if t.dim() < 3 or t.dtype != torch.float32:
+        raise RuntimeError(f"expected fp32 [B, d, *spatial], got {tuple(t.shape)} {t.dtype}")
+    _l.require_gpu(t)
+    B, d = t.shape[0], t.shape[1]
+    N = 1
+    for n in t.shape[2:]:
+        N *= n
+    if B < 1 or d < 1 or N < 1:
+        raise RuntimeError(f"empty feature tensor {tuple(t.shape)}")
+    want = 1
+    for size, stride in zip(reversed(t.shape[1:]), reversed(t.stride()[1:])):
+        if size > 1 and stride != want:
+            raise RuntimeError(f"feature view must be dense in (d, spatial); strides {t.stride()} shape {tuple(t.shape)}")
+        want *= size
+    bs = t.stride(0) if B > 1 else d * N
+    if bs < d * N:
+        raise RuntimeError(f"batch stride {bs} of a feature view overlaps its samples ({d} x {N})")
+    return B, d, N, bs
+
+
+def patch_nce(feat_q, feat_k, out, dfeat=None, temperature=0.07, grad_scale=1.0):
+    """Pixel-wise contrastive loss of ``feat_q`` against the detached ``feat_k`` (both ``[B, d, *spatial]``, d in
+    ``PATCH_NCE_DIMS``; reference code/utils/losses.py:283-337): ``out`` (>= 3 floats) = [loss, mean s_ii, mean
+    logsumexp_j s_ij]; ``dfeat``: ``grad_scale * d loss / d feat_q`` with respect to the raw features, or None for the
+    loss alone.  One flash-style pass: no [B, N, N] tensor, the workspace is linear in B * N * d."""
+    L = _l.load()
+    B, d, N, qbs = _geom_features(feat_q)
+    Bk, dk, Nk, kbs = _geom_features(feat_k)
+    assert (Bk, dk, Nk) == (B, d, N), (tuple(feat_q.shape), tuple(feat_k.shape))
+    if d not in PATCH_NCE_DIMS:
+        raise RuntimeError(f"patch_nce: feature dim {d} is not supported (supported dims: {PATCH_NCE_DIMS})")
+    _l.require_gpu(out)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 3
+    dbs = 0
+    if dfeat is not None:
+        Bd, dd, Nd, dbs = _geom_features(dfeat)
+        assert (Bd, dd, Nd) == (B, d, N), (tuple(feat_q.shape), tuple(dfeat.shape))
+    nb = L.mis_patch_nce_workspace_bytes(B, d, N)
+    if nb < 0:
+        _l.check(nb, "mis_patch_nce_workspace_bytes")
+    ws = scratch(nb, "patch_nce")
+    _l.check(L.mis_patch_nce(_l.ptr(feat_q), qbs, _l.ptr(feat_k), kbs, B, d, N, float(temperature), float(grad_scale),
+                             _l.ptr(out), _l.ptr(dfeat), dbs, _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_patch_nce")
+
+
 # ------------------------------------------------------------ optimizer / rng
 def sgd_ema_step(param, grad, momentum_buf, ema_param, lr=0.0, momentum=0.9, weight_decay=1e-4, ema_alpha=0.99,
                  grad_scale=1.0, state=None):

@@ -1,9 +1,10 @@
 """``utils.losses`` surface of the reference on HIP kernels (code/utils/losses.py).
 
-Only the two losses on the Mean-Teacher hot path are provided: ``DiceLoss`` (:165-201) and
-``softmax_mse_loss`` (:74-91).  Both are autograd-aware and run on the device through the C-ABI
-(``mis_dice_loss_*`` / ``mis_softmax_mse``); there is no CPU implementation here.  The fused training
-step (``mis_hip.step``) does not call these -- it uses the single-pass fused loss tail instead.
+The two losses on the Mean-Teacher hot path, ``DiceLoss`` (:165-201) and ``softmax_mse_loss`` (:74-91), and the
+pixel-wise contrastive loss of the contrastive trainers, ``ConLoss`` (:283-337) / ``contrastive_loss_sup`` (:479-531).
+All are autograd-aware and run on the device through the C-ABI (``mis_dice_loss_*`` / ``mis_softmax_mse`` /
+``mis_patch_nce``); there is no CPU implementation here.  The fused training step (``mis_hip.step``) does not call
+these -- it uses the single-pass fused loss tail instead.
 """
 import torch
 import torch.nn as nn
@@ -103,6 +104,53 @@ def softmax_mse_loss(input_logits, target_logits, sigmoid=False):
     if sigmoid:
         raise NotImplementedError("sigmoid=True is not on the Mean-Teacher hot path")
     return _SoftmaxMseFn.apply(input_logits, target_logits.detach())
+
+
+class _PatchNceFn(torch.autograd.Function):
+    """One ``mis_patch_nce`` call in the forward: the loss and d loss / d feat_q come from the same walk over the keys, so
+    the backward only scales the kept gradient by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, feat_q, feat_k, temperature):
+        out = torch.empty(3, dtype=torch.float32, device=feat_q.device)
+        dfeat = torch.empty_like(feat_q) if ctx.needs_input_grad[0] else None
+        _ops.patch_nce(feat_q, feat_k, out, dfeat=dfeat, temperature=temperature)
+        ctx.save_for_backward(dfeat)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, gloss):
+        dfeat, = ctx.saved_tensors
+        # feat_k is detached in the reference (:308); dfeat is None when only feat_k asked for a gradient
+        return (None if dfeat is None else dfeat * gloss), None, None
+
+
+def _patch_nce_loss(feat_q, feat_k, temperature):
+    assert feat_q.size() == feat_k.size(), (feat_q.size(), feat_k.size())
+    _l.require_gpu(feat_q, feat_k)
+    if feat_q.dtype != torch.float32 or feat_k.dtype != torch.float32 or feat_q.dim() < 3 or \
+            feat_q.shape[1] not in _ops.PATCH_NCE_DIMS:
+        raise RuntimeError(f"contrastive loss: expected fp32 [B, d, *spatial] features with d in {_ops.PATCH_NCE_DIMS} "
+                           f"(supported dims), got {tuple(feat_q.shape)} {feat_q.dtype} / {feat_k.dtype}")
+    return _PatchNceFn.apply(feat_q.contiguous(), feat_k.detach().contiguous(), float(temperature))
+
+
+class ConLoss(nn.Module):
+    """Drop-in for ``losses.ConLoss`` (code/utils/losses.py:283-337): PatchNCE over every pixel pair of one sample's
+    feature map, the negatives of a pixel being the other pixels of the same sample.  No [B, N, N] tensor is built."""
+
+    def __init__(self, temperature=0.07, base_temperature=0.07):
+        super().__init__()
+        self.temperature = temperature
+        self.base_temperature = base_temperature      # kept for the signature: the reference never reads it
+
+    def forward(self, feat_q, feat_k):
+        return _patch_nce_loss(feat_q, feat_k, self.temperature)
+
+
+class contrastive_loss_sup(ConLoss):
+    """Drop-in for ``losses.contrastive_loss_sup`` (code/utils/losses.py:479-531, the definition in force): the same
+    arithmetic as ``ConLoss``."""
 
 
 def update_ema_variables(model, ema_model, alpha, global_step):

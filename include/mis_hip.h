@@ -432,6 +432,23 @@ int mis_dice_loss_bwd(const float* probs, long long p_bs, const void* label, int
 int mis_softmax_mse(const float* input_logits, long long a_bs, const float* target_logits, long long b_bs,
                     const float* grad_out, long long g_bs, float* out, long long o_bs, int B, int C, long long S,
                     int backward, mis_stream_t stream);
+/* Pixel-wise contrastive (PatchNCE) loss: losses.ConLoss code/utils/losses.py:283-337 and losses.contrastive_loss_sup
+ * :479-531 (the same arithmetic), forward and gradient in one call, without an N x N object in memory.
+ * feat_q, feat_k: [B][d][N] fp32, the d channel planes contiguous with plane stride N, batch strides q_bs / k_bs in floats
+ * (>= d * N); no alignment beyond 4 bytes; N >= 1 is arbitrary (N = prod(spatial)); d in {16, 32}, any other d is
+ * MIS_ERR_UNSUPPORTED.  With q^_i = f_i / max(|f_i|_1, 1e-12), k^_j likewise (F.normalize, p = 1) and
+ * s_ij = q^_i . k^_j / temperature inside one sample:
+ *   out[0] = loss = mean over the B * N rows of (logsumexp_j s_ij - s_ii),  out[1] = mean_i s_ii,
+ *   out[2] = mean_i logsumexp_j s_ij                                          (out: >= 3 floats)
+ *   dfeat_q = grad_scale * d loss / d feat_q (with respect to the RAW features: the backward of the normalisation is
+ *   inside), [B][d][N] with batch stride dq_bs; NULL: loss only, and out is bit-identical to the call with a gradient.
+ * feat_k is detached: no gradient.  Deterministic (no atomics).  workspace >= mis_patch_nce_workspace_bytes(B, d, N),
+ * which is linear in B * N * d (about 16 bytes per feature element).  NULL pointers, non-positive sizes / strides /
+ * temperature: MIS_ERR_ARG before any launch; a workspace that is too small: MIS_ERR_WORKSPACE. */
+long long mis_patch_nce_workspace_bytes(int B, int d, long long N);
+int mis_patch_nce(const float* feat_q, long long q_bs, const float* feat_k, long long k_bs, int B, int d, long long N,
+                  float temperature, float grad_scale, float* out, float* dfeat_q, long long dq_bs, void* workspace,
+                  long long workspace_bytes, mis_stream_t stream);
 /* ema = alpha*ema + (1-alpha)*param over a flat buffer (update_ema_variables, train_mean_teacher_2D.py:124-128) */
 int mis_ema_update(float* ema_param, const float* param, long long n, float alpha, mis_stream_t stream);
 
