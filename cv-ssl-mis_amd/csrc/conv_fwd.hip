@@ -230,6 +230,20 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(const ConvFwdArgs a) {
     };
 
     // ---- software pipeline over chunks of CI_B input channels: DMA(k+1) || MFMA(k) ----
+    // The MFMA accumulates as one fp32 fmaf chain, whose rounding error grows with its length: over all Cin * TAPS
+    // products of a deep 3-D layer (256 channels x 27 taps) it is 4 .. 8 x that of a blocked fp32 sum
+    // (tests/test_conv_edges_gpu.py).  The small-tile 3x3x3 configurations -- the deep levels: many channels, few
+    // voxels -- hold at most 32 accumulator registers, so they can afford a second set: `acc` restarts with every
+    // chunk (CI_B * TAPS products) and is folded into `tot`, a chain of nchunks additions.  The 2-D configurations keep
+    // the single chain (same test: 3.3 .. 6.6 x at the 4 x 4 level).
+    constexpr bool FOLD = C::KD == 3 && C::NT <= 4;
+    f32x4 tot[FOLD ? C::M : 1][FOLD ? C::NT : 1];
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int m = 0; m < C::M; ++m)
+#pragma unroll
+            for (int i = 0; i < C::NT; ++i) tot[m][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     const int nchunks = (a.Cin_pad + C::CI_B - 1) / C::CI_B;
     stage(0, 0);
     dma_wait();
@@ -237,8 +251,23 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(const ConvFwdArgs a) {
     for (int k = 0; k < nchunks; ++k) {
         if (k + 1 < nchunks) stage((k + 1) & 1, (k + 1) * C::CI_B);
         compute(lds + (k & 1) * C::STAGE);
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int m = 0; m < C::M; ++m)
+#pragma unroll
+                for (int i = 0; i < C::NT; ++i) {
+                    tot[m][i] += acc[m][i];
+                    acc[m][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
         dma_wait();
         __syncthreads();   // chunk k+1 landed in the other buffer and every wave is done reading chunk k
+    }
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int m = 0; m < C::M; ++m)
+#pragma unroll
+            for (int i = 0; i < C::NT; ++i) acc[m][i] = tot[m][i];
     }
 
     // ---- epilogue: bias + store.  D: row = lk*4 + r -> channel, col = lj -> pixel pair (2j, 2j+1) ----

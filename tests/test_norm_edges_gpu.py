@@ -113,6 +113,12 @@ def _ops():
     return ops
 
 
+def finalize_factor(mean64, var64):
+    """Conditioning of one-pass statistics from fp32 partials (module docstring): the factor rstd and running_var get per
+    group in mis_norm_stats_finalize's tests (tests/test_conv_edges_gpu.py holds the split Winograd forward's to it too)."""
+    return 1.0 + mean64 ** 2 / (var64 + no.EPS)
+
+
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
@@ -438,7 +444,7 @@ def test_stats_finalize(name):
     part = no.tile_partials(c["x"], T, per_sample).cuda()
     G = N * C if per_sample else C
     mean, rstd = _nanvec(G), _nanvec(G)
-    factor = 1.0 + r64["mean"] ** 2 / (r64["var"] + no.EPS)
+    factor = finalize_factor(r64["mean"], r64["var"])
     if c["ratio"] == 0 and no.group_elems(c["x"].shape, c["kind"]) >= 2000:     # (a group of 8 .. 520 values has a sample mean)
         assert factor.max().item() < 1.01
     if per_sample:
