@@ -20,21 +20,6 @@
 
 namespace {
 
-struct Aug2D {   // == MisAug2D
-    long long img_off, lab_off;   // element offsets of the slice in the pools
-    int H, W;                     // slice size
-    int mode;                     // 0: none, 1: rot90(k) + flip(axis), 2: rotate(matrix, offset)
-    int k, axis, pad_;
-    double m00, m01, m10, m11, off0, off1;
-};
-
-struct Crop3D {  // == MisCrop3D
-    long long img_off, lab_off;
-    int d0, d1, d2;               // volume size (w, h, d)
-    int k, axis;                  // rot90 in the (0, 1) plane, flip along axis 0 | 1
-    int o0, o1, o2;               // crop origin in the rotated+flipped (and zero-padded) volume, may be negative
-};
-
 // source index of element (y, x) of flip(rot90(src, k), axis); src is H x W
 __device__ __forceinline__ void undo_rotflip(int k, int axis, int H, int W, int y, int x, int& sy, int& sx) {
     const int Ht = (k & 1) ? W : H, Wt = (k & 1) ? H : W;
@@ -58,10 +43,10 @@ __device__ __forceinline__ int zoom_src(int kk, int n_in, int n_out) {
 // grid = (ceil(out_w*out_h / 256), B)
 __global__ __launch_bounds__(256) void augment2d_kernel(const float* __restrict__ img_pool,
                                                         const unsigned char* __restrict__ lab_pool,
-                                                        const Aug2D* __restrict__ params, int out_h, int out_w,
+                                                        const MisAug2D* __restrict__ params, int out_h, int out_w,
                                                         float* __restrict__ image_out,
                                                         unsigned char* __restrict__ label_out) {
-    const Aug2D p = params[blockIdx.y];
+    const MisAug2D p = params[blockIdx.y];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= out_h * out_w) return;
     const int oy = i / out_w, ox = i - oy * out_w;
@@ -93,10 +78,10 @@ __global__ __launch_bounds__(256) void augment2d_kernel(const float* __restrict_
 // grid = (ceil(p0*p1*p2 / 256), B); innermost output dim == innermost source dim (coalesced both ways)
 __global__ __launch_bounds__(256) void crop_rotflip3d_kernel(const float* __restrict__ img_pool,
                                                              const unsigned char* __restrict__ lab_pool,
-                                                             const Crop3D* __restrict__ params, int p0, int p1, int p2,
+                                                             const MisCrop3D* __restrict__ params, int p0, int p1, int p2,
                                                              float* __restrict__ image_out, void* __restrict__ label_out,
                                                              int label_bytes) {
-    const Crop3D p = params[blockIdx.y];
+    const MisCrop3D p = params[blockIdx.y];
     const long long n = (long long)p0 * p1 * p2;
     const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= n) return;
@@ -125,22 +110,22 @@ __global__ __launch_bounds__(256) void crop_rotflip3d_kernel(const float* __rest
 
 extern "C" int mis_augment2d(const float* img_pool, const unsigned char* lab_pool, const void* params, int B,
                              int out_h, int out_w, float* image_out, unsigned char* label_out, hipStream_t stream) {
-    static_assert(sizeof(Aug2D) == 88, "MisAug2D layout");
+    static_assert(sizeof(MisAug2D) == 88, "MisAug2D layout");
     if (!img_pool || !params || !image_out || B <= 0 || out_h <= 0 || out_w <= 0) return MIS_ERR_ARG;
     if (label_out && !lab_pool) return MIS_ERR_ARG;
     hipLaunchKernelGGL(augment2d_kernel, dim3((unsigned)mis_cdiv((long long)out_h * out_w, 256), B), dim3(256), 0, stream,
-                       img_pool, lab_pool, reinterpret_cast<const Aug2D*>(params), out_h, out_w, image_out, label_out);
+                       img_pool, lab_pool, reinterpret_cast<const MisAug2D*>(params), out_h, out_w, image_out, label_out);
     return mis_launch_status();
 }
 
 extern "C" int mis_crop_rotflip3d(const float* img_pool, const unsigned char* lab_pool, const void* params, int B,
                                   int p0, int p1, int p2, float* image_out, void* label_out, int label_bytes,
                                   hipStream_t stream) {
-    static_assert(sizeof(Crop3D) == 48, "MisCrop3D layout");
+    static_assert(sizeof(MisCrop3D) == 48, "MisCrop3D layout");
     if (!img_pool || !params || !image_out || B <= 0 || p0 <= 0 || p1 <= 0 || p2 <= 0) return MIS_ERR_ARG;
     if (label_out && (!lab_pool || (label_bytes != 1 && label_bytes != 8))) return MIS_ERR_ARG;
     hipLaunchKernelGGL(crop_rotflip3d_kernel, dim3((unsigned)mis_cdiv((long long)p0 * p1 * p2, 256), B), dim3(256), 0,
-                       stream, img_pool, lab_pool, reinterpret_cast<const Crop3D*>(params), p0, p1, p2, image_out,
+                       stream, img_pool, lab_pool, reinterpret_cast<const MisCrop3D*>(params), p0, p1, p2, image_out,
                        label_out, label_bytes);
     return mis_launch_status();
 }

@@ -5,11 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MIS_OK 0
-#define MIS_ERR_ARG (-1)          // bad pointer / size / stride
-#define MIS_ERR_UNSUPPORTED (-2)  // shape the kernel family does not cover
-#define MIS_ERR_LAUNCH (-3)       // hipGetLastError() after launch
-#define MIS_ERR_WORKSPACE (-4)    // caller workspace too small
+// The C ABI: every extern "C" definition of the library is compiled against its declaration (a mismatch is a compile error),
+// and MIS_OK / MIS_ERR_*, MisStepState, MisAug2D and MisCrop3D come from there.  MIS_HIP_BUILD makes mis_stream_t hipStream_t.
+#define MIS_HIP_BUILD 1
+#include "../../include/mis_hip.h"
+static_assert(sizeof(MisStepState) == 40, "MisStepState layout");
 
 #define MIS_NUM_XCD 8
 #define MIS_WAVE 64
@@ -263,19 +263,6 @@ __device__ __forceinline__ void mis_philox4(uint32_t c0, uint32_t c1, uint32_t c
 
 // uniform in [0,1) from 32 random bits (24-bit mantissa path, never returns 1)
 __device__ __forceinline__ float mis_u01(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
-
-// Device-resident step state: lets a captured hipGraph replay with fresh
-// dropout masks, learning rate, EMA alpha and consistency weight without
-// re-capture or a per-step host->device copy.  Advanced by mis_step_advance().
-struct MisStepState {
-    uint64_t seed;       // Philox key
-    uint64_t offset;     // RNG offset, +1 per step
-    int64_t iter_num;    // reference's iter_num (train_mean_teacher_2D.py:198)
-    float lr;            // SGD learning rate of this step
-    float ema_alpha;     // EMA decay of this step
-    float cons_weight;   // consistency weight of this step (0 while gated off)
-    float cons_gate;     // 1 if the consistency term is live this step, else 0
-};
 
 // Exact-form (erf) GELU, nn.GELU() of the reference (swin_transformer_unet_skip_expand_decoder_sys.py:10,15):
 //   gelu(x) = x Phi(x),  gelu'(x) = Phi(x) + x u / sqrt(2 pi),  u = exp(-x^2 / 2).

@@ -339,7 +339,7 @@ extern "C" long long mis_patch_nce_workspace_bytes(int B, int d, long long N) {
 
 extern "C" int mis_patch_nce(const float* feat_q, long long q_bs, const float* feat_k, long long k_bs, int B, int d,
                              long long N, float temperature, float grad_scale, float* out, float* dfeat_q, long long dq_bs,
-                             void* workspace, long long workspace_bytes, void* stream) {
+                             void* workspace, long long workspace_bytes, hipStream_t stream) {
     if (!feat_q || !feat_k || !out || !workspace) return MIS_ERR_ARG;
     if (B <= 0 || d <= 0 || N <= 0 || !(temperature > 0.f)) return MIS_ERR_ARG;
     if (q_bs < (long long)d * N || k_bs < (long long)d * N || (dfeat_q && dq_bs < (long long)d * N)) return MIS_ERR_ARG;
@@ -347,8 +347,7 @@ extern "C" int mis_patch_nce(const float* feat_q, long long q_bs, const float* f
     if (st != MIS_OK) return st;
     if (workspace_bytes < mis_patch_nce_workspace_bytes(B, d, N)) return MIS_ERR_WORKSPACE;
     float* ws = reinterpret_cast<float*>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-    hipStream_t s = (hipStream_t)stream;
     if (d == 16)
-        return pn_launch<16>(feat_q, q_bs, feat_k, k_bs, B, (int)N, temperature, grad_scale, out, dfeat_q, dq_bs, ws, s);
-    return pn_launch<32>(feat_q, q_bs, feat_k, k_bs, B, (int)N, temperature, grad_scale, out, dfeat_q, dq_bs, ws, s);
+        return pn_launch<16>(feat_q, q_bs, feat_k, k_bs, B, (int)N, temperature, grad_scale, out, dfeat_q, dq_bs, ws, stream);
+    return pn_launch<32>(feat_q, q_bs, feat_k, k_bs, B, (int)N, temperature, grad_scale, out, dfeat_q, dq_bs, ws, stream);
 }

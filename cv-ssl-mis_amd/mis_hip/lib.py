@@ -6,12 +6,14 @@ only used for device memory (``tensor.data_ptr()``) and the current HIP stream.
 """
 import ctypes
 import os
+import re
 
 import torch  # imported first on purpose: libmis_hip.so binds to the libamdhip64 torch has loaded
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MIS_HIP_LIB overrides the library file (A/B timing of kernel variants); it is still a HIP build
 LIB_PATH = os.environ.get("MIS_HIP_LIB") or os.path.join(_HERE, "libmis_hip.so")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "mis_hip.h"))
 
 _lib = None
 
@@ -22,248 +24,64 @@ _ERRORS = {
     -4: "MIS_ERR_WORKSPACE (workspace too small)",
 }
 
-c_p = ctypes.c_void_p
-c_i = ctypes.c_int
-c_ll = ctypes.c_longlong
-c_f = ctypes.c_float
-c_d = ctypes.c_double
-c_u = ctypes.c_uint
-c_ull = ctypes.c_ulonglong
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+            "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "unsigned long long": ctypes.c_ulonglong}
+_POINTEES = set(_SCALARS) | {"void", "char", "unsigned char", "MisStepState"}
 
-# name -> (restype, argtypes); must stay in sync with include/mis_hip.h
-PROTOTYPES = {
-    "mis_abi_version": (c_i, []),
-    "mis_conv_cin_pad": (c_i, [c_i]),
-    "mis_conv_cout_pad": (c_i, [c_i]),
-    "mis_conv_packed_floats": (c_ll, [c_i, c_i, c_i, c_i]),
-    "mis_conv_pack_weights": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "mis_conv_pack_job_bytes": (c_i, []),
-    "mis_conv_pack_job": (c_ll, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_ll]),
-    "mis_conv_pack_batch": (c_i, [c_p, c_i, c_ll, c_p]),
-    "mis_conv_fwd": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_conv_fwd_stat_tiles": (c_ll, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv_fwd_stats": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll,
-                                 c_ll, c_p]),
-    "mis_norm_stats_finalize": (c_i, [c_p, c_i, c_i, c_ll, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_f, c_p]),
-    "mis_conv_fwd_kernel_name": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_char_p, c_i]),
-    "mis_conv3d_wino_select": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv3d_wino_stat_tiles": (c_ll, [c_i, c_i, c_i, c_i]),
-    "mis_conv3d_wino_kernel_name": (c_i, [c_i, ctypes.c_char_p, c_i]),
-    "mis_conv3d_wino_fwd": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_ll, c_i, c_p]),
-    "mis_conv1x1_gemm_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_ll]),
-    "mis_conv1x1_gemm": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_ll, c_i, c_p, c_ll, c_p]),
-    "mis_conv1x1_wgrad_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_ll]),
-    "mis_conv1x1_wgrad": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_ll, c_i, c_p, c_ll, c_p]),
-    "mis_conv3d_wino_fwd_splits": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv3d_wino_fwd_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv3d_wino_fwd_ws": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_ll, c_i, c_p, c_ll,
-                                     c_p]),
-    "mis_conv3d_wino_dgrad_norm": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_f, c_p,
-                                         c_ll, c_ll, c_i, c_p]),
-    "mis_norm_res_act_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_i, c_p]),
-    "mis_norm_res_act_bwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_ll, c_i, c_p, c_p,
-                                   c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_norm_act_bwd_tiles": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_p, c_p, c_f, c_p, c_i, c_p, c_p]),
-    "mis_conv2d_wino_select": (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv2d_wino_stat_tiles": (c_ll, [c_i, c_i, c_i]),
-    "mis_conv2d_wino_kernel_name": (c_i, [c_i, ctypes.c_char_p, c_i]),
-    "mis_conv2d_wino_fwd": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_ll, c_i, c_p]),
-    "mis_conv2d_wino_wgrad_select": (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv2d_wino_wgrad_kernel_name": (c_i, [c_i, ctypes.c_char_p, c_i]),
-    "mis_conv2d_wino_wgrad_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv2d_wino_wgrad": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_conv3d_wino_wgrad_select": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv3d_wino_wgrad_kernel_name": (c_i, [c_i, ctypes.c_char_p, c_i]),
-    "mis_conv3d_wino_wgrad_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv3d_wino_wgrad": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_conv_wgrad_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv_wgrad_kernel_name": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_char_p, c_i]),
-    "mis_conv_wgrad": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                             c_i, c_p]),
-    "mis_norm_workspace_bytes": (c_ll, [c_i, c_i, c_ll, c_i]),
-    "mis_norm_stats": (c_i, [c_p, c_ll, c_i, c_i, c_ll, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_ll, c_p]),
-    "mis_channel_sum": (c_i, [c_p, c_ll, c_i, c_i, c_ll, c_p, c_i, c_p, c_ll, c_p]),
-    "mis_norm_stats_from_running":(c_i, [c_p, c_p, c_f, c_p, c_p, c_i, c_p]),
-    "mis_norm_act_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_u, c_p,
-                               c_p, c_p]),
-    "mis_norm_act_bwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_f,
-                               c_u, c_p, c_p, c_p, c_p, c_i, c_p, c_ll, c_p]),
-    "mis_norm_act_fwd_g": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_u, c_p,
-                                 c_p, c_p]),
-    "mis_norm_act_bwd_g": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_f,
-                                 c_f, c_u, c_p, c_p, c_p, c_p, c_i, c_p, c_ll, c_p]),
-    "mis_norm_act_fwd_pool": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p,
-                                    c_p, c_f, c_f, c_u, c_p, c_p, c_p]),
-    "mis_norm_act_bwd_pool": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p,
-                                    c_p, c_p, c_p, c_f, c_f, c_u, c_p, c_p, c_p, c_p, c_i, c_p, c_ll, c_p]),
-    "mis_norm_act_bwd_sums": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_i,
-                                    c_p, c_ll, c_p]),
-    "mis_conv_wgrad_cin1_norm_eligible": (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv_wgrad_cin1_norm": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p,
-                                       c_f, c_p, c_p, c_ll, c_i, c_p]),
-    "mis_norm_head_eligible": (c_i, [c_i, c_i]),
-    "mis_norm_head_workspace_bytes": (c_ll, [c_i, c_i, c_ll, c_i, c_i]),
-    "mis_norm_head_fwd": (c_i, [c_p, c_ll, c_i, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_u, c_p, c_p, c_p, c_p, c_i,
-                                c_p, c_ll, c_p]),
-    "mis_norm_head_bwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_u,
-                                c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_ll, c_p]),
-    "mis_maxpool2_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_maxpool2_bwd": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_upsample2_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_upsample2_bwd": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_loss_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
-    "mis_loss_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_f, c_p, c_p, c_ll,
-                            c_p, c_ll, c_p]),
-    "mis_cross_teaching_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
-    "mis_cross_teaching_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_p, c_p, c_ll,
-                                      c_p, c_ll, c_p]),
-    "mis_softmax_mean_accumulate": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_ll, c_f, c_i, c_p]),
-    "mis_uamt_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
-    "mis_uamt_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_ll, c_d, c_f,
-                            c_p, c_p, c_ll, c_p, c_ll, c_p]),
-    "mis_beta_sample": (c_i, [c_p, c_i, c_d, c_u, c_p, c_p]),
-    "mis_ict_mix": (c_i, [c_p, c_p, c_p, c_i, c_i, c_ll, c_p]),
-    "mis_ict_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
-    "mis_ict_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_f, c_p, c_p,
-                           c_ll, c_p, c_ll, c_p]),
-    "mis_rot90": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_i, c_p]),
-    "mis_dct_tail_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i, c_i]),
-    "mis_dct_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_i, c_f, c_f, c_p, c_p,
-                           c_ll, c_p, c_ll, c_p, c_ll, c_p]),
-    "mis_grad_combine": (c_i, [c_p, c_p, c_ll, c_i, c_p]),
-    "mis_triple_view_tail_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
-    "mis_triple_view_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_p, c_p, c_p,
-                                   c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p]),
-    "mis_cross_pseudo_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_p, c_i, c_p, c_p, c_ll,
-                                    c_p, c_ll, c_p]),
-    "mis_cross_pseudo_mt_tail": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_ll, c_f, c_f, c_p,
-                                       c_i, c_p, c_p, c_ll, c_p, c_ll, c_p]),
-    "mis_dice_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
-    "mis_dice_loss_fwd": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_ll, c_p]),
-    "mis_dice_loss_bwd": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_ll, c_p]),
-    "mis_softmax_mse": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_i, c_p]),
-    "mis_patch_nce_workspace_bytes": (c_ll, [c_i, c_i, c_ll]),
-    "mis_patch_nce": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_f, c_f, c_p, c_p, c_ll, c_p, c_ll, c_p]),
-    "mis_ema_update": (c_i, [c_p, c_p, c_ll, c_f, c_p]),
-    "mis_sgd_ema_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
-    "mis_teacher_noise": (c_i, [c_p, c_p, c_ll, c_f, c_f, c_u, c_p, c_p]),
-    "mis_step_init": (c_i, [c_p, c_ull, c_ll, c_d, c_d, c_d, c_d, c_d, c_ll, c_ll, c_i, c_p]),
-    "mis_step_advance": (c_i, [c_p, c_d, c_d, c_d, c_d, c_d, c_ll, c_ll, c_i, c_p]),
-    "mis_argmax_channels": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_ll, c_p]),
-    "mis_conv_k2s2_eligible": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv_k2s2_down": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_conv_k2s2_up": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_conv_k2s2_wgrad_eligible": (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    "mis_conv_k2s2_wgrad_workspace_bytes": (c_ll, [c_i, c_i]),
-    "mis_conv_k2s2_wgrad": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_debug_poison_lds": (c_i, [c_p, c_p]),
-    "mis_debug_spin": (c_i, [c_i, c_i, c_i, c_p, c_p]),
-    "mis_debug_wgrad_prof": (c_i, [c_p]),
-    "mis_space_to_depth2": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_space_to_depth2d": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_add": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_ll, c_p]),
-    # token-major (SwinUnet) kernels
-    "mis_gemm_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i]),
-    "mis_gemm_dw_workspace_bytes": (c_ll, [c_i, c_i, c_i]),
-    "mis_gemm_dw": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_gemm_dw_parts": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_p]),
-    "mis_gemm_set_split_precision": (c_i, [c_i]),
-    "mis_gemm_nt_kernel_name": (c_i, [c_i, c_i, c_i, c_i, ctypes.c_char_p, c_i]),
-    "mis_gemm_tn_kernel_name": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, ctypes.c_char_p, c_i]),
-    "mis_gemm_expand_ln_head": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p,
-                                      c_p, c_ll, c_p]),
-    "mis_gemm_split_bytes": (c_ll, [c_i, c_i]),
-    "mis_gemm_split_b": (c_i, [c_p, c_ll, c_i, c_i, c_p, c_p]),
-    "mis_gemm_split_b_layout": (c_i, [c_p, c_ll, c_i, c_i, c_p, c_i, c_p]),
-    "mis_gemm_split_job_layout": (c_ll, [c_p, c_p, c_ll, c_i, c_i, c_p, c_ll, c_i]),
-    "mis_gemm_nt_split_natural": (c_i, [c_i, c_i, c_i]),
-    "mis_gemm_nt_split_layout": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_ll, c_p, c_ll,
-                                       c_i, c_i, c_i, c_i, c_p, c_ll, c_i, c_p]),
-    "mis_gemm_nt_split_layout_kernel_name": (c_i, [c_i, c_i, c_i, c_i, c_i, ctypes.c_char_p, c_i]),
-    "mis_gemm_expand_ln_head_split": (c_i, [c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p,
-                                            c_ll, c_p]),
-    "mis_gemm_nt_residual_ln": (c_i, [c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_f, c_p, c_ll,
-                                      c_p, c_p, c_p]),
-    "mis_gemm_split_job_bytes": (c_ll, []),
-    "mis_gemm_split_job": (c_ll, [c_p, c_p, c_ll, c_i, c_i, c_p, c_ll]),
-    "mis_gemm_split_batch": (c_i, [c_p, c_i, c_ll, c_p]),
-    "mis_gemm_nt_split_workspace_bytes": (c_ll, [c_i, c_i, c_i]),
-    "mis_gemm_nt_split": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_ll, c_p, c_ll,
-                                c_i, c_i, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_gemm_nt_split_kernel_name": (c_i, [c_i, c_i, c_i, c_i, ctypes.c_char_p, c_i]),
-    "mis_gemm_expand": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_gemm": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_gemm_ex": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p,
-                          c_ll, c_p]),
-    "mis_droppath_table": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
-    "mis_transpose": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_p]),
-    "mis_win3d_gather": (c_i, [c_p, c_p] + [c_i] * 12 + [c_p]),
-    "mis_win3d_windows": (c_ll, [c_i] * 7),
-    "mis_merge3d": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_win3d_attn_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "mis_win3d_attn_workspace_bytes": (c_ll, [c_i, c_i, c_i]),
-    "mis_win3d_attn_bwd": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p,
-                                 c_ll, c_p]),
-    "mis_transpose_job_bytes": (c_ll, []),
-    "mis_transpose_job": (c_ll, [c_p, c_p, c_p, c_i, c_i, c_ll]),
-    "mis_transpose_batch": (c_i, [c_p, c_i, c_ll, c_p]),
-    "mis_layernorm_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_p, c_ll, c_i, c_f, c_p]),
-    "mis_colreduce_workspace_bytes": (c_ll, [c_ll, c_i]),
-    "mis_layernorm_bwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_p,
-                                c_ll, c_p]),
-    "mis_layernorm_bwd_parts": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_layernorm_bwd_final": (c_i, [c_p, c_ll, c_ll, c_i, c_p, c_p, c_i, c_p]),
-    "mis_colsum_job_bytes": (c_ll, []),
-    "mis_colreduce_slabs": (c_ll, [c_ll]),
-    "mis_colsum_job": (c_ll, [c_p, c_p, c_ll, c_ll, c_i, c_i, c_p, c_p, c_i, c_ll]),
-    "mis_colsum_batch": (c_i, [c_p, c_i, c_ll, c_p]),
-    "mis_layernorm_bwd_residual_parts": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_i, c_p, c_ll, c_p, c_ll, c_p, c_p,
-                                               c_p, c_ll, c_i, c_p, c_ll, c_p]),
-    "mis_colsum": (c_i, [c_p, c_ll, c_ll, c_i, c_p, c_i, c_p, c_ll, c_p]),
-    "mis_gelu": (c_i, [c_p, c_p, c_p, c_ll, c_i, c_p]),
-    "mis_residual_droppath": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_ll, c_i, c_ll, c_f, c_u, c_p, c_p,
-                                    c_i, c_p]),
-    "mis_token_rearrange": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_patch_im2col": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "mis_ln_head_fwd": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_i, c_ll, c_i, c_i, c_f, c_p]),
-    "mis_ln_head_workspace_bytes": (c_ll, [c_ll, c_i, c_i]),
-    "mis_ln_head_bwd": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_p, c_ll, c_i, c_p, c_p, c_p, c_i, c_i, c_ll,
-                              c_i, c_i, c_p, c_ll, c_p]),
-    "mis_ln_head_bwd_unshuffle": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_p, c_ll, c_i, c_p, c_p, c_p, c_i, c_i, c_i,
-                                        c_i, c_i, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_head_fwd": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_i, c_ll, c_i, c_i, c_p]),
-    "mis_head_workspace_bytes": (c_ll, [c_i, c_i]),
-    "mis_head_bwd": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_ll, c_i, c_i, c_p, c_ll, c_p]),
-    "mis_window_attention_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
-    "mis_window_attention_workspace_bytes": (c_ll, [c_i, c_i, c_i, c_i]),
-    "mis_window_attention_bwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f,
-                                       c_p, c_ll, c_p]),
-    "mis_patch_im2col_c": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_window_attention_fwd_ws": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
-    "mis_window_attention_workspace_bytes_ws": (c_ll, [c_i, c_i, c_i, c_i, c_i]),
-    "mis_window_attention_bwd_ws": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f,
-                                          c_i, c_p, c_ll, c_p]),
-    "mis_window_attention_bwd_parts_ws": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p,
-                                                c_ll, c_p]),
-    "mis_window_attention_dtable_ws": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_window_attention_table_partials": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
-    "mis_full_attention_fwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_f, c_p]),
-    "mis_full_attention_workspace_bytes": (c_ll, [c_i, c_i, c_i]),
-    "mis_full_attention_bwd": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_i, c_i, c_i, c_f, c_p, c_ll, c_p]),
-    "mis_patch3d_im2col": (c_i, [c_p, c_ll, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "mis_add_rowcycle": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_ll, c_i, c_i, c_p]),
-    "mis_sum_rowcycle": (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_i, c_p]),
-    "mis_augment2d": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
-    "mis_crop_rotflip3d": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
-    # validation metrics
-    "mis_surface_metrics_workspace_bytes": (c_ll, [c_i, c_i, c_i]),
-    "mis_surface_metrics": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_ll, c_p]),
-    "mis_sq_edt": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_ll, c_p]),
-}
 
-STEP_STATE_BYTES = 40  # sizeof(MisStepState)
-AUG2D_BYTES = 88       # sizeof(MisAug2D)
-CROP3D_BYTES = 48      # sizeof(MisCrop3D)
+def _ctype(text, decl):
+    """The ctypes type of one return or parameter type as the header spells it; anything else is refused, never guessed."""
+    t = " ".join(text.replace("*", " * ").split())
+    if t in _SCALARS:
+        return _SCALARS[t]
+    if t == "char *":                          # the *_kernel_name out-buffers
+        return ctypes.c_char_p
+    m = re.fullmatch(r"(?:const )?([\w ]+) \*", t)
+    if t == "mis_stream_t" or (m and m.group(1) in _POINTEES):
+        return ctypes.c_void_p
+    raise ValueError(f"mis_hip.h: {decl}: type {text.strip()!r} has no ctypes mapping")
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) of every ``ret mis_name(type name, ...);`` in the text of a C header.  It understands what
+    include/mis_hip.h holds and nothing more: comments, preprocessor lines, the extern "C" braces and typedefs are dropped,
+    every statement left must be such a declaration with named parameters of the types _ctype knows."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|typedef\s+struct\s+\w+\s*\{[^{}]*\}\s*\w+\s*;|typedef\s[^;{}]*;', " ", text)
+    *stmts, rest = text.split(";")
+    if rest.strip() not in ("", "}"):
+        raise ValueError(f"mis_hip.h: text after the last declaration: {rest.strip()!r}")
+    protos = {}
+    for stmt in stmts:
+        stmt = " ".join(stmt.split())
+        m = re.fullmatch(r"([\w ]+?) ?\b(mis_\w+) ?\(([^()]*)\)", stmt)
+        if not m or m.group(2) in protos:
+            raise ValueError(f"mis_hip.h: not a (single) function declaration: {stmt!r}")
+        ret, name, args = m.groups()
+        argtypes = []
+        for arg in ([] if args.strip() == "void" else args.split(",")):
+            p = re.fullmatch(r"(.*[\s*])(\w+)", arg.strip())       # type, parameter name
+            if not p or p.group(2) in ("int", "long", "float", "double", "unsigned", "char", "void", "const"):
+                raise ValueError(f"mis_hip.h: {name}: parameter {arg.strip()!r} is not `type name`")
+            argtypes.append(_ctype(p.group(1), name))
+        protos[name] = (_ctype(ret, name), argtypes)
+    return protos
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes prototypes are read from the C header of the checkout.")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+# name -> (restype, argtypes), read from include/mis_hip.h -- the same text the library's definitions are compiled against
+PROTOTYPES = _read_header()
+
+STEP_STATE_BYTES = 40  # sizeof(MisStepState): static_assert in csrc/common.h
+AUG2D_BYTES = 88       # sizeof(MisAug2D): static_assert in csrc/augment.hip
+CROP3D_BYTES = 48      # sizeof(MisCrop3D): static_assert in csrc/augment.hip
 SURFACE_RECORD_WORDS = 12   # 8-byte fields of mis_surface_metrics' result record
 
 

@@ -22,23 +22,38 @@
 #ifndef MIS_HIP_H
 #define MIS_HIP_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
 
 #define MIS_OK 0
-#define MIS_ERR_ARG (-1)
-#define MIS_ERR_UNSUPPORTED (-2)
-#define MIS_ERR_LAUNCH (-3)
-#define MIS_ERR_WORKSPACE (-4)
+#define MIS_ERR_ARG (-1)         /* bad pointer / size / stride */
+#define MIS_ERR_UNSUPPORTED (-2) /* shape the kernel family does not cover */
+#define MIS_ERR_LAUNCH (-3)      /* hipGetLastError() after launch */
+#define MIS_ERR_WORKSPACE (-4)   /* caller workspace too small */
 
+/* The library's own sources (csrc/common.h defines MIS_HIP_BUILD after <hip/hip_runtime.h>) compile their definitions
+ * against these declarations with the HIP type; for every caller a stream is an opaque pointer.  Same ABI. */
+#ifdef MIS_HIP_BUILD
+typedef hipStream_t mis_stream_t;
+#else
 typedef void* mis_stream_t; /* hipStream_t */
+#endif
 
-/* Device-resident per-step state (40 bytes): Philox seed/offset, iter_num and the schedule values
- * of the current step.  Lets one captured hipGraph replay with fresh dropout masks, learning rate,
- * EMA alpha and consistency weight.  Layout: u64 seed, u64 offset, i64 iter_num, f32 lr,
- * f32 ema_alpha, f32 cons_weight, f32 cons_gate. */
-typedef struct MisStepState MisStepState;
+/* Device-resident per-step state (40 bytes): lets one captured hipGraph replay with fresh dropout masks, learning
+ * rate, EMA alpha and consistency weight without re-capture or a per-step host->device copy.  Written by
+ * mis_step_init, advanced by mis_step_advance. */
+typedef struct MisStepState {
+    uint64_t seed;     /* Philox key */
+    uint64_t offset;   /* RNG offset, +1 per step */
+    int64_t iter_num;  /* reference's iter_num (train_mean_teacher_2D.py:198) */
+    float lr;          /* SGD learning rate of this step */
+    float ema_alpha;   /* EMA decay of this step */
+    float cons_weight; /* consistency weight of this step (0 while gated off) */
+    float cons_gate;   /* 1 if the consistency term is live this step, else 0 */
+} MisStepState;
 
 int mis_abi_version(void);
 
@@ -524,14 +539,14 @@ long long mis_gemm_workspace_bytes(int M, int N, int K, int trans);
  * aligned operands; workspace >= mis_gemm_dw_workspace_bytes(M, N, K) (0: none needed). */
 long long mis_gemm_dw_workspace_bytes(int M, int N, int K);
 int mis_gemm_dw(const float* dy, long long lddy, const float* x, long long ldx, float* dW, long long lddw, float* db, int M,
-                int N, int K, int accumulate, float* workspace, long long workspace_bytes, hipStream_t stream);
+                int N, int K, int accumulate, float* workspace, long long workspace_bytes, mis_stream_t stream);
 /* mis_gemm_dw without its finishing launch (db may be NULL: the weight gradient of a bias-free Linear, :361-362, :390).
  * *slices > 0: the contraction was split and `workspace` -- the caller's own until the sums have run -- holds *slices partial
  * matrices [M][N] followed by *slices partial rows [M] of the bias gradient; dW / db are untouched and `accumulate` is the sum's
  * business (two mis_colsum_job records: stride M*N -> dW, stride M -> db).  *slices == 0: dW / db are complete. */
 int mis_gemm_dw_parts(const float* dy, long long lddy, const float* x, long long ldx, float* dW, long long lddw, float* db,
                       int M, int N, int K, int accumulate, float* workspace, long long workspace_bytes, int* slices,
-                      hipStream_t stream);
+                      mis_stream_t stream);
 /* the NT kernel instantiation mis_gemm / mis_gemm_ex run this shape with (aligned operands), as a profiler names it */
 int mis_gemm_nt_kernel_name(int M, int N, int K, int epilogue, char* name, int name_len);
 /* Arithmetic of the nn.Linear GEMMs (mis_gemm / mis_gemm_ex / mis_gemm_dw / mis_gemm_expand): bit 0 forward + dX, bit 1 dW as
@@ -558,7 +573,7 @@ int mis_gemm_expand_ln_head(const float* x, long long lda, const float* W, long 
  * accumulators are token rows of the shuffled tensor, LayerNorm and the head run in registers. */
 int mis_gemm_expand_ln_head_split(const float* x, long long lda, const void* B3, float* out, int B, int H, int W, int K, int P,
                                   int c, const float* gamma, const float* beta, const float* head_w, int NC, float eps,
-                                  float* mean, float* rstd, float* logits, long long logits_bs, hipStream_t stream);
+                                  float* mean, float* rstd, float* logits, long long logits_bs, mis_stream_t stream);
 /* The NT form with a pre-split B operand.  The bf16x3 kernels cut every fp32 operand into three bf16 pieces; for B = an
  * nn.Linear weight (forward: F.linear(x, W), swin_transformer_unet_skip_expand_decoder_sys.py:14,16,107,109; data gradient:
  * dy . W, i.e. B = W^T) that cut is the same for every tile of the launch and every launch of the step, so it is done once:
@@ -590,12 +605,12 @@ int mis_gemm_nt_split(const float* A, long long lda, const void* B3, float* C, l
  * must be cut with mis_gemm_split_b_layout / mis_gemm_split_job_layout (natural = 1); layout / natural = 0 are the entry points
  * above.  Same split products, same k-block order: results agree with the staged kernels to fp32 rounding. */
 int mis_gemm_nt_split_natural(int M, int N, int K);
-int mis_gemm_split_b_layout(const float* B, long long ldb, int N, int K, void* B3, int natural, hipStream_t stream);
+int mis_gemm_split_b_layout(const float* B, long long ldb, int N, int K, void* B3, int natural, mis_stream_t stream);
 long long mis_gemm_split_job_layout(void* job, const float* B, long long ldb, int N, int K, void* B3, long long first, int natural);
 int mis_gemm_nt_split_layout(const float* A, long long lda, const void* B3, float* C, long long ldc, const float* bias, int M,
                              int N, int K, int accumulate, int epilogue, const float* E1, long long lde1, float* C2,
                              long long ldc2, const float* rowscale, long long rows_per_scale, int ex_H, int ex_W, int ex_P,
-                             int ex_c, float* workspace, long long workspace_bytes, int layout, hipStream_t stream);
+                             int ex_c, float* workspace, long long workspace_bytes, int layout, mis_stream_t stream);
 int mis_gemm_nt_split_layout_kernel_name(int M, int N, int K, int epilogue, int layout, char* name, int name_len);
 /* proj / fc2 of a 96-channel Swin block with everything up to the next LayerNorm in the register-A kernels' epilogue (planes in
  * the natural order): X = E1 + rowscale[m / rows_per_scale] * (A . B^T + bias) (the residual stream, :276 / :281) and
@@ -605,7 +620,7 @@ int mis_gemm_nt_split_layout_kernel_name(int M, int N, int K, int epilogue, int 
 int mis_gemm_nt_residual_ln(const float* A, long long lda, const void* B3, const float* bias, int M, int N, int K,
                             const float* E1, long long lde1, const float* rowscale, long long rows_per_scale, float* X,
                             long long ldx, const float* gamma, const float* beta, float eps, float* Y, long long ldy,
-                            float* mean, float* rstd, hipStream_t stream);
+                            float* mean, float* rstd, mis_stream_t stream);
 int mis_gemm_nt_split_kernel_name(int M, int N, int K, int epilogue, char* name, int name_len);
 /* nn.Linear of PatchExpand / FinalPatchExpand_X4 fused with their pixel shuffle
  * 'b h w (p1 p2 c) -> b (h p1) (w p2) c' (swin_transformer_unet_skip_expand_decoder_sys.py:373-380, :401-408):

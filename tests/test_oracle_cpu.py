@@ -267,15 +267,35 @@ def test_dice_loss_edge_cases():
 
 
 def test_c_abi_library_exports_every_declared_symbol():
-    """include/mis_hip.h <-> libmis_hip.so <-> ctypes prototypes stay in sync (no compute calls here)."""
+    """include/mis_hip.h <-> libmis_hip.so <-> ctypes prototypes: the library is compiled against the header and lib.PROTOTYPES
+    is parsed from it; here the parse is held to hand-written expectations that cover every mapped type (no compute calls)."""
+    import ctypes
     from mis_hip import lib
     L = lib.load()
     header = open(os.path.join(ROOT, "include", "mis_hip.h")).read()
-    declared = set(re.findall(r"\b(mis_[a-z0-9_]+)\s*\(", header))
+    # names come from declarations only: the same regex as before, but on the text without its comments
+    declared = set(re.findall(r"\b(mis_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", header, flags=re.S)))
     assert declared, "no declarations parsed from include/mis_hip.h"
     assert declared == set(lib.PROTOTYPES), declared ^ set(lib.PROTOTYPES)
+    assert len(declared) == 187
     for name in declared:
         assert hasattr(L, name), name
+    P, CH, I, LL, ULL = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong
+    U, F, D = ctypes.c_uint, ctypes.c_float, ctypes.c_double
+    expected = {
+        "mis_abi_version": (I, []),                                                  # (void)
+        "mis_step_init": (I, [P, ULL, LL, D, D, D, D, D, LL, LL, I, P]),            # unsigned long long, double, long long
+        "mis_uamt_tail": (I, [P, LL, P, LL, P, LL, P, I, I, I, I, LL, F, P, LL, D, F, P, P, LL, P, LL, P]),   # double by float
+        "mis_beta_sample": (I, [P, I, D, U, P, P]),                                  # unsigned, const MisStepState*
+        "mis_conv_fwd_kernel_name": (I, [I] * 9 + [CH, I]),                          # char*
+        "mis_surface_metrics": (I, [P, P, I, I, I, I, I, P, P, LL, P]),              # const unsigned char*
+        "mis_debug_wgrad_prof": (I, [P]),                                            # unsigned long long*
+        "mis_win3d_gather": (I, [P, P] + [I] * 12 + [P]),                            # twelve ints in a row
+        "mis_conv_packed_floats": (LL, [I, I, I, I]),                                # long long result
+    }
+    for name, (res, args) in expected.items():
+        assert lib.PROTOTYPES[name] == (res, args), (name, lib.PROTOTYPES[name])
+        assert getattr(L, name).restype is res and list(getattr(L, name).argtypes or []) == args, name
     assert L.mis_abi_version() == 1
     assert L.mis_conv_cin_pad(1) == 4 and L.mis_conv_cout_pad(2) == 16
     assert L.mis_conv_packed_floats(16, 48, 27, 0) == 48 * 27 * 16
@@ -285,6 +305,36 @@ def test_c_abi_library_exports_every_declared_symbol():
     assert L.mis_conv_wgrad_workspace_bytes(8, 48, 16, 96, 96, 96, 3, 3, 3) > 0
     # argument validation happens before any launch
     assert L.mis_conv_fwd(None, 0, None, None, None, 0, 1, 1, 1, 1, 1, 1, 3, 3, 3, None) == -1
+
+
+def test_c_abi_header_compiles_alone():
+    """include/mis_hip.h is self-contained C and C++: the host compiler takes it with no HIP header in sight."""
+    import shutil
+    import subprocess
+    if shutil.which("cc") is None:
+        pytest.skip("no host C compiler (cc) on this machine")
+    path = os.path.join(ROOT, "include", "mis_hip.h")
+    for cc, lang in (("cc", "c"), (shutil.which("c++") and "c++" or "cc", "c++")):
+        r = subprocess.run([cc, "-fsyntax-only", "-Wall", "-x", lang, path], capture_output=True, text=True)
+        assert r.returncode == 0 and not r.stderr, (lang, r.stderr)
+
+
+def test_c_abi_header_parser_refuses_what_it_does_not_know():
+    """lib.parse_header never guesses: an unknown type, a struct by value, a variadic or function-pointer parameter raise and
+    name the declaration; a declaration broken over lines around a comment with '(' and ';' in it parses."""
+    import ctypes
+    from mis_hip.lib import parse_header
+    ok = parse_header("#define X 1\ntypedef void* mis_stream_t;\ntypedef struct S { int a, b; } S;\n"
+                      "long long mis_three_lines(const float* x, /* batch stride (elements); may be 0 */\n"
+                      "        long long x_bs,\n        unsigned int n, mis_stream_t stream);\nint mis_none(void);\n")
+    assert ok == {"mis_three_lines": (ctypes.c_longlong, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_uint, ctypes.c_void_p]),
+                  "mis_none": (ctypes.c_int, [])}
+    for bad in ("int mis_bad_scalar(short n);", "int mis_bad_struct(MisAug2D rec, int n);", "int mis_bad_dots(int n, ...);",
+                "int mis_bad_callback(int (*cb)(int), int n);", "int mis_bad_unnamed(long long);",
+                "int mis_bad_pointee(const MisAug2D* rec);", "size_t mis_bad_result(int n);",
+                "int mis_bad_twice(int n); int mis_bad_twice(int n);", "int mis_bad_field; int mis_fine(int n);"):
+        with pytest.raises(ValueError, match=r"mis_bad_\w+"):
+            parse_header(bad)
 
 
 def test_product_path_refuses_to_run_without_gpu():
