@@ -1,9 +1,12 @@
 """Static forward/backward executor for the convolutional segmentation nets on the hot path.
 
 Instead of recording a torch autograd graph per op, a network describes its layers once as a
-*plan*: a list of ops over pre-allocated activation buffers.  ``Plan.forward`` walks the list,
-``Plan.backward`` walks it in reverse; every op is one or two launches of the gfx950 kernels
-through the C-ABI (``mis_hip.ops``).  Consequences:
+*plan*: a list of ops over pre-allocated activation buffers.  ``PlanBase.forward`` walks the list,
+``PlanBase.backward`` walks it in reverse; every op is one or two launches of the gfx950 kernels
+through the C-ABI (``mis_hip.ops`` / ``mis_hip.tops``).  The walks, the buffer base ``Buf`` and the per-pass
+context ``Ctx`` are written once, here, for both kinds of plan: ``Plan`` (the volume ops of this module, and
+with them the token ops of the mixed UNETR / SwinUNETR) and ``swin_plan.SwinPlan`` (token ops only).
+Consequences:
 
 * no per-step allocation, so the whole training step can be captured in one hipGraph;
 * skip connections are channel-slices of the decoder's concat buffer, so ``torch.cat``
@@ -21,7 +24,8 @@ import torch
 import torch.nn as nn
 
 from . import lib as _lib
-from . import ops
+from . import ops, tops
+from .dist import param_progress
 
 _net_ids = itertools.count(1)
 
@@ -47,33 +51,22 @@ PROGRESS_SYNC_MAIN = os.environ.get("MIS_PROGRESS_SYNC_MAIN", "0") == "1"
 NORM_RES = os.environ.get("MIS_NORM_RES", "1") != "0"
 
 
-class Act:
-    """Activation buffer ``[N,C,D,H,W]`` (fp32), optionally a channel-slice of a wider buffer."""
+class Buf:
+    """What a volume buffer (``Act``) and a token buffer (``TAct``) share: ``t`` is the fp32 device tensor, optionally the
+    slice ``[:, c0:c0+C]`` of a wider buffer ``parent`` (a concatenation that never runs); ``g`` its gradient, allocated on first
+    use; ``written`` tells an op's backward whether to accumulate into ``g`` or to overwrite it."""
 
-    def __init__(self, shape=None, parent=None, c0=0, C=None, tensor=None):
+    def __init__(self, parent=None, c0=0):
         self.parent, self.c0 = parent, c0
         self._written = False
         self.g = None
-        if tensor is not None:
-            self.t = tensor
-        elif parent is not None:
-            self.t = parent.t[:, c0:c0 + C]
-        else:
-            self.t = torch.empty(shape, dtype=torch.float32, device="cuda")
-
-    @property
-    def shape(self):
-        return tuple(self.t.shape)
-
-    def slice(self, c0, C):
-        return Act(parent=self, c0=c0, C=C)
 
     def grad(self):
         if self.g is None:
             if self.parent is not None:
                 self.g = self.parent.grad()[:, self.c0:self.c0 + self.t.shape[1]]
             else:
-                self.g = torch.empty(self.shape, dtype=torch.float32, device="cuda")
+                self.g = torch.empty(tuple(self.t.shape), dtype=torch.float32, device="cuda")
         return self.g
 
     def _root(self):
@@ -93,8 +86,55 @@ class Act:
         self._written = False
 
 
+class Act(Buf):
+    """Activation buffer ``[N,C,D,H,W]``, optionally a channel-slice of a wider buffer.  ``isinstance(v, Act)`` means a 5-D
+    volume buffer and nothing else (Plan._fuse_head / _fuse_dgrad_norm count an activation's readers with it)."""
+
+    def __init__(self, shape=None, parent=None, c0=0, C=None, tensor=None):
+        super().__init__(parent, c0)
+        if tensor is not None:
+            self.t = tensor
+        elif parent is not None:
+            self.t = parent.t[:, c0:c0 + C]
+        else:
+            self.t = torch.empty(shape, dtype=torch.float32, device="cuda")
+
+    @property
+    def shape(self):
+        return tuple(self.t.shape)
+
+    def slice(self, c0, C):
+        return Act(parent=self, c0=c0, C=C)
+
+
+class TAct(Buf):
+    """Token activation ``[rows, C]``, optionally a column slice of a wider buffer (the ops over it: mis_hip.swin_plan)."""
+
+    def __init__(self, rows=None, C=None, parent=None, c0=0):
+        super().__init__(parent, c0)
+        if parent is not None:
+            self.t = parent.t[:, c0:c0 + C]
+        else:
+            self.t = torch.empty((rows, C), dtype=torch.float32, device="cuda")
+
+    @property
+    def rows(self):
+        return self.t.shape[0]
+
+    @property
+    def C(self):
+        return self.t.shape[1]
+
+    def cols(self, c0, C):
+        return TAct(parent=self, c0=c0, C=C)
+
+
 class Ctx:
-    """Per-call execution context."""
+    """Per-call execution context: what the caller fixes for a pass, then what the plan sets for it.  Every field is declared
+    here with its "off" value (an op run on a bare ``Ctx`` takes its plain one-stream form); a field that is not is an error."""
+
+    __slots__ = ("training", "rng_stream", "dropout", "state", "drop_masks", "no_backward", "b3_fwd", "b3_bwd",
+                 "wgrad_stream", "deferred", "finals", "finals_bytes", "final_batches")
 
     def __init__(self, training, state=None, drop_masks=None, dropout=True, rng_stream=0):
         self.training = training
@@ -102,6 +142,13 @@ class Ctx:
         self.dropout = dropout          # False: every dropout p := 0 (fixture mode)
         self.state = state              # device MisStepState (needed for Philox dropout)
         self.drop_masks = drop_masks    # optional {salt_index: mask tensor} (parity tests)
+        self.no_backward = False        # True: nobody differentiates this pass (HipNet.forward_raw)
+        self.b3_fwd = self.b3_bwd = False       # True: the Linears' pre-split W / W^T are current (split_linear_weights)
+        self.wgrad_stream = None        # the backward's side stream for weight gradients (PlanBase.backward)
+        self.deferred = None            # finishing launches queued for the side stream (defer)
+        self.finals = None              # ColsumJob records queued for the next batch of finishing sums (defer_final) ...
+        self.finals_bytes = 0           # ... and the bytes of partials they read
+        self.final_batches = None       # the plan's cache of those batches' device job tables (begin_finals)
 
 
 class ConvOp:
@@ -139,12 +186,11 @@ class ConvOp:
             return               # the NormActOp's backward writes w.grad / b.grad / its own input gradient
         if self.norm_bwd is not None:      # need_dx False, bias gradient exactly 0: the weight gradient is all there is
             n = self.norm_bwd
-            ops.conv_wgrad_cin1_norm(self.x.t, n.y.grad(), self.y.t, n.per_sample, n.mean, n.rstd,
-                                     None if n.gamma is None else n.gamma.data, None if n.beta is None else n.beta.data,
-                                     n.sums, n.slope, self.w.grad)
+            ops.conv_wgrad_cin1_norm(self.x.t, n.y.grad(), self.y.t, n.per_sample, n.mean, n.rstd, *n._affine(), n.sums,
+                                     n.slope, self.w.grad)
             return
         dy = self.y.grad()
-        side = getattr(ctx, "wgrad_stream", None) if self.need_dx else None
+        side = ctx.wgrad_stream if self.need_dx else None
         if side is not None:
             _lib.wait_stream(side, torch.cuda.current_stream())     # dy is final
             with torch.cuda.stream(side):
@@ -197,8 +243,8 @@ class NormActOp:
         self.mean = torch.zeros(G, dtype=torch.float32, device="cuda")     # no_norm: stays (0, 1)
         self.rstd = torch.ones(G, dtype=torch.float32, device="cuda")
         self._p = 0.0
-        self._mask = None
-        self.pool = None         # MaxPoolOp fed by this op's output whose backward runs inside this op's (Plan.maxpool)
+        self._mask = self._state = None     # this pass's mask override / device step state (fixed by fwd, read by bwd)
+        self.pool = None        # MaxPoolOp fed by this op's output whose backward runs inside this op's (Plan.maxpool)
         self.sums = None         # set: backward only reduces (into this [G, 2] buffer); the producing first-layer conv applies
         self.ext_part = None     # [N*C*tiles, 2] partial sums of the backward written by the consuming conv's data-gradient
         self.ext_tiles, self.ext_ready, self.ext_sums = 0, False, None     # launch (Plan._fuse_dgrad_norm)
@@ -206,6 +252,14 @@ class NormActOp:
         self.res_post = False    # True: added behind the activation instead (Plan.add's fusion of V-Net's x_up + skip)
         self.head = None         # 1x1x1 classifier ConvOp computed in this op's pass (Plan._fuse_head); head_w / head_b:
         self.head_w = self.head_b = None     # its parameters (their gradients are written by THIS op: dist.param_progress)
+
+    def _affine(self):
+        """(gamma.data, beta.data) for a launch, each None when the normalisation has no such parameter.  A method, not a
+        stored pair: dist.param_progress finds an op's parameters in ``vars(op)``, where gamma and beta stand once."""
+        return (None if self.gamma is None else self.gamma.data, None if self.beta is None else self.beta.data)
+
+    def _affine_grad(self):
+        return (None if self.gamma is None else self.gamma.grad, None if self.beta is None else self.beta.grad)
 
     def fwd(self, ctx):
         if self.no_norm:
@@ -232,39 +286,29 @@ class NormActOp:
         if self._p > 0 and self._mask is None and ctx.state is None:
             raise RuntimeError("dropout is active but no device step state was supplied (Ctx.state)")
         if self.res is not None:
-            ops.norm_res_act_fwd(self.x.t, self.res.t, self.y.t, self.per_sample, self.mean, self.rstd,
-                                 None if self.gamma is None else self.gamma.data,
-                                 None if self.beta is None else self.beta.data, self.slope, post=self.res_post)
+            ops.norm_res_act_fwd(self.x.t, self.res.t, self.y.t, self.per_sample, self.mean, self.rstd, *self._affine(),
+                                 self.slope, post=self.res_post)
             return
         if self.pool is not None and self.pool.fwd_fused:
             pl = self.pool
-            ops.norm_act_fwd_pool(self.x.t, self.y.t, pl.y.t, pl.idx, self.per_sample, self.mean, self.rstd,
-                                  None if self.gamma is None else self.gamma.data,
-                                  None if self.beta is None else self.beta.data, self.slope, self._p, self.salt,
-                                  self._state, self._mask, cg=self.cg)
+            ops.norm_act_fwd_pool(self.x.t, self.y.t, pl.y.t, pl.idx, self.per_sample, self.mean, self.rstd, *self._affine(),
+                                  self.slope, self._p, self.salt, self._state, self._mask, cg=self.cg)
             return
         if self.head is not None:
             h = self.head
-            ops.norm_head_fwd(self.x.t, h.y.t, self.per_sample, self.mean, self.rstd,
-                              None if self.gamma is None else self.gamma.data,
-                              None if self.beta is None else self.beta.data, self.slope,
+            ops.norm_head_fwd(self.x.t, h.y.t, self.per_sample, self.mean, self.rstd, *self._affine(), self.slope,
                               h.w.data.view(h.cout, h.cin), None if h.b is None else h.b.data, self._p, self.salt,
                               self._state, self._mask)
             return
-        ops.norm_act_fwd(self.x.t, self.y.t, self.per_sample, self.mean, self.rstd,
-                         None if self.gamma is None else self.gamma.data,
-                         None if self.beta is None else self.beta.data, self.slope, self._p, self.salt,
-                         self._state, self._mask, cg=self.cg)
+        ops.norm_act_fwd(self.x.t, self.y.t, self.per_sample, self.mean, self.rstd, *self._affine(), self.slope, self._p,
+                         self.salt, self._state, self._mask, cg=self.cg)
 
     def bwd(self, ctx):
         assert not self.x.written
         if self.res is not None:
             r = self.res
             ops.norm_res_act_bwd(self.x.t, r.t, self.y.grad(), self.x.grad(), r.grad(), r.written, self.per_sample,
-                                 self.mean, self.rstd, None if self.gamma is None else self.gamma.data,
-                                 None if self.beta is None else self.beta.data, self.slope,
-                                 None if self.gamma is None else self.gamma.grad,
-                                 None if self.beta is None else self.beta.grad, post=self.res_post)
+                                 self.mean, self.rstd, *self._affine(), self.slope, *self._affine_grad(), post=self.res_post)
             r.mark_written()
             self.x.mark_written()
             return
@@ -277,39 +321,27 @@ class NormActOp:
                 self.x.mark_written()
             return
         if self.sums is not None:
-            ops.norm_act_bwd_sums(self.x.t, self.y.grad(), self.per_sample, self.mean, self.rstd,
-                                  None if self.gamma is None else self.gamma.data,
-                                  None if self.beta is None else self.beta.data, self.slope, self.sums,
-                                  None if self.gamma is None else self.gamma.grad,
-                                  None if self.beta is None else self.beta.grad)
+            ops.norm_act_bwd_sums(self.x.t, self.y.grad(), self.per_sample, self.mean, self.rstd, *self._affine(), self.slope,
+                                  self.sums, *self._affine_grad())
             return
         if self.pool is not None:
             pl = self.pool
             ops.norm_act_bwd_pool(self.x.t, self.y.grad() if self.y.written else None, pl.y.grad(), pl.idx, self.x.grad(),
-                                  self.per_sample, self.mean, self.rstd,
-                                  None if self.gamma is None else self.gamma.data,
-                                  None if self.beta is None else self.beta.data, self.slope, self._p, self.salt,
-                                  self._state, self._mask, None if self.gamma is None else self.gamma.grad,
-                                  None if self.beta is None else self.beta.grad, cg=self.cg)
+                                  self.per_sample, self.mean, self.rstd, *self._affine(), self.slope, self._p, self.salt,
+                                  self._state, self._mask, *self._affine_grad(), cg=self.cg)
             self.x.mark_written()
             return
         if self.head is not None:
             h = self.head
-            ops.norm_head_bwd(self.x.t, h.y.grad(), self.x.grad(), self.per_sample, self.mean, self.rstd,
-                              None if self.gamma is None else self.gamma.data,
-                              None if self.beta is None else self.beta.data, self.slope,
-                              h.w.data.view(h.cout, h.cin), h.w.grad.view(h.cout, h.cin),
+            ops.norm_head_bwd(self.x.t, h.y.grad(), self.x.grad(), self.per_sample, self.mean, self.rstd, *self._affine(),
+                              self.slope, h.w.data.view(h.cout, h.cin), h.w.grad.view(h.cout, h.cin),
                               h.b.grad if (h.b is not None and h.bias_grad) else None, self._p, self.salt, self._state,
-                              self._mask, None if self.gamma is None else self.gamma.grad,
-                              None if self.beta is None else self.beta.grad)
+                              self._mask, *self._affine_grad())
             self.x.mark_written()
             return
-        ops.norm_act_bwd(self.x.t, self.y.grad(), self.x.grad(), self.per_sample, self.mean, self.rstd,
-                         None if self.gamma is None else self.gamma.data,
-                         None if self.beta is None else self.beta.data, self.slope, self._p, self.salt,
-                         self._state, self._mask,
-                         None if self.gamma is None else self.gamma.grad,
-                         None if self.beta is None else self.beta.grad, cg=self.cg, no_norm=self.no_norm)
+        ops.norm_act_bwd(self.x.t, self.y.grad(), self.x.grad(), self.per_sample, self.mean, self.rstd, *self._affine(),
+                         self.slope, self._p, self.salt, self._state, self._mask, *self._affine_grad(), cg=self.cg,
+                         no_norm=self.no_norm)
         self.x.mark_written()
 
 
@@ -377,7 +409,6 @@ class DownConvOp:
         self._xs_valid = True
         if ops.conv1x1_gemm_eligible(self._xs, self.y.t, self.cin8, self.cout):
             # few voxels, many channels (the 12^3 / 6^3 levels): a batched GEMM with the weights contraction-major
-            from . import tops
             if self._wT is None:
                 self._wT = torch.empty((self.cin8, self.cout), dtype=torch.float32, device="cuda")
             tops.transpose(self.w.data.view(self.cout, self.cin8), self._wT)
@@ -459,7 +490,6 @@ class UpConvOp:
         ops.space_to_depth2(self.y8, self.y.t, self.y.shape, False, bias=None if self.b is None else self.b.data)
 
     def bwd(self, ctx):
-        from . import tops
         if self.bias_grad and self.b is not None:
             ops.channel_sum(self.y.grad(), self.b.grad)
         dyf = self.y.grad()
@@ -515,7 +545,6 @@ class UpConv2dOp:
         ops.space_to_depth2d(self.y4, self.y.t, self.y.shape, False, bias=None if self.b is None else self.b.data)
 
     def bwd(self, ctx):
-        from . import tops
         dyf = self.y.grad()
         if self.bias_grad and self.b is not None:
             ops.channel_sum(dyf, self.b.grad)
@@ -550,24 +579,130 @@ class AddOp:
             t.mark_written()
 
 
-class Plan:
-    """Layer list + buffers of one network for one input geometry."""
+def _token_ops():
+    """The module of the token-major ops.  It imports this one at its top, so this module reaches it at call time, and here only
+    (PlanBase: LinearOp for the transpose batch, split_linear_weights, pair_ln_residual)."""
+    from . import swin_plan
+    return swin_plan
+
+
+class PlanBase:
+    """Op list + buffers of one network for one input geometry, and the two walks over them.  ``Plan`` (volume ops, and the
+    token ops of the mixed UNETR / SwinUNETR) and ``swin_plan.SwinPlan`` (token ops only) add their builders and override the
+    steps in front of a walk: ``_begin_forward`` and ``_begin_backward``."""
 
     def __init__(self, net, in_shape):
         self.net = net
         self.in_shape = tuple(in_shape)      # (N, C, D, H, W)
-        self._tbatch = None
-        self.ops = []
-        self.acts = []
-        self.inp = Act(tensor=torch.empty(0, device="cuda"))
-        self.acts.append(self.inp)
-        self._wgrad_stream = None
-        self._salt = itertools.count(0)
+        self.ops, self.acts = [], []
         self.out = None
-        self._packs = None
-        self._head_checked = False
         self.generation = 0      # forwards run on this plan (its buffers hold the activations of the LAST one)
         self._progress = None    # dist.param_progress(self.ops, net.flat_grad), built on the first overlapped backward
+        self._wgrad_stream = None
+        self._paired = False     # pair_ln_residual has run over the op list
+        self._tbatch = None      # tops.TransposeBatch of the Linears' W^T (False: none needs one), built on the first backward
+        self._split = [None, None]       # tops.SplitBatch of the Linears' W / of their W^T (split_linear_weights)
+        self._final_batches = {}         # tops.ColsumBatch by the identity of the jobs of a flush (run_finals)
+
+    # ---- builders of the token ops ----
+    def tok(self, rows, C):
+        a = TAct(rows, C)
+        self.acts.append(a)
+        return a
+
+    def push(self, op):
+        self.ops.append(op)
+        return op
+
+    # ---- execution ----
+    def _pair_token_ops(self):
+        if not self._paired:
+            _token_ops().pair_ln_residual(self.ops)
+            self._paired = True
+
+    def _transpose_weights(self):
+        """W^T of every Linear that needs a data gradient in ONE launch (the weights changed with the last SGD update; 136
+        launches of ~5 us per UNETR backward before)."""
+        if self._tbatch is None:
+            Linear, jobs = _token_ops().LinearOp, []
+            for op in self.ops:
+                if isinstance(op, Linear) and op.need_dx and op.w2.is_contiguous():
+                    op.wT = torch.empty((op.w2.shape[1], op.w2.shape[0]), dtype=torch.float32, device="cuda")
+                    op.wT_batched = True
+                    jobs.append((op.w2, op.wT))
+            self._tbatch = tops.TransposeBatch(jobs) if jobs else False
+        if self._tbatch:
+            self._tbatch.run()
+
+    def _split_weights(self, transposed):
+        if self._split[transposed] is False:        # no Linear in this plan
+            return False
+        return _token_ops().split_linear_weights(self, transposed)
+
+    def _begin_forward(self, x5):
+        """Bind the input; what else a subclass does once per forward in front of the walk."""
+        raise NotImplementedError
+
+    def _begin_backward(self):
+        """What a subclass does once per backward in front of the shared preparation."""
+
+    def forward(self, x5, ctx):
+        assert tuple(x5.shape) == self.in_shape, (tuple(x5.shape), self.in_shape)
+        self.generation += 1
+        self._begin_forward(x5)
+        ctx.b3_fwd = self._split_weights(False)
+        for op in self.ops:
+            op.fwd(ctx)
+        return self.out.t
+
+    def backward(self, dlogits5, ctx, on_progress=None):
+        """``on_progress(lo)``: called after every op with the start of the finished suffix of the flat gradient
+        buffer (data-parallel runs issue the finished gradient buckets while the backward continues, mis_hip.dist)."""
+        for a in self.acts:
+            a.reset()
+        if dlogits5 is not None:
+            self.out.g = dlogits5
+        self._begin_backward()
+        self._pair_token_ops()
+        self._transpose_weights()
+        ctx.b3_bwd = self._split_weights(True)
+        main = torch.cuda.current_stream()
+        side = None
+        if WGRAD_STREAM:
+            if self._wgrad_stream is None:
+                self._wgrad_stream = _lib.side_stream("wgrad")
+            side = self._wgrad_stream
+        ctx.wgrad_stream = side
+        ctx.deferred = [] if side is not None else None      # see defer(): finishing launches queued for the side stream
+        begin_finals(ctx, self)
+        if on_progress is None:
+            for op in reversed(self.ops):
+                op.bwd(ctx)
+        else:
+            if self._progress is None:
+                self._progress = param_progress(self.ops, self.net.flat_grad)
+            # a reported gradient range is complete on (main, side): what was queued is finished before the callback issues anything
+            report = progress_reporter(on_progress, main, side, before=lambda: flush_deferred(ctx))
+            for i in range(len(self.ops) - 1, -1, -1):
+                self.ops[i].bwd(ctx)
+                if i == 0 or self._progress[i] != self._progress[i - 1] or i == len(self.ops) - 1:
+                    report(self._progress[i])
+        flush_deferred(ctx)
+        ctx.deferred = ctx.finals = None
+        if side is not None:
+            _lib.wait_stream(main, side)          # every weight gradient is in the flat buffer before the optimizer reads it
+
+
+class Plan(PlanBase):
+    """The plan of the convolutional nets: volume ops over ``Act`` buffers, the first of them ``inp``."""
+
+    def __init__(self, net, in_shape):
+        super().__init__(net, in_shape)
+        self.inp = Act(tensor=torch.empty(0, device="cuda"))
+        self.acts.append(self.inp)
+        self._salt = itertools.count(0)
+        self._packs = None
+        self._head_checked = False
 
     # ---- builders used by the networks ----
     def new(self, C, spatial, N=None):
@@ -671,7 +806,7 @@ class Plan:
         self.ops.append(UpsampleOp(x, y, align_corners))
         return y
 
-    # ---- execution ----
+    # ---- what this plan does in front of a walk ----
     def _pack(self, mode):
         """Re-layout the weights of every ConvOp for the MFMA kernels in ONE launch (mode 0 before the forward,
         mode 1 = flipped/transposed filters before the backward); weights change with every SGD update."""
@@ -694,29 +829,6 @@ class Plan:
             self._packs = (ops.PackBatch(fj) if fj else None, ops.PackBatch(bj) if bj else None)
         if self._packs[mode] is not None:
             self._packs[mode].run()
-
-    def _transpose_linear_weights(self):
-        """Mixed plans (UNETR, SwinUNETR): W^T of every token-major Linear that needs a data gradient in ONE launch (as
-        SwinPlan.transpose_weights; 136 launches of ~5 us per UNETR backward before)."""
-        if self._tbatch is None:
-            from . import tops
-            from .swin_plan import LinearOp
-            jobs = []
-            for op in self.ops:
-                if isinstance(op, LinearOp) and op.need_dx and op.w2.is_contiguous():
-                    op.wT = torch.empty((op.w2.shape[1], op.w2.shape[0]), dtype=torch.float32, device="cuda")
-                    op.wT_batched = True
-                    jobs.append((op.w2, op.wT))
-            self._tbatch = tops.TransposeBatch(jobs) if jobs else False
-        if self._tbatch:
-            self._tbatch.run()
-
-    def _split_linear_weights(self, transposed):
-        """Mixed plans: the token-major Linears' weights as pre-split GEMM operands (swin_plan.split_linear_weights)."""
-        if self._tbatch is False:       # no Linear in this plan
-            return False
-        from .swin_plan import split_linear_weights
-        return split_linear_weights(self, self.ops, transposed)
 
     def _fuse_dgrad_norm(self):
         """conv_a -> InstanceNorm -> ReLU -> conv_b (reference UnetConv3, utils.py:99-123): when the activation between
@@ -775,62 +887,18 @@ class Plan:
         norm.head, norm.head_w, norm.head_b = conv, conv.w, conv.b
         conv.fused_into = norm
 
-    def forward(self, x5, ctx):
-        assert tuple(x5.shape) == self.in_shape, (tuple(x5.shape), self.in_shape)
+    def _begin_forward(self, x5):
         if not self._head_checked:
             self._fuse_head()
             self._fuse_dgrad_norm()
-        self.generation += 1
         self.inp.t = x5
         self._pack(0)
-        ctx.b3_fwd = self._split_linear_weights(False)
-        for op in self.ops:
-            op.fwd(ctx)
-        return self.out.t
+        # NOT _pair_token_ops(): the token ops of a mixed plan (UNETR, SwinUNETR) are paired by its first backward, so a
+        # forward before that -- every forward of a network that is never differentiated -- runs its LayerNorms on their own
+        # ("open")
 
-    def backward(self, dlogits5, ctx, on_progress=None):
-        """``on_progress(lo)``: called after every op with the start of the finished suffix of the flat gradient
-        buffer (data-parallel runs issue the finished gradient buckets while the backward continues, mis_hip.dist)."""
-        for a in self.acts:
-            a.reset()
-        if dlogits5 is not None:
-            self.out.g = dlogits5
+    def _begin_backward(self):
         self._pack(1)
-        if self._tbatch is None:        # first backward of a mixed plan (UNETR, SwinUNETR): pair its token ops
-            from .swin_plan import pair_ln_residual
-            pair_ln_residual(self.ops)
-        self._transpose_linear_weights()
-        ctx.b3_bwd = self._split_linear_weights(True)
-        main = torch.cuda.current_stream()
-        side = None
-        if WGRAD_STREAM:
-            if self._wgrad_stream is None:
-                self._wgrad_stream = _lib.side_stream("wgrad")
-            side = self._wgrad_stream
-        ctx.wgrad_stream = side
-        ctx.deferred = [] if side is not None else None      # see defer(): finishing launches queued for the side stream
-        begin_finals(ctx, self)
-        if on_progress is None:
-            for op in reversed(self.ops):
-                op.bwd(ctx)
-            flush_deferred(ctx)
-            ctx.deferred = ctx.finals = None
-            if side is not None:
-                _lib.wait_stream(main, side)      # every weight gradient is in the flat buffer before the optimizer reads it
-            return
-        if self._progress is None:
-            from .dist import param_progress
-            self._progress = param_progress(self.ops, self.net.flat_grad)
-        # a reported gradient range is complete on (main, side): what was queued is finished before the callback issues anything
-        report = progress_reporter(on_progress, main, side, before=lambda: flush_deferred(ctx))
-        for i in range(len(self.ops) - 1, -1, -1):
-            self.ops[i].bwd(ctx)
-            if i == 0 or self._progress[i] != self._progress[i - 1] or i == len(self.ops) - 1:
-                report(self._progress[i])
-        flush_deferred(ctx)
-        ctx.deferred = ctx.finals = None
-        if side is not None:
-            _lib.wait_stream(main, side)          # every weight gradient is in the flat buffer before the optimizer reads it
 
     def drop_sites(self):
         """Site ids (keys of ``net.drop_masks``) of the active dropout layers, in forward order."""
@@ -849,7 +917,7 @@ DEFER = os.environ.get("MIS_DEFER_FINALS", "1") != "0"
 
 def defer(ctx, fn):
     """Queue ``fn`` for the side stream (False: there is none in this pass and the caller runs the one-stream form)."""
-    if not DEFER or getattr(ctx, "wgrad_stream", None) is None or getattr(ctx, "deferred", None) is None:
+    if not DEFER or ctx.wgrad_stream is None or ctx.deferred is None:
         return False
     ctx.deferred.append(fn)
     return True
@@ -864,20 +932,18 @@ BATCH_FINALS = os.environ.get("MIS_BATCH_FINALS", "1") != "0"
 FINALS_FLUSH_BYTES = int(os.environ.get("MIS_FINALS_FLUSH_MB", "32")) << 20
 
 
-def begin_finals(ctx, holder):
+def begin_finals(ctx, plan):
     """Start a backward pass: ``ctx.finals`` collects ColsumJob records (None: batching is off -- no side stream, or switched
-    off); the device job tables are cached on ``holder`` (the plan) by the identity of the jobs of a flush."""
-    on = BATCH_FINALS and DEFER and getattr(ctx, "wgrad_stream", None) is not None
+    off); the device job tables are cached on the plan by the identity of the jobs of a flush."""
+    on = BATCH_FINALS and DEFER and ctx.wgrad_stream is not None
     ctx.finals = [] if on else None
     ctx.finals_bytes = 0
-    if on and not hasattr(holder, "_final_batches"):
-        holder._final_batches = {}
-    ctx.final_batches = getattr(holder, "_final_batches", None)
+    ctx.final_batches = plan._final_batches
 
 
 def defer_final(ctx, *jobs):
     """Queue finishing sums for the next batch (False: batching is off and the caller launches its own finishing kernel)."""
-    if getattr(ctx, "finals", None) is None:
+    if ctx.finals is None:
         return False
     ctx.finals.extend(jobs)
     ctx.finals_bytes += sum(j.bytes for j in jobs)
@@ -886,9 +952,8 @@ def defer_final(ctx, *jobs):
 
 def run_finals(ctx):
     """Called with the side stream current and ordered behind the producers of every queued partial."""
-    pend = getattr(ctx, "finals", None)
+    pend = ctx.finals
     if pend:
-        from . import tops
         key = tuple(id(j) for j in pend)
         batch = ctx.final_batches.get(key)
         if batch is None:
@@ -900,18 +965,18 @@ def run_finals(ctx):
 
 def run_deferred(ctx):
     """Called with the side stream current and ordered behind everything enqueued on the compute stream so far."""
-    pend = getattr(ctx, "deferred", None)
+    pend = ctx.deferred
     if pend:
         for fn in pend:
             fn()
         del pend[:]
-    if getattr(ctx, "finals_bytes", 0) >= FINALS_FLUSH_BYTES:
+    if ctx.finals_bytes >= FINALS_FLUSH_BYTES:
         run_finals(ctx)
 
 
 def flush_deferred(ctx):
-    side = getattr(ctx, "wgrad_stream", None)
-    if side is not None and (getattr(ctx, "deferred", None) or getattr(ctx, "finals", None)):
+    side = ctx.wgrad_stream
+    if side is not None and (ctx.deferred or ctx.finals):
         _lib.wait_stream(side, torch.cuda.current_stream())
         with torch.cuda.stream(side):
             run_deferred(ctx)
@@ -1101,7 +1166,7 @@ class HipNet(nn.Module):
 
     def backward_raw(self, dlogits5=None, on_progress=None, pass_=None):
         plan, ctx = self._pass(pass_)
-        if getattr(ctx, "no_backward", False):
+        if ctx.no_backward:
             raise RuntimeError("backward_raw() after forward_raw(no_backward=True): that pass did not keep its activations")
         if on_progress is None:
             plan.backward(dlogits5, ctx)

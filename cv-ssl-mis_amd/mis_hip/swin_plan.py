@@ -1,7 +1,8 @@
-"""Static forward/backward executor for the token-major (B*L, C) layers of SwinUnet.
+"""The token-major (B*L, C) ops of SwinUnet, UNETR and SwinUNETR, and SwinUnet's plan.
 
-Same idea as ``mis_hip.plan`` (one pre-allocated op list, reverse walk for backward, gradients
-straight into the flat buffer), over 2-D token tensors.  Concatenations along C
+Same idea as the volume ops of ``mis_hip.plan`` (one pre-allocated op list, reverse walk for backward, gradients
+straight into the flat buffer), over 2-D token tensors (``plan.TAct``); the walks themselves, the weight-transpose batch and
+the side-stream contract are ``plan.PlanBase``'s, which ``SwinPlan`` shares with ``plan.Plan``.  Concatenations along C
 (``torch.cat([x, skip], -1)``, reference swin_transformer_unet_skip_expand_decoder_sys.py:767) are
 column slices of one buffer; roll / window_partition / window_reverse never materialise (they are
 token-index arithmetic inside the attention kernel).
@@ -12,8 +13,9 @@ import os
 import torch
 
 from . import lib as _lib
+from . import plan as _plan
 from . import tops
-from .plan import Act, begin_finals, defer, defer_final, run_deferred, flush_deferred
+from .plan import Act, PlanBase, TAct, defer, defer_final, run_deferred      # noqa: F401  (TAct: part of this module's surface)
 
 # GEMM epilogue fusions (GELU into fc1 / fc2-dX, DropPath + residual add into proj / fc2); MIS_SWIN_FUSE=0 runs the
 # separate element-wise passes (A/B timing, and the reference point of the fusion tests)
@@ -21,54 +23,6 @@ LN_HEAD = os.environ.get("MIS_LN_HEAD", "1") != "0"        # last LayerNorm + ou
 UNSHUFFLE = os.environ.get("MIS_LN_HEAD_UNSHUFFLE", "1") != "0"   # ... whose backward stores dx through FinalPatchExpand_X4's inverse shuffle
 EXPAND_HEAD = os.environ.get("MIS_EXPAND_HEAD", "1") != "0"       # ... and its forward inside the expand GEMM's epilogue
 FUSE = int(os.environ.get("MIS_SWIN_FUSE", "7"))      # bit 0: GELU forward, bit 1: GELU backward, bit 2: residual
-
-
-class TAct:
-    """Token activation ``[rows, C]`` (fp32), optionally a column slice of a wider buffer."""
-
-    def __init__(self, rows=None, C=None, parent=None, c0=0):
-        self.parent, self.c0 = parent, c0
-        self._written = False
-        self.g = None
-        if parent is not None:
-            self.t = parent.t[:, c0:c0 + C]
-        else:
-            self.t = torch.empty((rows, C), dtype=torch.float32, device="cuda")
-
-    @property
-    def rows(self):
-        return self.t.shape[0]
-
-    @property
-    def C(self):
-        return self.t.shape[1]
-
-    def cols(self, c0, C):
-        return TAct(parent=self, c0=c0, C=C)
-
-    def grad(self):
-        if self.g is None:
-            if self.parent is not None:
-                self.g = self.parent.grad()[:, self.c0:self.c0 + self.t.shape[1]]
-            else:
-                self.g = torch.empty_like(self.t)
-        return self.g
-
-    def _root(self):
-        a = self
-        while a.parent is not None:
-            a = a.parent
-        return a
-
-    @property
-    def written(self):
-        return self._written or self._root()._written
-
-    def mark_written(self):
-        self._written = True
-
-    def reset(self):
-        self._written = False
 
 
 class LinearOp:
@@ -86,21 +40,21 @@ class LinearOp:
         self.w2 = w.data.view(w.data.shape[0], -1)
         self.gw2 = w.grad.view(w.grad.shape[0], -1)
         self.wT = None
-        self.wT_batched = False      # True: the plan transposes every Linear weight in one launch (SwinPlan.backward)
+        self.wT_batched = False      # True: the plan transposes every Linear weight in one launch (PlanBase._transpose_weights)
         self.gelu = self.res = self.dx_gelu = None
         self.b3 = self.bT3 = None    # W / W^T cut into bf16 pieces once per pass (split_linear_weights)
         self._dw_ws, self._dw_jobs = None, {}      # own split-K workspace of the weight gradient + its finishing-sum jobs
 
     def _b3(self, ctx):
-        return self.b3 if getattr(ctx, "b3_fwd", False) else None
+        return self.b3 if ctx.b3_fwd else None
 
     def _bT3(self, ctx):
-        return self.bT3 if getattr(ctx, "b3_bwd", False) else None
+        return self.bT3 if ctx.b3_bwd else None
 
     def fwd(self, ctx):
         bias = None if self.b is None else self.b.data
         if (FUSE & 1) and self.gelu is not None:
-            pre = None if getattr(ctx, "no_backward", False) else self.y.t      # only the backward reads the pre-activation
+            pre = None if ctx.no_backward else self.y.t      # only the backward reads the pre-activation
             if tops.gemm_ex(self.x.t, self.w2, pre, tops.EP_GELU_FWD, bias=bias, C2=self.gelu.y.t, b3=self._b3(ctx)):
                 self.gelu.skip_fwd = True
                 return
@@ -121,7 +75,7 @@ class LinearOp:
 
     def _wgrad(self, dy, ctx=None):
         db = None if self.b is None else self.b.grad
-        if ctx is not None and getattr(ctx, "finals", None) is not None and self.gw2.is_contiguous() and \
+        if ctx is not None and ctx.finals is not None and self.gw2.is_contiguous() and \
                 self.gw2.shape[0] % 4 == 0 and self.gw2.shape[1] % 4 == 0:
             # split contraction: the k-slices' partials stay in a workspace of this layer's own and their sums join the pass's
             # batch of finishing sums (plan.defer_final) -- no gemm_reduce launch per Linear
@@ -149,7 +103,7 @@ class LinearOp:
         dy = self.y.grad()
         # dW / db need only (x, dy) and nothing downstream needs them: on the plan's side stream they run beside the
         # dX chain (mis_hip.plan.WGRAD_STREAM)
-        side = getattr(ctx, "wgrad_stream", None) if self.need_dx else None
+        side = ctx.wgrad_stream if self.need_dx else None
         if side is not None:
             _lib.wait_stream(side, torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -189,17 +143,16 @@ def pair_ln_residual(ops_list):
             r.ln_next = ln           # forward: the producing GEMM's epilogue may run this LayerNorm (LinearOp.fwd)
 
 
-def split_linear_weights(holder, ops_list, transposed):
-    """Every Linear weight of the op list (``transposed``: its W^T, which the plan's transpose batch just wrote) cut into the
+def split_linear_weights(plan, transposed):
+    """Every Linear weight of the plan's op list (``transposed``: its W^T, which the plan's transpose batch just wrote) cut into the
     bf16 piece planes the NT GEMMs consume, in one launch; the weights changed with the last SGD / EMA update, so once per
     forward and once per backward.  Returns True when the ops' ``b3`` / ``bT3`` are current (False: bf16x3 products are off)."""
     if not tops.split_active():
         return False
-    key = "_split_bwd" if transposed else "_split_fwd"
-    batch = getattr(holder, key, None)
+    batch = plan._split[transposed]
     if batch is None:
         splits = []
-        for op in ops_list:
+        for op in plan.ops:
             if not isinstance(op, LinearOp) or not op.w2.is_contiguous():
                 continue
             n_out, k_in = op.w2.shape
@@ -217,7 +170,7 @@ def split_linear_weights(holder, ops_list, transposed):
                 op.b3 = tops.SplitB(op.w2, rows=None if staged_only else op.x.rows)
                 splits.append(op.b3)
         batch = tops.SplitBatch(splits) if splits else False
-        setattr(holder, key, batch)
+        plan._split[transposed] = batch
     if batch:
         batch.run()
     return bool(batch)
@@ -273,13 +226,12 @@ class LayerNormOp:
 
     @staticmethod
     def _can_defer(ctx):
-        from .plan import DEFER
-        return DEFER and getattr(ctx, "wgrad_stream", None) is not None and getattr(ctx, "deferred", None) is not None
+        return _plan.DEFER and ctx.wgrad_stream is not None and ctx.deferred is not None
 
     def _defer_final(self, ctx):
         """The affine gradients from the partial rows in ``_ws``: a job of the pass's batch of finishing sums, else the deferred
         per-op launch; False: neither (the caller finishes on its own stream)."""
-        if getattr(ctx, "finals", None) is not None and self.g.grad is not None and self.b.grad is not None:
+        if ctx.finals is not None and self.g.grad is not None and self.b.grad is not None:
             if self._job is None:
                 C = self.x.t.shape[1]
                 self._job = tops.ColsumJob(self._ws.view(torch.float32), 0, C, tops.colreduce_slabs(self.x.rows), C, True,
@@ -327,7 +279,7 @@ class AttnOp:
                 self._ws = tops.window_attention_workspace(*self.geo[:4], window=self.window)
             tops.window_attention_bwd_parts(self.qkv.t, self.out.grad(), self.qkv.grad(), self.table.data, self._ws,
                                             *self.geo, self.scale, window=self.window)
-            if getattr(ctx, "finals", None) is not None and self.table.grad.is_contiguous():
+            if ctx.finals is not None and self.table.grad.is_contiguous():
                 if self._job is None:
                     shape = tops.window_attention_table_partials(*self.geo[:4], window=self.window)
                     self._job = False if shape is None else tops.ColsumJob(self._ws.view(torch.float32), 0, shape[1], shape[0],
@@ -353,7 +305,7 @@ class ResidualOp:
         self.a, self.y, self.out = a, y, out
         self.rps, self.drop_p, self.site = rows_per_sample, drop_p, site
         self._p, self._salt, self._state, self._scale = 0.0, 0, None, None
-        self.plan = None            # set by SwinPlan.add: the per-forward DropPath scale table lives there
+        self.plan = None            # set by SwinPlan.push: the per-forward DropPath scale table lives there
         self.skip_fwd = self.skip_bwd = False
         self.ln_next = None         # the LayerNormOp directly behind this op that reads ``out`` (pair_ln_residual)
 
@@ -414,7 +366,7 @@ class ExpandLinearOp(LinearOp):
     def fwd(self, ctx):
         B, H, W, c, P = self.geo
         h = self.ln_head if EXPAND_HEAD else None
-        keep = None if getattr(ctx, "no_backward", False) else self.sh.t     # the shuffled tokens: only the backward reads them
+        keep = None if ctx.no_backward else self.sh.t     # the shuffled tokens: only the backward reads them
         if h is not None and tops.gemm_expand_ln_head(self.x.t, self.w2, keep, B, H, W, P, c, h.g.data, h.b.data, h.w2,
                                                       h.mean, h.rstd, h.logits.t, b3=self._b3(ctx)):
             h.skip_fwd = True        # LayerNorm + output head ran in this GEMM's epilogue
@@ -661,38 +613,24 @@ class Merge3dOp:
         self.src.mark_written()
 
 
-class SwinPlan:
-    """Op list + buffers of one SwinUnet for one input geometry; same interface as ``plan.Plan``."""
+class SwinPlan(PlanBase):
+    """The plan of SwinUnet: token ops only, over the image ``inp_t``; the per-forward DropPath scale table of its residuals."""
 
     def __init__(self, net, in_shape):
-        self.net = net
-        self.in_shape = tuple(in_shape)      # (N, 1, 1, H, W)
-        self.ops, self.acts = [], []
+        super().__init__(net, in_shape)      # (N, 1, 1, H, W)
         self.inp_t = None
         self._site = itertools.count(0)
-        self.out = None
-        self.generation = 0      # forwards run on this plan (see mis_hip.plan.Plan / _NetFn.backward)
-        self._progress = None
-        self._wgrad_stream = None
-        self._tbatch = None
         self._dp_gen, self._dp_const = -1, None
-        self._paired = False
-
-    def new(self, rows, C):
-        a = TAct(rows, C)
-        self.acts.append(a)
-        return a
 
     def cols(self, parent, c0, C):
         a = parent.cols(c0, C)
         self.acts.append(a)
         return a
 
-    def add(self, op):
+    def push(self, op):
         if isinstance(op, ResidualOp):
-            op.plan = self
-        self.ops.append(op)
-        return op
+            op.plan = self          # DropPath p > 0: the scale table below
+        return super().push(op)
 
     def droppath_scales(self, ctx):
         """[sites][B] DropPath scales of THIS forward pass (one launch per forward, cached by generation): the values
@@ -720,71 +658,12 @@ class SwinPlan:
     def next_site(self):
         return next(self._site)
 
-    def transpose_weights(self, ops_list=None):
-        """W^T of every Linear that needs a data gradient, one launch (the weights changed with the last SGD update)."""
-        if self._tbatch is None:
-            jobs = []
-            for op in (self.ops if ops_list is None else ops_list):
-                if isinstance(op, LinearOp) and op.need_dx and op.w2.is_contiguous():
-                    op.wT = torch.empty((op.w2.shape[1], op.w2.shape[0]), dtype=torch.float32, device="cuda")
-                    op.wT_batched = True
-                    jobs.append((op.w2, op.wT))
-            self._tbatch = tops.TransposeBatch(jobs) if jobs else False
-        if self._tbatch:
-            self._tbatch.run()
-
-    def forward(self, x5, ctx):
-        assert tuple(x5.shape) == self.in_shape, (tuple(x5.shape), self.in_shape)
-        if not self._paired:
-            pair_ln_residual(self.ops)
-            self._paired = True
-        self.generation += 1
+    def _begin_forward(self, x5):
+        self._pair_token_ops()               # from the first forward on (a mixed plan.Plan: from its first backward on)
         self.inp_t = x5[:, :, 0]             # [N, 1 | 3, H, W]
-        ctx.b3_fwd = split_linear_weights(self, self.ops, False)
-        for op in self.ops:
-            op.fwd(ctx)
-        return self.out.t
 
-    def backward(self, dlogits5, ctx, on_progress=None):
-        for a in self.acts:
-            a.reset()
-        self.out.reset()
-        if dlogits5 is not None:
-            self.out.g = dlogits5
-        if not self._paired:
-            pair_ln_residual(self.ops)
-            self._paired = True
-        self.transpose_weights()
-        ctx.b3_bwd = split_linear_weights(self, self.ops, True)
-        from . import plan as _plan
-        main, side = torch.cuda.current_stream(), None
-        if _plan.WGRAD_STREAM:
-            if self._wgrad_stream is None:
-                self._wgrad_stream = _lib.side_stream("wgrad")
-            side = self._wgrad_stream
-        ctx.wgrad_stream = side
-        ctx.deferred = [] if side is not None else None
-        begin_finals(ctx, self)
-        if on_progress is None:
-            for op in reversed(self.ops):
-                op.bwd(ctx)
-            flush_deferred(ctx)
-            ctx.deferred = ctx.finals = None
-            if side is not None:
-                _lib.wait_stream(main, side)
-            return
-        if self._progress is None:
-            from .dist import param_progress
-            self._progress = param_progress(self.ops, self.net.flat_grad)
-        report = _plan.progress_reporter(on_progress, main, side, before=lambda: flush_deferred(ctx))
-        for i in range(len(self.ops) - 1, -1, -1):      # see mis_hip.plan.Plan.backward
-            self.ops[i].bwd(ctx)
-            if i == 0 or self._progress[i] != self._progress[i - 1] or i == len(self.ops) - 1:
-                report(self._progress[i])
-        flush_deferred(ctx)
-        ctx.deferred = ctx.finals = None
-        if side is not None:
-            _lib.wait_stream(main, side)
+    def _begin_backward(self):
+        self.out.reset()                     # the logits are a volume buffer of their own (new_logits), not one of ``acts``
 
     def drop_sites(self):
         return [op.site for op in self.ops if isinstance(op, ResidualOp) and op.drop_p > 0]

@@ -117,14 +117,7 @@ class SwinUNETR(HipNet):
                                f"(MONAI _check_input_size); got {plan.in_shape}")
         P, f, B = self.P, self.fs, N
 
-        def tok(rows, C_):
-            a = sp.TAct(rows, C_)
-            plan.acts.append(a)
-            return a
-
-        def add(op):
-            plan.ops.append(op)
-            return op
+        tok, add = plan.tok, plan.push       # token buffers and ops (ResidualOp.plan stays unset: DropPath p is 0 here)
 
         # ---- Swin encoder (token-major [B, d, h, w, C]) ----
         dims = (D0 // 2, H0 // 2, W0 // 2)

@@ -129,14 +129,10 @@ class UNETR(HipNet):
         P, H, f, L, B = self.P, self.hid, self.fs, self.L, N
         rows = B * L
 
-        def tok(C_):
-            a = sp.TAct(rows, C_)
-            plan.acts.append(a)
-            return a
+        add = plan.push      # token ops (ResidualOp.plan stays unset: DropPath p is 0 here)
 
-        def add(op):
-            plan.ops.append(op)
-            return op
+        def tok(C_):
+            return plan.tok(rows, C_)
 
         # ---- ViT encoder (token-major) ----
         cols = tok(4096)

@@ -191,29 +191,29 @@ class SwinUnet(HipNet):
     def _block(self, plan, p, x, out, B, res, dim, heads, shift, dp):
         P = self.P
         rows, L = B * res * res, res * res
-        n1 = plan.new(rows, dim)
-        plan.add(sp.LayerNormOp(x, n1, P(p + ".norm1.weight"), P(p + ".norm1.bias")))
-        qkv = plan.new(rows, 3 * dim)
-        plan.add(sp.LinearOp(n1, qkv, P(p + ".attn.qkv.weight"), P(p + ".attn.qkv.bias")))
-        att = plan.new(rows, dim)
-        plan.add(sp.AttnOp(qkv, att, P(p + ".attn.relative_position_bias_table"), B, res, res, heads, shift,
+        n1 = plan.tok(rows, dim)
+        plan.push(sp.LayerNormOp(x, n1, P(p + ".norm1.weight"), P(p + ".norm1.bias")))
+        qkv = plan.tok(rows, 3 * dim)
+        plan.push(sp.LinearOp(n1, qkv, P(p + ".attn.qkv.weight"), P(p + ".attn.qkv.bias")))
+        att = plan.tok(rows, dim)
+        plan.push(sp.AttnOp(qkv, att, P(p + ".attn.relative_position_bias_table"), B, res, res, heads, shift,
                            window=self.ws))
-        pr = plan.new(rows, dim)
-        proj = plan.add(sp.LinearOp(att, pr, P(p + ".attn.proj.weight"), P(p + ".attn.proj.bias")))
-        x1 = plan.new(rows, dim)
-        proj.res = plan.add(sp.ResidualOp(x, pr, x1, L, dp, plan.next_site()))    # fused into proj's epilogue
-        n2 = plan.new(rows, dim)
-        plan.add(sp.LayerNormOp(x1, n2, P(p + ".norm2.weight"), P(p + ".norm2.bias")))
+        pr = plan.tok(rows, dim)
+        proj = plan.push(sp.LinearOp(att, pr, P(p + ".attn.proj.weight"), P(p + ".attn.proj.bias")))
+        x1 = plan.tok(rows, dim)
+        proj.res = plan.push(sp.ResidualOp(x, pr, x1, L, dp, plan.next_site()))    # fused into proj's epilogue
+        n2 = plan.tok(rows, dim)
+        plan.push(sp.LayerNormOp(x1, n2, P(p + ".norm2.weight"), P(p + ".norm2.bias")))
         hdim = int(dim * self.mlp_ratio)
-        h = plan.new(rows, hdim)
-        fc1 = plan.add(sp.LinearOp(n2, h, P(p + ".mlp.fc1.weight"), P(p + ".mlp.fc1.bias")))
-        hg = plan.new(rows, hdim)
-        fc1.gelu = gelu = plan.add(sp.GeluOp(h, hg))                               # GELU in fc1's epilogue
-        m = plan.new(rows, dim)
-        fc2 = plan.add(sp.LinearOp(hg, m, P(p + ".mlp.fc2.weight"), P(p + ".mlp.fc2.bias")))
+        h = plan.tok(rows, hdim)
+        fc1 = plan.push(sp.LinearOp(n2, h, P(p + ".mlp.fc1.weight"), P(p + ".mlp.fc1.bias")))
+        hg = plan.tok(rows, hdim)
+        fc1.gelu = gelu = plan.push(sp.GeluOp(h, hg))                               # GELU in fc1's epilogue
+        m = plan.tok(rows, dim)
+        fc2 = plan.push(sp.LinearOp(hg, m, P(p + ".mlp.fc2.weight"), P(p + ".mlp.fc2.bias")))
         fc2.dx_gelu = gelu                                                         # gelu' in fc2's dX epilogue
-        x2 = out if out is not None else plan.new(rows, dim)
-        fc2.res = plan.add(sp.ResidualOp(x1, m, x2, L, dp, plan.next_site()))      # residual add in fc2's epilogue
+        x2 = out if out is not None else plan.tok(rows, dim)
+        fc2.res = plan.push(sp.ResidualOp(x1, m, x2, L, dp, plan.next_site()))      # residual add in fc2's epilogue
         return x2
 
     def _expand(self, plan, p, x, out, B, res, dim, P_, norm=True):
@@ -222,13 +222,13 @@ class SwinUnet(HipNet):
         rows = B * res * res
         cout = (2 * dim) if P_ == 2 else 16 * dim
         c = cout // (P_ * P_)
-        e = plan.new(rows, cout)               # token-major expansion: only its gradient is ever materialised
-        sh = plan.new(rows * P_ * P_, c)
-        plan.add(sp.ExpandLinearOp(x, e, sh, self.P(p + ".expand.weight"), (B, res, res, c, P_)))
+        e = plan.tok(rows, cout)               # token-major expansion: only its gradient is ever materialised
+        sh = plan.tok(rows * P_ * P_, c)
+        plan.push(sp.ExpandLinearOp(x, e, sh, self.P(p + ".expand.weight"), (B, res, res, c, P_)))
         if not norm:
             return sh
-        y = out if out is not None else plan.new(rows * P_ * P_, c)
-        plan.add(sp.LayerNormOp(sh, y, self.P(p + ".norm.weight"), self.P(p + ".norm.bias")))
+        y = out if out is not None else plan.tok(rows * P_ * P_, c)
+        plan.push(sp.LayerNormOp(sh, y, self.P(p + ".norm.weight"), self.P(p + ".norm.bias")))
         return y
 
     def _build(self, plan):
@@ -246,14 +246,14 @@ class SwinUnet(HipNet):
         cat = {}
         for i in range(1, nl):
             k = nl - 1 - i
-            cat[k] = plan.new(B * (pr // 2 ** k) ** 2, 2 * E * 2 ** k)
-        cols = plan.new(B * pr * pr, self.in_chans * 16)
-        plan.add(sp.Im2colOp(plan, cols, self.in_chans))
-        e0 = plan.new(B * pr * pr, E)
-        plan.add(sp.LinearOp(cols, e0, Pn("swin_unet.patch_embed.proj.weight"), Pn("swin_unet.patch_embed.proj.bias"),
+            cat[k] = plan.tok(B * (pr // 2 ** k) ** 2, 2 * E * 2 ** k)
+        cols = plan.tok(B * pr * pr, self.in_chans * 16)
+        plan.push(sp.Im2colOp(plan, cols, self.in_chans))
+        e0 = plan.tok(B * pr * pr, E)
+        plan.push(sp.LinearOp(cols, e0, Pn("swin_unet.patch_embed.proj.weight"), Pn("swin_unet.patch_embed.proj.bias"),
                              need_dx=False))
         x = plan.cols(cat[0], E, E)                       # x_downsample[0]
-        plan.add(sp.LayerNormOp(e0, x, Pn("swin_unet.patch_embed.norm.weight"), Pn("swin_unet.patch_embed.norm.bias")))
+        plan.push(sp.LayerNormOp(e0, x, Pn("swin_unet.patch_embed.norm.weight"), Pn("swin_unet.patch_embed.norm.bias")))
         di = 0
         for i in range(nl):
             dim, res = E * 2 ** i, pr // 2 ** i
@@ -263,24 +263,24 @@ class SwinUnet(HipNet):
                 di += 1
             if i < nl - 1:                               # PatchMerging (:325-346)
                 p = f"swin_unet.layers.{i}.downsample"
-                g = plan.new(B * (res // 2) ** 2, 4 * dim)
-                plan.add(sp.RearrangeOp(x, g, B, res, res, dim, 2, 0))
-                n = plan.new(B * (res // 2) ** 2, 4 * dim)
-                plan.add(sp.LayerNormOp(g, n, Pn(p + ".norm.weight"), Pn(p + ".norm.bias")))
-                nxt = plan.cols(cat[i + 1], 2 * dim, 2 * dim) if (i + 1) in cat else plan.new(B * (res // 2) ** 2, 2 * dim)
-                plan.add(sp.LinearOp(n, nxt, Pn(p + ".reduction.weight"), None))
+                g = plan.tok(B * (res // 2) ** 2, 4 * dim)
+                plan.push(sp.RearrangeOp(x, g, B, res, res, dim, 2, 0))
+                n = plan.tok(B * (res // 2) ** 2, 4 * dim)
+                plan.push(sp.LayerNormOp(g, n, Pn(p + ".norm.weight"), Pn(p + ".norm.bias")))
+                nxt = plan.cols(cat[i + 1], 2 * dim, 2 * dim) if (i + 1) in cat else plan.tok(B * (res // 2) ** 2, 2 * dim)
+                plan.push(sp.LinearOp(n, nxt, Pn(p + ".reduction.weight"), None))
                 x = nxt
         dimb, resb = E * 2 ** (nl - 1), pr // 2 ** (nl - 1)
-        xn = plan.new(B * resb * resb, dimb)
-        plan.add(sp.LayerNormOp(x, xn, Pn("swin_unet.norm.weight"), Pn("swin_unet.norm.bias")))
+        xn = plan.tok(B * resb * resb, dimb)
+        plan.push(sp.LayerNormOp(x, xn, Pn("swin_unet.norm.weight"), Pn("swin_unet.norm.bias")))
         # decoder
         k = nl - 2
         x = self._expand(plan, "swin_unet.layers_up.0", xn, plan.cols(cat[k], 0, dimb // 2), B, resb, dimb, 2)
         for i in range(1, nl):
             k = nl - 1 - i
             dim, res = E * 2 ** k, pr // 2 ** k
-            c = plan.new(B * res * res, dim)
-            plan.add(sp.LinearOp(cat[k], c, Pn(f"swin_unet.concat_back_dim.{i}.weight"),
+            c = plan.tok(B * res * res, dim)
+            plan.push(sp.LinearOp(cat[k], c, Pn(f"swin_unet.concat_back_dim.{i}.weight"),
                                  Pn(f"swin_unet.concat_back_dim.{i}.bias")))
             x = c
             base = sum(self.depths[:k])
@@ -290,8 +290,8 @@ class SwinUnet(HipNet):
             if i < nl - 1:
                 x = self._expand(plan, f"swin_unet.layers_up.{i}.upsample", x, plan.cols(cat[k - 1], 0, dim // 2), B,
                                  res, dim, 2)
-        xu = plan.new(B * pr * pr, E)
-        plan.add(sp.LayerNormOp(x, xu, Pn("swin_unet.norm_up.weight"), Pn("swin_unet.norm_up.bias")))
+        xu = plan.tok(B * pr * pr, E)
+        plan.push(sp.LayerNormOp(x, xu, Pn("swin_unet.norm_up.weight"), Pn("swin_unet.norm_up.bias")))
         plan.out = sp.new_logits(B, self.num_classes, H, W)
         if sp.LnHeadOp.eligible(E, self.num_classes):      # up.norm + output in one pass over the 16x expanded tokens
             sh = self._expand(plan, "swin_unet.up", xu, None, B, pr, E, 4, norm=False)
@@ -301,10 +301,10 @@ class SwinUnet(HipNet):
             head.expand = expand if isinstance(expand, sp.ExpandLinearOp) else None
             if head.expand is not None:
                 head.expand.ln_head = head
-            plan.add(head)
+            plan.push(head)
         else:
             xf = self._expand(plan, "swin_unet.up", xu, None, B, pr, E, 4)
-            plan.add(sp.HeadOp(xf, Pn("swin_unet.output.weight"), plan.out))
+            plan.push(sp.HeadOp(xf, Pn("swin_unet.output.weight"), plan.out))
 
 
 ViT_seg = SwinUnet

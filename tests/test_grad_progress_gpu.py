@@ -1,4 +1,4 @@
-"""The data-parallel overlap contract of ``Plan.backward(on_progress=...)`` / ``SwinPlan.backward`` on one GPU.
+"""The data-parallel overlap contract of ``PlanBase.backward(on_progress=...)`` (``Plan`` and ``SwinPlan`` share it) on one GPU.
 
 ``mis_hip.dist.GradBucketer`` all-reduces a bucket of the flat gradient buffer as soon as ``on_progress(lo)`` reports
 that everything at offsets >= lo is final (``dist.param_progress``: the highest gradient range of the ops still to run).
