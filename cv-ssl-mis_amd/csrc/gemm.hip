@@ -29,6 +29,7 @@
 // (deterministic).  Workgroups are ordered XCD-aware over one linear (k-slice, tile) index.
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -63,7 +64,7 @@ struct GemmArgs {
     // NT only, optional (mis_gemm_nt_split): B as the three bf16 piece planes mis_gemm_split_b wrote (PREC = 2 kernels; the
     // fp32 B is not read).  b3_plane = bytes of one plane (N x K3 x 2), K3 = K rounded up to the k-step
     const void* B3; unsigned b3_plane; int K3;
-    int bm_force;          // host only: rows per tile chosen by the caller (0: nt_tile_m)
+    int bm_force;          // unused (the rows per tile are the host plan's); kept for the layout of the kernel argument
     // EP_LNHEAD (mis_gemm_expand_ln_head): LayerNorm over the c = 96 columns of a tile row (= one token of the pixel-shuffled
     // tensor) + the bias-free output head, in the epilogue; C may be NULL (the expanded tokens are not kept)
     const float* ln_g; const float* ln_b; const float* head_w;
@@ -72,6 +73,10 @@ struct GemmArgs {
 };
 
 enum { EP_NONE = 0, EP_GELU_FWD = 1, EP_GELU_BWD = 2, EP_RESIDUAL = 3, EP_LNHEAD = 4, EP_RESIDUAL_LN = 5 };
+
+// an integer knob of the environment, knob(getenv("MIS_GEMM_.."), default): the callers keep it in a function-local static
+// (read once, at first use), each knob in one place
+int knob(const char* value, int dflt) { return value ? atoi(value) : dflt; }
 
 // same functions as token_ops.hip::gelu_kernel (common.h)
 __device__ __forceinline__ float gelu_f(float x) { return mis_gelu(x); }
@@ -158,7 +163,7 @@ __global__ __launch_bounds__(256) void gemm_split_batch_kernel(const SplitJob* _
 // products (attention_impl.inc) as bf16x3 products; 0 = fp32 MFMA everywhere.  Default 7 (MIS_GEMM_BF3 overrides at load;
 // mis_gemm_set_split_precision at run time: bench.py times both).
 std::atomic<int>& gemm_bf3_state() {
-    static std::atomic<int> m{[] { const char* e = getenv("MIS_GEMM_BF3"); return e ? atoi(e) & 7 : 7; }()};
+    static std::atomic<int> m{knob(getenv("MIS_GEMM_BF3"), 7) & 7};
     return m;
 }
 bool gemm_bf3() { return gemm_bf3_state().load(std::memory_order_relaxed) & 1; }
@@ -1773,45 +1778,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MIS_TN_REG_
         }
 }
 
-// the register-only TN form serves this shape (widths multiples of 96, 8-byte aligned float2 rows)
-bool tn_reg_ok(const float* A, long long lda, const float* B, long long ldb, const float* C, long long ldc, int M, int N, int K) {
-    static const bool on = [] { const char* e = getenv("MIS_GEMM_TN_REG"); return !(e && e[0] == '0'); }();
-    return on && M % RT == 0 && N % RT == 0 && lda % 2 == 0 && ldb % 2 == 0 && ldc % 2 == 0 &&
-           !((uintptr_t)A & 7) && !((uintptr_t)B & 7) && !((uintptr_t)C & 7) && K >= 64;
-}
-// workgroup slices: one resident workgroup per CU (a wave = 144 accumulator + 48 ring registers); a wave wants >= 16 groups
-int tn_reg_slices(int M, int N, int K) {
-    const long long tiles = (long long)(M / RT) * (N / RT);
-    long long ks = (256 * MIS_TN_REG_WAVES) / tiles;
-    const long long kmax = K / (4 * 64);
-    if (ks > kmax) ks = kmax;
-    if (ks < 1) ks = 1;
-    return (int)ks;
-}
-// rows per workgroup slice: a multiple of 16 (4 waves x groups of 4 rows)
-void tn_reg_plan(GemmArgs& a) {
-    a.KS = tn_reg_slices(a.M, a.N, a.K);
-    a.kchunk = (int)(mis_cdiv(mis_cdiv(a.K, a.KS), 16) * 16);
-    a.KS = (int)mis_cdiv(a.K, a.kchunk);
-    a.tiles_n = a.N / RT; a.tiles_m = a.M / RT;
-    const long long nb = (long long)a.tiles_n * a.tiles_m * a.KS;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-}
-int launch_tn_reg(GemmArgs& a, hipStream_t stream) {
-    constexpr int LDSB = 2 * 36 * 64 * 16 + 2 * 64 * 6 * 4;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (gemm_bf3_tn()) {
-        static std::atomic<unsigned long long> attr_done1{0};
-        if (mis_set_lds_attr(reinterpret_cast<const void*>(&gemm_tn_reg_kernel<1>), LDSB, attr_done1) != MIS_OK) return MIS_ERR_LAUNCH;
-        hipLaunchKernelGGL(gemm_tn_reg_kernel<1>, dim3(a.n_blocks_padded), dim3(256), LDSB, stream, a);
-        return mis_launch_status();
-    }
-    if (mis_set_lds_attr(reinterpret_cast<const void*>(&gemm_tn_reg_kernel<0>), LDSB, attr_done) != MIS_OK) return MIS_ERR_LAUNCH;
-    hipLaunchKernelGGL(gemm_tn_reg_kernel<0>, dim3(a.n_blocks_padded), dim3(256), LDSB, stream, a);
-    return mis_launch_status();
-}
-
 // C[m][n] (+)= bias[n] + sum_k ws[k][m][n]   (fixed order)
 // block = 32 consecutive elements x 8 slice lanes: lane kl sums slices kl, kl+8, ... (four loads in flight), then a
 // fixed-order LDS tree over the 8 lanes -- the reduction is latency-bound (dW of a 96 x 288 Linear: 64+ slices of
@@ -1867,12 +1833,19 @@ __global__ __launch_bounds__(256) void gemm_reduce_kernel(const GemmArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ host dispatch
+// An entry point validates its operands and fills a GemmArgs; its family's plan function (plan_nt, plan_nt_rega, plan_tn) then
+// decides everything about the launch, ONCE: kernel family and template parameters, grid, k slices and tile counts (written
+// into the GemmArgs the kernel reads), the reduce launch.  run() launches a plan, plan_name() prints it, the *_workspace_bytes
+// queries read its slices: what a profile row says and what a workspace holds cannot drift from what runs.
+
+// ---- tile rules and cost models
 // tile edge of the TN form / tile width of the NT form: 96 when it removes padding
 int tn_tile(int M, int N) { return (M % 96 == 0 && N % 96 == 0 && (M % 128 != 0 || N % 128 != 0)) ? 96 : 128; }
 int nt_tile_n(int N) { return (N % 96 == 0 && N % 128 != 0) ? 96 : 128; }
 // pre-split B: a 64 x 96 tile keeps three workgroups per CU (52 KB of LDS; 64 x 128 needs 64 KB: two)
 int nt_tile_n_b3(int N) {       // (MIS_GEMM_B3_RULE=0 sweeps only)
-    static const int pref = getenv("MIS_GEMM_B3_BN") ? atoi(getenv("MIS_GEMM_B3_BN")) : 96;
+    static const int pref = knob(getenv("MIS_GEMM_B3_BN"), 96);
     if (pref == 96 && N % 96 == 0) return 96;
     return nt_tile_n(N);
 }
@@ -1885,7 +1858,7 @@ int nt_tile_n_b3(int N) {       // (MIS_GEMM_B3_RULE=0 sweeps only)
 // slices + reduction (49 + 20 us) or 162 tiles unsplit -- the cost model below (workgroup time ~ rows x K / slices, +
 // a fixed share per round, + the reduction) picks between them.
 void nt_choice(int M, int N, int K, int& bm, int& ks, int rows_arg = 0, int bn_arg = 0) {
-    static const int force_env = getenv("MIS_GEMM_BM") ? atoi(getenv("MIS_GEMM_BM")) : 0;
+    static const int force_env = knob(getenv("MIS_GEMM_BM"), 0);
     const int force = rows_arg ? rows_arg : force_env;
     const long long tn = mis_cdiv(N, bn_arg ? bn_arg : nt_tile_n(N));
     if (force != 128 && mis_cdiv(M, 128) * tn >= 512) {      // plenty of tiles: 64 rows = three resident workgroups per CU
@@ -1903,7 +1876,7 @@ void nt_choice(int M, int N, int K, int& bm, int& ks, int rows_arg = 0, int bn_a
         const long long rounds = mis_cdiv(tiles * s, 256);
         // units: one row of a tile over one k; 128 rows x 768 k = 40 us measured -> 2458 units / us.  bf16x3 products run the
         // k-loop ~2x faster (MIS_GEMM_NT_BF3_SCALE percent of the fp32 k-loop cost), the fixed costs stay: fewer slices pay
-        static const int bf3_pct = getenv("MIS_GEMM_NT_BF3_SCALE") ? atoi(getenv("MIS_GEMM_NT_BF3_SCALE")) : 50;
+        static const int bf3_pct = knob(getenv("MIS_GEMM_NT_BF3_SCALE"), 50);
         const long long kloop = (long long)rows * mis_cdiv(K, s) * (gemm_bf3() ? bf3_pct : 100) / 100;
         long long cost = rounds * (kloop + 128 * 96);
         if (s > 1) cost += 49152 + (long long)(0.0039 * (double)s * M * N);
@@ -1912,22 +1885,23 @@ void nt_choice(int M, int N, int K, int& bm, int& ks, int rows_arg = 0, int bn_a
     }
 }
 
-int nt_tile_m(int M, int N, int K);
+// rows per tile and k slices of the NT form on fp32 B: 64 rows for the short contractions of the first stages (K = 96 / 192 over
+// 10^4 .. 10^5 token rows), where a tile is a prologue, 3 .. 6 k-steps and an epilogue: three resident workgroups per CU overlap
+// them; a short contraction on 64-row tiles is never split
+void nt_rule(int M, int N, int K, int& bm, int& ks) {
+    nt_choice(M, N, K, bm, ks);
+    if (K <= 192 && (bm == 64 || mis_cdiv(M, 64) * mis_cdiv(N, nt_tile_n(N)) >= 1536)) { bm = 64; ks = 1; }
+}
 
-int pick_ks(int M, int N, int K, int trans) {
-    if (!trans) {
-        if (nt_tile_m(M, N, K) == 64 && K <= 192) return 1;      // the short contractions: never split
-        int bm, ks;
-        nt_choice(M, N, K, bm, ks);
-        return ks;
-    }
+// k slices of the staged TN form
+int tn_slices(int M, int N, int K) {
     const int bt = tn_tile(M, N);
     const long long tiles = mis_cdiv(M, bt) * mis_cdiv(N, bt);
     if (tiles >= 256) return 1;
     // slices x tiles ~ three workgroups per CU for the short contractions (deep Swin stages, UNETR's 1 728 token rows); with
     // the register prefetch of the k-loop a long contraction (>= 32 768 rows) runs better on half as many, longer slices
     // (less partial traffic): SwinUnet 28.9 -> 28.5 ms per step, UNETR keeps 43.5 (44.5 with 384 everywhere)
-    static const int forced = getenv("MIS_GEMM_TN_SLOTS") ? atoi(getenv("MIS_GEMM_TN_SLOTS")) : 0;
+    static const int forced = knob(getenv("MIS_GEMM_TN_SLOTS"), 0);
     const int slots = forced ? forced : (K >= 32768 ? 384 : 768);
     long long ks = slots / tiles;
     const long long kmax = mis_cdiv(K, 4 * BK);   // at least 4 k-steps per slice
@@ -1937,65 +1911,21 @@ int pick_ks(int M, int N, int K, int trans) {
     return (int)ks;
 }
 
-bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// (Round 4 also tried the register-only form for the NT GEMMs -- forward and dX: lanes load float4 A[m0 + 16 t + i][k0 + 4 kk ..]
-// straight into the MFMA layout, 64 x 96 wave tiles, two waves per SIMD, epilogues on registers.  Correct, and SLOWER than the
-// staged kernels on every SwinUnet shape: 2277 us against 1750 us for the 20 Linear shapes of a step, 0.26-0.47 of the pipe on the
-// K = 96 / 192 layers.  Row-major operands put the 16 lanes of a load group on 16 different rows -- 64 separate 16-byte accesses
-// per instruction for the texture-address unit, ~5000 of its cycles per 6144-cycle k-step of a CU's 8 waves; the TN form above
-// works because ITS operands are contraction-major and a lane group reads 128 contiguous bytes.  The NT GEMMs need the transpose
-// that the LDS stage provides.  Removed; scripts/gemm_nt_bench.py is the measurement.)
-
-template <int BMT, int BN, int EP, int PREC, int NW = 4>
-int launch_nt_waves(const GemmArgs& a, hipStream_t stream) {
-    static std::atomic<unsigned long long> attr_done{0};   // per instantiation, one bit per device
-    using G = NtCfg<BMT, BN, PREC, NW>;
-    if (mis_set_lds_attr(reinterpret_cast<const void*>(&gemm_nt_kernel<BMT, BN, EP, PREC, NW>), G::LDS_BYTES, attr_done) != MIS_OK)
-        return MIS_ERR_LAUNCH;
-    hipLaunchKernelGGL((gemm_nt_kernel<BMT, BN, EP, PREC, NW>), dim3(a.n_blocks_padded), dim3(NW * 64), G::LDS_BYTES, stream, a);
-    return mis_launch_status();
+// the register-only TN form serves this shape (widths multiples of 96, 8-byte aligned float2 rows, 32-bit operand offsets)
+bool tn_reg_ok(const float* A, long long lda, const float* B, long long ldb, const float* C, long long ldc, int M, int N, int K) {
+    static const bool on = knob(getenv("MIS_GEMM_TN_REG"), 1) != 0;
+    return on && M % RT == 0 && N % RT == 0 && lda % 2 == 0 && ldb % 2 == 0 && ldc % 2 == 0 &&
+           !((uintptr_t)A & 7) && !((uintptr_t)B & 7) && !((uintptr_t)C & 7) && K >= 64 &&
+           (long long)K * lda * 4 < (1LL << 31) && (long long)K * ldb * 4 < (1LL << 31);
 }
-
-// MIS_GEMM_NT_WAVES=8: eight waves per workgroup for the 64 x 96 tiles of the pre-split form.  Measured (profiles/r06_gemm_nt_waves.txt):
-// alone, most shapes gain 3 .. 10 % (six waves per SIMD hide the k-step's DMA wait and barrier), the split-K shapes lose 4 .. 11 %,
-// 1305 -> 1293 us over the 20 shapes of a step; INSIDE the step, where the weight-gradient and teacher streams already fill the idle
-// issue slots, it is 0.1 .. 0.15 ms SLOWER (SwinUnet 18.69 -> 18.80 ms, cross teaching 18.95 -> 19.12).  Default: four.
-inline bool nt_eight_waves() {
-    static const int w = getenv("MIS_GEMM_NT_WAVES") ? atoi(getenv("MIS_GEMM_NT_WAVES")) : 4;
-    return w == 8;
-}
-
-template <int BMT, int BN, int EP, int PREC>
-int launch_nt_prec(const GemmArgs& a, hipStream_t stream) {
-    if constexpr (BMT == 64 && BN == 96 && PREC == 2 && EP != EP_LNHEAD) {
-        if (nt_eight_waves()) return launch_nt_waves<BMT, BN, EP, PREC, 8>(a, stream);
-    }
-    return launch_nt_waves<BMT, BN, EP, PREC, 4>(a, stream);
-}
-
-template <int BMT, int BN, int EP>
-int launch_nt_ep(const GemmArgs& a, hipStream_t stream) {
-    if (a.B3) return launch_nt_prec<BMT, BN, EP, 2>(a, stream);
-    return gemm_bf3() ? launch_nt_prec<BMT, BN, EP, 1>(a, stream) : launch_nt_prec<BMT, BN, EP, 0>(a, stream);
-}
-
-// split-K slices write raw partials (the epilogue runs in gemm_reduce_kernel): always the plain instantiation
-template <int BMT, int BN>
-int launch_nt_bm(const GemmArgs& a, hipStream_t stream) {
-    if (a.KS > 1 || a.ep == EP_NONE) return launch_nt_ep<BMT, BN, EP_NONE>(a, stream);
-    if (a.ep == EP_GELU_FWD) return launch_nt_ep<BMT, BN, EP_GELU_FWD>(a, stream);
-    if (a.ep == EP_GELU_BWD) return launch_nt_ep<BMT, BN, EP_GELU_BWD>(a, stream);
-    return launch_nt_ep<BMT, BN, EP_RESIDUAL>(a, stream);
-}
-
-// rows per tile of the NT form: 64 for the short contractions of the first stages (K = 96 / 192 over 10^4 .. 10^5 token
-// rows), where a tile is a prologue, 3 .. 6 k-steps and an epilogue: three resident workgroups per CU overlap them
-int nt_tile_m(int M, int N, int K) {
-    if (K <= 192 && mis_cdiv(M, 64) * mis_cdiv(N, nt_tile_n(N)) >= 1536) return 64;
-    int bm, ks;
-    nt_choice(M, N, K, bm, ks);
-    return bm;
+// its workgroup slices: one resident workgroup per CU (a wave = 144 accumulator + 48 ring registers); a wave wants >= 16 groups
+int tn_reg_slices(int M, int N, int K) {
+    const long long tiles = (long long)(M / RT) * (N / RT);
+    long long ks = (256 * MIS_TN_REG_WAVES) / tiles;
+    const long long kmax = K / (4 * 64);
+    if (ks > kmax) ks = kmax;
+    if (ks < 1) ks = 1;
+    return (int)ks;
 }
 
 // Tile shape and k slices of the pre-split form, from per-shape sweeps of the SwinUnet Linears at 16, 24, 32 (256 x 256) and 48
@@ -2007,13 +1937,12 @@ int nt_tile_m(int M, int N, int K) {
 // x 768: 79 -> 63 us; 9408 x 1536 x 384: 74 -> 69).  Sums of the 20 shapes, fp32-B kernels -> this rule: 48 images 1432 ->
 // 1307 us, 32: 1352 -> 1184, 24: 897 -> 832, 16: 708 -> 653.  MIS_GEMM_B3_RULE=0: the tile choice of the fp32-B path.
 bool b3_choice(int M, int N, int K, int& bm, int& bn, int& ks) {
-    static const bool rule = !(getenv("MIS_GEMM_B3_RULE") && getenv("MIS_GEMM_B3_RULE")[0] == '0');
-    static const int kmin = getenv("MIS_GEMM_B3_KMIN") ? atoi(getenv("MIS_GEMM_B3_KMIN")) : 97;
+    static const bool rule = knob(getenv("MIS_GEMM_B3_RULE"), 1) != 0;
+    static const int kmin = knob(getenv("MIS_GEMM_B3_KMIN"), 97);
     if (K < kmin) return false;
     if (!rule) {
         bn = nt_tile_n_b3(N);
-        bm = nt_tile_m(M, N, K);
-        ks = pick_ks(M, N, K, 0);
+        nt_rule(M, N, K, bm, ks);
         return true;
     }
     const bool wide = N % 128 == 0 && N >= 1536 && mis_cdiv(M, 64) * mis_cdiv(N, 96) >= 1000;
@@ -2024,8 +1953,8 @@ bool b3_choice(int M, int N, int K, int& bm, int& bn, int& ks) {
 
 // the short-contraction kernel serves: float4 epilogue, no split-K, no pixel-shuffle store, K <= 192, many tiles
 bool nt_short(const GemmArgs& a) {
-    static const int force = getenv("MIS_GEMM_SHORT") ? atoi(getenv("MIS_GEMM_SHORT")) : -1;
-    if (force == 0 || a.KS > 1 || !a.vec4 || a.ex_P || a.K % 4 || a.B3) return false;
+    static const int force = knob(getenv("MIS_GEMM_SHORT"), -1);
+    if (force == 0 || a.KS > 1 || !a.vec4 || a.ex_P || a.K % 4 || a.K3) return false;
     // bf16x3: the K = 32 products of the general kernel win from K = 192 on (72 vs 75 us at 37632 x 576 x 192); at K = 96 the
     // short kernel's residency still pays (150528 x 384 x 96: 120 vs 132 us, x 288: 93 vs 92, scripts/gemm_nt_bench.py)
     if (gemm_bf3() && force != 1 && a.K > 96) return false;
@@ -2033,235 +1962,382 @@ bool nt_short(const GemmArgs& a) {
     return a.K <= 192 && mis_cdiv(a.M, 64) * mis_cdiv(a.N, nt_tile_n(a.N)) >= 1536;
 }
 
-template <int BN, int EP>
-int launch_nt_short_ep(const GemmArgs& a, hipStream_t stream) {
-    using G = NsCfg<BN>;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (gemm_bf3()) {
-        static std::atomic<unsigned long long> attr_done1{0};
-        if (mis_set_lds_attr(reinterpret_cast<const void*>(&gemm_nt_short_kernel<BN, EP, 1>), G::LDS_BYTES, attr_done1) != MIS_OK)
-            return MIS_ERR_LAUNCH;
-        hipLaunchKernelGGL((gemm_nt_short_kernel<BN, EP, 1>), dim3(a.n_blocks_padded), dim3(256), G::LDS_BYTES, stream, a);
-        return mis_launch_status();
-    }
-    if (mis_set_lds_attr(reinterpret_cast<const void*>(&gemm_nt_short_kernel<BN, EP, 0>), G::LDS_BYTES, attr_done) != MIS_OK)
-        return MIS_ERR_LAUNCH;
-    hipLaunchKernelGGL((gemm_nt_short_kernel<BN, EP, 0>), dim3(a.n_blocks_padded), dim3(256), G::LDS_BYTES, stream, a);
-    return mis_launch_status();
-}
-
-template <int BN>
-int launch_nt_short(const GemmArgs& a, hipStream_t stream) {
-    if (a.ep == EP_NONE) return launch_nt_short_ep<BN, EP_NONE>(a, stream);
-    if (a.ep == EP_GELU_FWD) return launch_nt_short_ep<BN, EP_GELU_FWD>(a, stream);
-    if (a.ep == EP_GELU_BWD) return launch_nt_short_ep<BN, EP_GELU_BWD>(a, stream);
-    return launch_nt_short_ep<BN, EP_RESIDUAL>(a, stream);
-}
-
-// fills tiles_m / n_blocks for the NT form and launches
-template <int BN>
-int launch_nt(GemmArgs& a, hipStream_t stream) {
-    if (nt_short(a)) {
-        a.tiles_m = (int)mis_cdiv(a.M, 64);
-        const long long nbs = (long long)a.tiles_n * a.tiles_m;
-        if (nbs > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-        a.n_blocks = (unsigned)nbs;
-        a.n_blocks_padded = (unsigned)(mis_cdiv(nbs, MIS_NUM_XCD) * MIS_NUM_XCD);
-        return launch_nt_short<BN>(a, stream);
-    }
-    const int bm = a.bm_force ? a.bm_force : nt_tile_m(a.M, a.N, a.K);
-    a.tiles_m = (int)mis_cdiv(a.M, bm);
-    const long long nb = (long long)a.tiles_n * a.tiles_m * a.KS;
-    if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    return bm == 64 ? launch_nt_bm<64, BN>(a, stream) : launch_nt_bm<BM, BN>(a, stream);
-}
-
 // the register-A kernel serves: bf16x3 products, pre-split B in the natural element order, N a multiple of 96, the float4
 // epilogue, no split-K, no pixel-shuffle store, enough 128-row tiles for three workgroups per CU (MIS_GEMM_REGA=0: never)
 bool nt_rega_shape(int M, int N, int K) {
-    static const int on = getenv("MIS_GEMM_REGA") ? atoi(getenv("MIS_GEMM_REGA")) : 1;
-    static const int kmin = getenv("MIS_GEMM_REGA_KMIN") ? atoi(getenv("MIS_GEMM_REGA_KMIN")) : 96;
-    static const int tmin = getenv("MIS_GEMM_REGA_TILES") ? atoi(getenv("MIS_GEMM_REGA_TILES")) : 512;
-    static const int mmin = getenv("MIS_GEMM_REGA_MMIN") ? atoi(getenv("MIS_GEMM_REGA_MMIN")) : 30000;
+    static const int on = knob(getenv("MIS_GEMM_REGA"), 1);
+    static const int kmin = knob(getenv("MIS_GEMM_REGA_KMIN"), 96);
+    static const int tmin = knob(getenv("MIS_GEMM_REGA_TILES"), 512);
+    static const int mmin = knob(getenv("MIS_GEMM_REGA_MMIN"), 30000);
     if (!on || !gemm_bf3() || N % 96 || N % 4 || K % 4 || K < kmin) return false;
     if ((long long)M * 4 >= (1LL << 31)) return false;
     // per-shape sweep at 48 images (scripts/gemm_nt_bench.py --rega, profiles/r06_gemm_nt_rega.txt): ahead of the staged kernels
     // for the 10^5-row stage and, at 4 x 10^4 rows, where the output is wider than the contraction; behind them below that
-    static const int msq = getenv("MIS_GEMM_REGA_MSQ") ? atoi(getenv("MIS_GEMM_REGA_MSQ")) : 100000;
+    static const int msq = knob(getenv("MIS_GEMM_REGA_MSQ"), 100000);
     // N == 96 (proj / fc2 of a 96-channel block): the register-A kernels carry the residual add AND the next LayerNorm in their
     // epilogue (mis_gemm_nt_residual_ln) -- a LayerNorm pass less outweighs the few us the staged kernel is ahead by at 7 x 10^4 rows
-    static const int n96 = getenv("MIS_GEMM_REGA_N96") ? atoi(getenv("MIS_GEMM_REGA_N96")) : 1;
+    static const int n96 = knob(getenv("MIS_GEMM_REGA_N96"), 1);
     if (M < mmin || (M < msq && N <= K && !(n96 && N == 96))) return false;
     return mis_cdiv(M, 128) * (N / 96) >= tmin;
 }
 
-template <int BN, int EP>
-int launch_nt_rega_ep(const GemmArgs& a, hipStream_t stream) {
-    static std::atomic<unsigned long long> attr_done{0};
-    constexpr int LDSB = rega_lds_bytes<BN>();
-    if (mis_set_lds_attr(reinterpret_cast<const void*>(&gemm_nt_rega_kernel<BN, EP>), LDSB, attr_done) != MIS_OK) return MIS_ERR_LAUNCH;
-    hipLaunchKernelGGL((gemm_nt_rega_kernel<BN, EP>), dim3((unsigned)a.KS), dim3(256), LDSB, stream, a);
+// (Round 4 also tried the register-only form for the NT GEMMs -- forward and dX: lanes load float4 A[m0 + 16 t + i][k0 + 4 kk ..]
+// straight into the MFMA layout, 64 x 96 wave tiles, two waves per SIMD, epilogues on registers.  Correct, and SLOWER than the
+// staged kernels on every SwinUnet shape: 2277 us against 1750 us for the 20 Linear shapes of a step, 0.26-0.47 of the pipe on the
+// K = 96 / 192 layers.  Row-major operands put the 16 lanes of a load group on 16 different rows -- 64 separate 16-byte accesses
+// per instruction for the texture-address unit, ~5000 of its cycles per 6144-cycle k-step of a CU's 8 waves; the TN form above
+// works because ITS operands are contraction-major and a lane group reads 128 contiguous bytes.  The NT GEMMs need the transpose
+// that the LDS stage provides.  Removed; scripts/gemm_nt_bench.py is the measurement.)
+
+// ---- instantiations: runtime (family, BM, BN, EP, PREC, waves) -> compiled kernel, once per family
+using LaunchFn = int (*)(unsigned grid, const GemmArgs& a, hipStream_t stream);
+struct Inst { LaunchFn launch = nullptr; int block = 0, lds = 0; };      // launch == nullptr: no such kernel is compiled
+
+template <auto KERNEL, int BLOCK, int LDS>
+int launch_inst(unsigned grid, const GemmArgs& a, hipStream_t stream) {
+    static std::atomic<unsigned long long> attr_done{0};   // per instantiation, one bit per device
+    if (mis_set_lds_attr(reinterpret_cast<const void*>(KERNEL), LDS, attr_done) != MIS_OK) return MIS_ERR_LAUNCH;
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(BLOCK), LDS, stream, a);
     return mis_launch_status();
 }
+template <auto KERNEL, int BLOCK, int LDS>
+Inst inst() { return {&launch_inst<KERNEL, BLOCK, LDS>, BLOCK, LDS}; }
 
-template <int EP>
-int launch_nt_rega_res_ep(const GemmArgs& a, hipStream_t stream) {
-    static std::atomic<unsigned long long> attr_done{0};
-    const int ldsb = 3 * (96 * BK * 3 / 2) * 4 + (192 + 384) * 4;      // the panel (up to three k-blocks) + gamma / beta / head weights
-    if (mis_set_lds_attr(reinterpret_cast<const void*>(&gemm_nt_rega_res_kernel<EP>), ldsb, attr_done) != MIS_OK)
-        return MIS_ERR_LAUNCH;
-    hipLaunchKernelGGL((gemm_nt_rega_res_kernel<EP>), dim3(a.n_blocks_padded), dim3(256), ldsb, stream, a);
-    return mis_launch_status();
+// the epilogue number as a compile-time constant, for the epilogues EPS a family is compiled with
+template <int... EPS, class F>
+Inst for_ep(int ep, F f) {
+    Inst k;
+    ((ep == EPS ? (void)(k = f(std::integral_constant<int, EPS>{})) : (void)0), ...);
+    return k;
 }
 
-int launch_nt_rega(GemmArgs& a, hipStream_t stream) {
-    static const int res_on = getenv("MIS_GEMM_REGA_RES") ? atoi(getenv("MIS_GEMM_REGA_RES")) : 1;
-    if (res_on && a.K3 <= 96) {
-        // persistent: two workgroups per CU, split evenly over the column panels; a walker's four waves want >= 2 slabs each
-        a.tiles_n = a.N / 96;
-        long long walkers = 512 / a.tiles_n;
-        const long long slabs = mis_cdiv(a.M, 32);
-        if (walkers > mis_cdiv(slabs, 8)) walkers = mis_cdiv(slabs, 8);
-        if (walkers < 1) walkers = 1;
-        a.tiles_m = (int)walkers;
-        a.n_blocks = (unsigned)(walkers * a.tiles_n);
-        a.n_blocks_padded = (unsigned)(mis_cdiv((long long)a.n_blocks, MIS_NUM_XCD) * MIS_NUM_XCD);
-        a.KS = 1;
-        if (a.ep == EP_NONE) return launch_nt_rega_res_ep<EP_NONE>(a, stream);
-        if (a.ep == EP_GELU_FWD) return launch_nt_rega_res_ep<EP_GELU_FWD>(a, stream);
-        if (a.ep == EP_GELU_BWD) return launch_nt_rega_res_ep<EP_GELU_BWD>(a, stream);
-        if (a.ep == EP_RESIDUAL_LN) return launch_nt_rega_res_ep<EP_RESIDUAL_LN>(a, stream);
-        if (a.ep == EP_LNHEAD) return launch_nt_rega_res_ep<EP_LNHEAD>(a, stream);
-        return launch_nt_rega_res_ep<EP_RESIDUAL>(a, stream);
+enum { F_NT, F_NT_SHORT, F_NT_REGA, F_NT_REGA_RES, F_TN, F_TN_REG };
+
+struct Plan {
+    int status = MIS_OK;
+    int family = F_NT, bm = 0, bn = 0, ep = EP_NONE, prec = 0, waves = 4;      // the instantiation ...
+    Inst k;                                                                    // ... its launcher, block and LDS bytes
+    unsigned grid = 0, reduce_blocks = 0;      // reduce_blocks > 0: gemm_reduce_kernel follows
+    int slices = 1;      // k slices a workspace must hold (KS, kchunk and the tile counts are in the GemmArgs)
+};
+
+template <int BMT, int BN, int EP, int PREC, int NW>
+Inst nt_k() { return inst<&gemm_nt_kernel<BMT, BN, EP, PREC, NW>, NW * 64, NtCfg<BMT, BN, PREC, NW>::LDS_BYTES>(); }
+
+// MIS_GEMM_NT_WAVES=8: eight waves per workgroup for the 64 x 96 tiles of the pre-split form.  Measured (profiles/r06_gemm_nt_waves.txt):
+// alone, most shapes gain 3 .. 10 % (six waves per SIMD hide the k-step's DMA wait and barrier), the split-K shapes lose 4 .. 11 %,
+// 1305 -> 1293 us over the 20 shapes of a step; INSIDE the step, where the weight-gradient and teacher streams already fill the idle
+// issue slots, it is 0.1 .. 0.15 ms SLOWER (SwinUnet 18.69 -> 18.80 ms, cross teaching 18.95 -> 19.12).  Default: four.
+int nt_waves(const Plan& p) {
+    static const int w = knob(getenv("MIS_GEMM_NT_WAVES"), 4);
+    return (w == 8 && p.bm == 64 && p.bn == 96 && p.prec == 2 && p.ep != EP_LNHEAD) ? 8 : 4;
+}
+
+template <int BMT, int BN>
+Inst nt_inst(const Plan& p) {
+    return for_ep<EP_NONE, EP_GELU_FWD, EP_GELU_BWD, EP_RESIDUAL>(p.ep, [&](auto e) {
+        constexpr int EP = decltype(e)::value;
+        if (p.waves == 8) {
+            if constexpr (BMT == 64 && BN == 96) return p.prec == 2 ? nt_k<BMT, BN, EP, 2, 8>() : Inst{};
+            return Inst{};
+        }
+        return p.prec == 2 ? nt_k<BMT, BN, EP, 2, 4>() : p.prec == 1 ? nt_k<BMT, BN, EP, 1, 4>() : nt_k<BMT, BN, EP, 0, 4>();
+    });
+}
+
+template <int BN>
+Inst nt_short_inst(const Plan& p) {
+    return for_ep<EP_NONE, EP_GELU_FWD, EP_GELU_BWD, EP_RESIDUAL>(p.ep, [&](auto e) {
+        constexpr int EP = decltype(e)::value;
+        return p.prec ? inst<&gemm_nt_short_kernel<BN, EP, 1>, 256, NsCfg<BN>::LDS_BYTES>()
+                      : inst<&gemm_nt_short_kernel<BN, EP, 0>, 256, NsCfg<BN>::LDS_BYTES>();
+    });
+}
+
+Inst instantiation(const Plan& p) {
+    constexpr int TN_REG_LDS = 2 * 36 * 64 * 16 + 2 * 64 * 6 * 4;
+    constexpr int REGA_RES_LDS = 3 * (96 * BK * 3 / 2) * 4 + (192 + 384) * 4;      // the panel (up to three k-blocks) + gamma / beta / head weights
+    switch (p.family) {
+    case F_NT:
+        if (p.ep == EP_LNHEAD) {      // the fused tail of FinalPatchExpand_X4: 64 x 96 tiles on fp32 B, four waves
+            if (p.bm != 64 || p.bn != 96 || p.prec > 1 || p.waves != 4) return {};
+            return p.prec ? nt_k<64, 96, EP_LNHEAD, 1, 4>() : nt_k<64, 96, EP_LNHEAD, 0, 4>();
+        }
+        if (p.bn != 96 && p.bn != 128) return {};
+        if (p.bm == 64) return p.bn == 96 ? nt_inst<64, 96>(p) : nt_inst<64, 128>(p);
+        if (p.bm == BM) return p.bn == 96 ? nt_inst<BM, 96>(p) : nt_inst<BM, 128>(p);
+        return {};
+    case F_NT_SHORT:
+        return p.bn == 96 ? nt_short_inst<96>(p) : p.bn == 128 ? nt_short_inst<128>(p) : Inst{};
+    case F_NT_REGA:      // (no fused tail here: EP_LNHEAD needs the resident-panel form)
+        return for_ep<EP_NONE, EP_GELU_FWD, EP_GELU_BWD, EP_RESIDUAL, EP_RESIDUAL_LN>(p.ep, [](auto e) {
+            return inst<&gemm_nt_rega_kernel<96, decltype(e)::value>, 256, rega_lds_bytes<96>()>();
+        });
+    case F_NT_REGA_RES:
+        return for_ep<EP_NONE, EP_GELU_FWD, EP_GELU_BWD, EP_RESIDUAL, EP_LNHEAD, EP_RESIDUAL_LN>(p.ep, [](auto e) {
+            return inst<&gemm_nt_rega_res_kernel<decltype(e)::value>, 256, REGA_RES_LDS>();
+        });
+    case F_TN:
+        return p.bn == 96 ? inst<&gemm_tn_kernel<96>, 256, 0>() : p.bn == 128 ? inst<&gemm_tn_kernel<128>, 256, 0>() : Inst{};
+    case F_TN_REG:
+        return p.prec ? inst<&gemm_tn_reg_kernel<1>, 256, TN_REG_LDS>() : inst<&gemm_tn_reg_kernel<0>, 256, TN_REG_LDS>();
     }
-    if (a.ep == EP_LNHEAD) return MIS_ERR_UNSUPPORTED;
-    a.tiles_n = a.N / 96;
-    a.tiles_m = (int)mis_cdiv(a.M, 128);
-    const long long nb = (long long)a.tiles_n * a.tiles_m;
+    return {};
+}
+
+// ---- the steps every plan shares
+// one linear, XCD-remapped index over (k-slice, tile): slices of a tile and tiles of a row-block are spread over all XCDs in
+// contiguous runs (a 1-tile split-K dW must not land on a single XCD)
+int fill_grid(GemmArgs& a, long long tiles_n, long long tiles_m, long long slices) {
+    const long long nb = tiles_n * tiles_m * slices;
     if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
+    a.tiles_n = (int)tiles_n; a.tiles_m = (int)tiles_m;
     a.n_blocks = (unsigned)nb;
     a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    a.KS = 1;
+    return MIS_OK;
+}
+
+// split-K: `ks` slices asked for, each a whole number of k-steps of `step` rows -- KS = the slices that are not empty
+void split_k(GemmArgs& a, int ks, int step) {
+    a.kchunk = (int)(mis_cdiv(mis_cdiv(a.K, ks), step) * step);
+    a.KS = (int)mis_cdiv(a.K, a.kchunk);
+}
+
+// grid, instantiation and reduce launch of a plan whose tiles and slices are in `a`
+Plan finish(Plan p, const GemmArgs& a, unsigned grid) {
+    p.grid = grid;
+    p.k = instantiation(p);
+    if (a.KS > 1 && p.family != F_NT_REGA)      // (the register-A kernel is never split: its KS carries the grid of the walkers)
+        p.reduce_blocks = (unsigned)(mis_cdiv((long long)a.M * a.N, 32) + (a.dbias ? mis_cdiv(a.M, 32) : 0));
+    return p;
+}
+
+int split_k3(int K) { return (int)(mis_cdiv(K, BK) * BK); }
+
+// ---- the plans
+// NT, staged operands: B fp32 (split per tile under bf16x3) or pre-split planes (a.K3 > 0); the short-contraction kernel where it serves
+Plan plan_nt(GemmArgs& a) {
+    Plan p;
+    int ks;
+    if (a.K3) {
+        p.prec = 2;
+        if (!b3_choice(a.M, a.N, a.K, p.bm, p.bn, ks)) { p.status = MIS_ERR_UNSUPPORTED; return p; }
+    } else {
+        p.prec = gemm_bf3() ? 1 : 0;
+        nt_rule(a.M, a.N, a.K, p.bm, ks);
+        p.bn = nt_tile_n(a.N);
+        if (a.ep == EP_LNHEAD) { p.bm = 64; p.bn = 96; }      // the fused tail: a 96-wide tile is one (p1, p2), its rows whole tokens
+    }
+    if (a.ex_P && ks != 1) { p.status = MIS_ERR_UNSUPPORTED; return p; }      // the pixel-shuffle store has no split-K form
+    p.slices = ks;
+    a.KS = 1; a.kchunk = a.K;
+    if (ks > 1) split_k(a, ks, BK);
+    if (nt_short(a)) {
+        p.family = F_NT_SHORT; p.bm = 64; p.ep = a.ep;
+        p.status = fill_grid(a, mis_cdiv(a.N, p.bn), mis_cdiv(a.M, 64), 1);
+    } else {
+        p.ep = a.KS > 1 ? EP_NONE : a.ep;      // split-K slices write raw partials (the epilogue runs in gemm_reduce_kernel)
+        p.waves = nt_waves(p);
+        p.status = fill_grid(a, mis_cdiv(a.N, p.bn), mis_cdiv(a.M, p.bm), a.KS);
+    }
+    return finish(p, a, a.n_blocks_padded);
+}
+
+// NT, A straight from HBM into the MFMA registers, natural-order planes: the resident-panel form (K <= 96) or the walking one
+Plan plan_nt_rega(GemmArgs& a) {
+    Plan p;
+    p.bm = 128; p.bn = 96; p.ep = a.ep; p.prec = 2;
+    if (!nt_rega_shape(a.M, a.N, a.K) || (a.ex_P && a.ep != EP_LNHEAD) || !a.vec4) { p.status = MIS_ERR_UNSUPPORTED; return p; }
+    a.KS = 1; a.kchunk = a.K;
+    static const int res_on = knob(getenv("MIS_GEMM_REGA_RES"), 1);
+    if (res_on && a.K3 <= 96) {
+        // persistent: two workgroups per CU, split evenly over the column panels; a walker's four waves want >= 2 slabs each
+        p.family = F_NT_REGA_RES;
+        const long long tiles_n = a.N / 96, slabs = mis_cdiv(a.M, 32);
+        long long walkers = 512 / tiles_n;
+        if (walkers > mis_cdiv(slabs, 8)) walkers = mis_cdiv(slabs, 8);
+        if (walkers < 1) walkers = 1;
+        p.status = fill_grid(a, tiles_n, walkers, 1);
+        return finish(p, a, a.n_blocks_padded);
+    }
+    p.family = F_NT_REGA;
+    p.status = fill_grid(a, a.N / 96, mis_cdiv(a.M, 128), 1);
     // persistent above three workgroups per CU (KS carries the grid size; MIS_GEMM_REGA_WALK=0: one workgroup per tile)
-    static const int walk = getenv("MIS_GEMM_REGA_WALK") ? atoi(getenv("MIS_GEMM_REGA_WALK")) : 768;
+    static const int walk = knob(getenv("MIS_GEMM_REGA_WALK"), 768);
     a.KS = (walk > 0 && a.n_blocks_padded > (unsigned)walk) ? walk / MIS_NUM_XCD * MIS_NUM_XCD : (int)a.n_blocks_padded;
-    if (a.ep == EP_NONE) return launch_nt_rega_ep<96, EP_NONE>(a, stream);
-    if (a.ep == EP_GELU_FWD) return launch_nt_rega_ep<96, EP_GELU_FWD>(a, stream);
-    if (a.ep == EP_GELU_BWD) return launch_nt_rega_ep<96, EP_GELU_BWD>(a, stream);
-    if (a.ep == EP_RESIDUAL_LN) return launch_nt_rega_ep<96, EP_RESIDUAL_LN>(a, stream);
-    return launch_nt_rega_ep<96, EP_RESIDUAL>(a, stream);
+    return finish(p, a, (unsigned)a.KS);
+}
+
+// TN: the register-only form (`reg`: tn_reg_ok for these operands) or the staged one
+Plan plan_tn(GemmArgs& a, bool reg) {
+    Plan p;
+    if (reg) {
+        p.family = F_TN_REG; p.bm = p.bn = RT; p.prec = gemm_bf3_tn() ? 1 : 0;
+        p.slices = tn_reg_slices(a.M, a.N, a.K);
+        split_k(a, p.slices, 16);      // rows per workgroup slice: a multiple of 16 (4 waves x groups of 4 rows)
+        p.status = fill_grid(a, a.N / RT, a.M / RT, a.KS);
+    } else {
+        p.family = F_TN; p.bm = p.bn = tn_tile(a.M, a.N);
+        p.slices = tn_slices(a.M, a.N, a.K);
+        a.KS = 1; a.kchunk = a.K;
+        if (p.slices > 1) split_k(a, p.slices, BK);
+        p.status = fill_grid(a, mis_cdiv(a.N, p.bn), mis_cdiv(a.M, p.bm), a.KS);
+    }
+    return finish(p, a, a.n_blocks_padded);
+}
+
+// ---- running and printing a plan
+int run(const Plan& p, const GemmArgs& a, hipStream_t stream) {
+    if (p.status) return p.status;
+    if (!p.k.launch) return MIS_ERR_UNSUPPORTED;
+    const int st = p.k.launch(p.grid, a, stream);
+    if (st || !p.reduce_blocks) return st;
+    hipLaunchKernelGGL(gemm_reduce_kernel, dim3(p.reduce_blocks), dim3(256), 0, stream, a);
+    return mis_launch_status();
+}
+
+// a split contraction needs its partials' workspace: `cols` floats per row and slice
+bool workspace_short(const Plan& p, const GemmArgs& a, long long cols, const float* workspace, long long workspace_bytes) {
+    return p.reduce_blocks && (!workspace || workspace_bytes < (long long)p.slices * a.M * cols * 4);
+}
+
+int run_nt(GemmArgs& a, const float* workspace, long long workspace_bytes, hipStream_t stream, bool rega = false) {
+    const Plan p = rega ? plan_nt_rega(a) : plan_nt(a);
+    if (p.status) return p.status;
+    if (workspace_short(p, a, a.N, workspace, workspace_bytes)) return MIS_ERR_WORKSPACE;
+    return run(p, a, stream);
+}
+
+// the kernel as rocprofv3 prints it minus the anonymous-namespace prefix: for bench.py's attribution
+int plan_name(const Plan& p, char* name, int name_len) {
+    if (p.status) return p.status;
+    switch (p.family) {
+    case F_NT: snprintf(name, name_len, "gemm_nt_kernel<%d, %d, %d, %d, %d>", p.bm, p.bn, p.ep, p.prec, p.waves); break;
+    case F_NT_SHORT: snprintf(name, name_len, "gemm_nt_short_kernel<%d, %d, %d>", p.bn, p.ep, p.prec); break;
+    case F_NT_REGA: snprintf(name, name_len, "gemm_nt_rega_kernel<%d, %d>", p.bn, p.ep); break;
+    case F_NT_REGA_RES: snprintf(name, name_len, "gemm_nt_rega_res_kernel<%d>", p.ep); break;
+    case F_TN: snprintf(name, name_len, "gemm_tn_kernel<%d>", p.bn); break;
+    default: snprintf(name, name_len, "gemm_tn_reg_kernel<%d>", p.prec); break;
+    }
+    return MIS_OK;
+}
+
+// the GemmArgs of a query: what the plans read of a launch with float4-addressable operands
+GemmArgs query_args(long long M, long long N, int K, int epilogue, bool planes) {
+    GemmArgs a{};
+    a.M = (int)M; a.N = (int)N; a.K = K; a.KS = 1; a.kchunk = K; a.ep = epilogue; a.vec4 = N % 4 == 0;
+    if (planes) a.K3 = split_k3(K);
+    return a;
+}
+
+bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// operands of the fused epilogues 1 .. 3: present, then float4-addressable
+int check_epilogue(int epilogue, const float* E1, long long lde1, const float* C2, long long ldc2, const float* rowscale,
+                   long long rows_per_scale, int N) {
+    if (epilogue == EP_GELU_FWD ? (!C2 || ldc2 < N) : (!E1 || lde1 < N)) return MIS_ERR_ARG;
+    if (epilogue == EP_RESIDUAL && rowscale && rows_per_scale <= 0) return MIS_ERR_ARG;
+    if (epilogue == EP_GELU_FWD ? (ldc2 % 4 || !a16(C2)) : (lde1 % 4 || !a16(E1))) return MIS_ERR_UNSUPPORTED;
+    return MIS_OK;
+}
+
+// the pixel-shuffle store and, with gamma, the fused LayerNorm + head tail of the expand forms
+void set_expand(GemmArgs& a, int H, int W, int P, int c) { a.ex_P = P; a.ex_H = H; a.ex_W = W; a.ex_c = c; }
+void set_ln_head(GemmArgs& a, const float* gamma, const float* beta, const float* head_w, int NC, float eps, float* mean,
+                 float* rstd, float* logits, long long logits_bs) {
+    a.ep = EP_LNHEAD;
+    a.ln_g = gamma; a.ln_b = beta; a.head_w = head_w; a.ln_mean = mean; a.ln_rstd = rstd; a.logits = logits;
+    a.logits_bs = logits_bs; a.head_nc = NC; a.ln_eps = eps;
 }
 
 }  // namespace
 
 int mis_split_precision_mask() { return gemm_bf3_state().load(std::memory_order_relaxed); }
 
-// Arithmetic of the nn.Linear GEMMs: mask bit 0 = forward / dX (NT), bit 1 = dW (TN, widths % 96 == 0) as bf16x3 split
-// products on v_mfma_f32_16x16x32_bf16 (exact 3-way split of the fp32 operands, six piece products, fp32 accumulation: error
-// against float64 no larger than the fp32 MFMA kernels'); 0 = v_mfma_f32_16x16x4_f32 everywhere.  Returns the previous mask;
-// mask < 0 only queries.
+// the split-precision mask of the nn.Linear GEMMs (above); returns the previous mask, mask < 0 only queries
 extern "C" int mis_gemm_set_split_precision(int mask) {
     const int prev = gemm_bf3_state().load();
     if (mask >= 0) gemm_bf3_state().store(mask & 7);
     return prev;
 }
 
-// NT kernel instantiation mis_gemm / mis_gemm_ex run this shape with (16-byte aligned operands, N % 4 == 0), as
-// rocprofv3 prints it minus the anonymous-namespace prefix: for bench.py's attribution
+// ---- queries: the plan of a launch, printed or measured
+// NT kernel instantiation mis_gemm / mis_gemm_ex run this shape with (16-byte aligned operands, N % 4 == 0)
 extern "C" int mis_gemm_nt_kernel_name(int M, int N, int K, int epilogue, char* name, int name_len) {
     if (M <= 0 || N <= 0 || K <= 0 || !name || name_len <= 0) return MIS_ERR_ARG;
-    GemmArgs a{};
-    a.M = M; a.N = N; a.K = K; a.vec4 = N % 4 == 0; a.KS = pick_ks(M, N, K, 0);
-    const int bn = nt_tile_n(N);
-    if (nt_short(a)) snprintf(name, name_len, "gemm_nt_short_kernel<%d, %d, %d>", bn, epilogue, gemm_bf3() ? 1 : 0);
-    else snprintf(name, name_len, "gemm_nt_kernel<%d, %d, %d, %d, 4>", nt_tile_m(M, N, K), bn, a.KS > 1 ? 0 : epilogue, gemm_bf3() ? 1 : 0);
-    return MIS_OK;
+    GemmArgs a = query_args(M, N, K, epilogue, false);
+    return plan_name(plan_nt(a), name, name_len);
 }
 
-// ... and the instantiation mis_gemm_nt_split runs it with
-extern "C" int mis_gemm_nt_split_kernel_name(int M, int N, int K, int epilogue, char* name, int name_len) {
-    if (M <= 0 || N <= 0 || K <= 0 || !name || name_len <= 0) return MIS_ERR_ARG;
-    int bm, bn, ks;
-    if (!b3_choice(M, N, K, bm, bn, ks)) return MIS_ERR_UNSUPPORTED;
-    const int ep = ks > 1 ? 0 : epilogue;
-    snprintf(name, name_len, "gemm_nt_kernel<%d, %d, %d, 2, %d>", bm, bn, ep, (bm == 64 && bn == 96 && ep != EP_LNHEAD && nt_eight_waves()) ? 8 : 4);
-    return MIS_OK;
-}
-static int split_k3(int K);
-// ... on natural-order planes (layout 1): the register-A kernel
+// ... the instantiation mis_gemm_nt_split runs it with; on natural-order planes (layout 1): the register-A kernel
 extern "C" int mis_gemm_nt_split_layout_kernel_name(int M, int N, int K, int epilogue, int layout, char* name, int name_len) {
-    if (!layout) return mis_gemm_nt_split_kernel_name(M, N, K, epilogue, name, name_len);
     if (M <= 0 || N <= 0 || K <= 0 || !name || name_len <= 0) return MIS_ERR_ARG;
-    if (!nt_rega_shape(M, N, K)) return MIS_ERR_UNSUPPORTED;
-    static const int res_on = getenv("MIS_GEMM_REGA_RES") ? atoi(getenv("MIS_GEMM_REGA_RES")) : 1;
-    if (res_on && split_k3(K) <= 96) snprintf(name, name_len, "gemm_nt_rega_res_kernel<%d>", epilogue);
-    else snprintf(name, name_len, "gemm_nt_rega_kernel<96, %d>", epilogue);
-    return MIS_OK;
+    GemmArgs a = query_args(M, N, K, epilogue, true);
+    return plan_name(layout ? plan_nt_rega(a) : plan_nt(a), name, name_len);
+}
+extern "C" int mis_gemm_nt_split_kernel_name(int M, int N, int K, int epilogue, char* name, int name_len) {
+    return mis_gemm_nt_split_layout_kernel_name(M, N, K, epilogue, 0, name, name_len);
 }
 
-// TN kernel mis_gemm(trans = 1) / mis_gemm_dw run this shape with (operands as the callers pass them: row strides in
-// floats, base pointers), as rocprofv3 prints it minus the anonymous-namespace prefix: for bench.py's attribution
+// ... and the kernel of the expand forms: mis_gemm_expand (ln_head = 0) / mis_gemm_expand_ln_head (1) on fp32 B (planes = 0),
+// mis_gemm_nt_split with ex_P on staged planes (1), mis_gemm_expand_ln_head_split on natural-order planes (2).
+// MIS_ERR_UNSUPPORTED where the entry point refuses the shape or no entry point takes that pair.
+extern "C" int mis_gemm_expand_kernel_name(int B, int H, int W, int K, int P, int c, int ln_head, int planes, char* name, int name_len) {
+    if (B <= 0 || H <= 0 || W <= 0 || K <= 0 || P <= 0 || c <= 0 || planes < 0 || planes > 2 || !name || name_len <= 0) return MIS_ERR_ARG;
+    const long long M = (long long)B * H * W, N = (long long)P * P * c;
+    if (K % 4 || c % 16 || (ln_head && c != 96) || M * N * 4 >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    if (planes && (ln_head ? planes == 1 || split_k3(K) > 96 : planes == 2)) return MIS_ERR_UNSUPPORTED;
+    GemmArgs a = query_args(M, N, K, ln_head ? EP_LNHEAD : EP_NONE, planes != 0);
+    set_expand(a, H, W, P, c);
+    const Plan p = planes == 2 ? plan_nt_rega(a) : plan_nt(a);
+    if (!p.status && !p.k.launch) return MIS_ERR_UNSUPPORTED;
+    return plan_name(p, name, name_len);
+}
+
+// TN kernel mis_gemm(trans = 1) / mis_gemm_dw run this shape with (operands as the callers pass them)
 extern "C" int mis_gemm_tn_kernel_name(const float* A, long long lda, const float* B, long long ldb, const float* C,
                                        long long ldc, int M, int N, int K, char* name, int name_len) {
     if (M <= 0 || N <= 0 || K <= 0 || !name || name_len <= 0) return MIS_ERR_ARG;
-    if (tn_reg_ok(A, lda, B, ldb, C, ldc, M, N, K) && (long long)K * lda * 4 < (1LL << 31) && (long long)K * ldb * 4 < (1LL << 31))
-        snprintf(name, name_len, "gemm_tn_reg_kernel<%d>", gemm_bf3_tn() ? 1 : 0);
-    else snprintf(name, name_len, "gemm_tn_kernel<%d>", tn_tile(M, N));
-    return MIS_OK;
+    GemmArgs a = query_args(M, N, K, EP_NONE, false);
+    return plan_name(plan_tn(a, tn_reg_ok(A, lda, B, ldb, C, ldc, M, N, K)), name, name_len);
 }
 
-extern "C" long long mis_gemm_workspace_bytes(int M, int N, int K, int trans) {
+// bytes of the partials of a split contraction: slices of [M][cols] floats.  trans: the pointers are not known here, so either TN form
+static long long partials_bytes(int M, int N, int K, int trans, long long cols) {
     if (M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;
-    int ks = pick_ks(M, N, K, trans);
-    if (trans && M % RT == 0 && N % RT == 0) { const int kr = tn_reg_slices(M, N, K); if (kr > ks) ks = kr; }   // either TN form
-    return ks > 1 ? (long long)ks * M * N * 4 : 0;
+    GemmArgs a = query_args(M, N, K, EP_NONE, false);
+    int ks = trans ? plan_tn(a, false).slices : plan_nt(a).slices;
+    if (trans && M % RT == 0 && N % RT == 0) { const int kr = plan_tn(a, true).slices; if (kr > ks) ks = kr; }
+    return ks > 1 ? (long long)ks * M * cols * 4 : 0;
+}
+extern "C" long long mis_gemm_workspace_bytes(int M, int N, int K, int trans) { return partials_bytes(M, N, K, trans, N); }
+extern "C" long long mis_gemm_dw_workspace_bytes(int M, int N, int K) { return partials_bytes(M, N, K, 1, N + 1LL); }
+extern "C" long long mis_gemm_nt_split_workspace_bytes(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;
+    GemmArgs a = query_args(M, N, K, EP_NONE, true);
+    const Plan p = plan_nt(a);
+    return (!p.status && p.slices > 1) ? (long long)p.slices * M * N * 4 : 0;
 }
 
-// mis_gemm (NT form only) with a fused epilogue, v = A.B^T + bias:
-//   epilogue 1  C = v, C2 = gelu(v)                      Mlp.fc1 + GELU (reference ...sys.py:14-15,20-21): the
-//                                                        pre-activation stays for the backward, the GELU pass is gone;
-//                                                        C NULL: only C2 (a forward nobody differentiates)
-//   epilogue 2  C = v * gelu'(E1)                        dX of Mlp.fc2 straight into the gradient of fc1's output
-//   epilogue 3  C = E1 + rowscale[m / rows_per_scale] * v  proj / fc2 + DropPath + residual add (:276, :281);
-//                                                        rowscale NULL = 1
-// E1 / C2 are [M][N] views with their own row strides.  accumulate is not supported here.
-extern "C" int mis_gemm_ex(const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc,
-                           const float* bias, int M, int N, int K, int epilogue, const float* E1, long long lde1,
-                           float* C2, long long ldc2, const float* rowscale, long long rows_per_scale,
-                           float* workspace, long long workspace_bytes, hipStream_t stream) {
-    if (!A || !B || (!C && epilogue != EP_GELU_FWD) || M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;      // epilogue 1: C may be NULL
-    if (epilogue < EP_GELU_FWD || epilogue > EP_RESIDUAL) return MIS_ERR_ARG;
-    if (epilogue == EP_GELU_FWD ? (!C2 || ldc2 < N) : (!E1 || lde1 < N)) return MIS_ERR_ARG;
-    if (epilogue == EP_RESIDUAL && rowscale && rows_per_scale <= 0) return MIS_ERR_ARG;
-    if (!a16(A) || !a16(B) || lda % 4 || ldb % 4 || K % 4) return MIS_ERR_UNSUPPORTED;
-    // the fused epilogues live in the float4 (LDS-staged) epilogue
-    if (N % 4 || ldc % 4 || !a16(C) || (bias && !a16(bias))) return MIS_ERR_UNSUPPORTED;
-    if (epilogue == EP_GELU_FWD ? (ldc2 % 4 || !a16(C2)) : (lde1 % 4 || !a16(E1))) return MIS_ERR_UNSUPPORTED;
-    if ((long long)M * lda * 4 >= (1LL << 31) || (long long)N * ldb * 4 >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
-    GemmArgs a{A, lda, B, ldb, C, ldc, bias, workspace, M, N, K, 1, K, 0};
-    a.ex_P = 0;
-    a.ep = epilogue; a.E1 = E1; a.lde1 = lde1; a.C2 = C2; a.ldc2 = ldc2; a.rowscale = rowscale; a.rps = rows_per_scale;
-    a.vec4 = 1;
-    a.KS = pick_ks(M, N, K, 0);
-    if (a.KS > 1) {
-        if (!workspace || workspace_bytes < (long long)a.KS * M * N * 4) return MIS_ERR_WORKSPACE;
-        a.kchunk = (int)(mis_cdiv(mis_cdiv(K, a.KS), BK) * BK);
-        a.KS = (int)mis_cdiv(K, a.kchunk);
-    }
-    const int bn = nt_tile_n(N);
-    a.tiles_n = (int)mis_cdiv(N, bn);
-    a.tiles_m = (int)mis_cdiv(M, BM);
-    const long long nb = (long long)a.tiles_n * a.tiles_m * a.KS;
-    if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    int st = bn == 96 ? launch_nt<96>(a, stream) : launch_nt<128>(a, stream);
-    if (st) return st;
-    if (a.KS > 1)
-        hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)mis_cdiv((long long)M * N, 32)), dim3(256), 0, stream, a);
-    return mis_launch_status();
+// 1: mis_gemm_nt_split runs this shape on the register-A kernel, which reads the planes in the NATURAL element order
+// (mis_gemm_split_*_layout with natural = 1, mis_gemm_nt_split_layout with layout = 1); 0: the staged kernels' order
+extern "C" int mis_gemm_nt_split_natural(int M, int N, int K) {
+    return (M > 0 && N > 0 && K > 0 && nt_rega_shape(M, N, K)) ? 1 : 0;
+}
+
+// ---- fp32 B
+// TN: C[M,N] (+)= A[K,M]^T . B[K,N] and, with a.dbias, dbias[M] (+)= the column sums of A.  `cols` floats of workspace per row
+// and slice (N, or N + 1 with the column sums behind the partials).  slices != NULL: no finishing launch -- a split
+// contraction leaves its partials in the workspace and *slices = KS
+static int run_tn(GemmArgs& a, long long cols, float* workspace, long long workspace_bytes, hipStream_t stream, int* slices) {
+    Plan p = plan_tn(a, tn_reg_ok(a.A, a.lda, a.B, a.ldb, a.C, a.ldc, a.M, a.N, a.K));
+    if (p.status) return p.status;
+    if (workspace_short(p, a, cols, workspace, workspace_bytes)) return MIS_ERR_WORKSPACE;
+    if (a.KS > 1 && cols > a.N) a.wsb = workspace + (long long)a.KS * a.M * a.N;
+    if (slices) p.reduce_blocks = 0;
+    const int st = run(p, a, stream);
+    if (!st && slices && a.KS > 1) *slices = a.KS;
+    return st;
 }
 
 extern "C" int mis_gemm(const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc,
@@ -2275,142 +2351,61 @@ extern "C" int mis_gemm(const float* A, long long lda, const float* B, long long
     const long long rowsA = trans ? K : M, rowsB = trans ? K : N;
     if (rowsA * lda * 4 >= (1LL << 31) || rowsB * ldb * 4 >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
     GemmArgs a{A, lda, B, ldb, C, ldc, bias, workspace, M, N, K, 1, K, accumulate};
-    a.ex_P = 0;
-    a.ep = EP_NONE;
-    a.vec4 = (!trans && N % 4 == 0 && ldc % 4 == 0 && a16(C) && (!bias || a16(bias))) ? 1 : 0;
-    if (trans && tn_reg_ok(A, lda, B, ldb, C, ldc, M, N, K)) {
-        a.dbias = nullptr;
-        tn_reg_plan(a);
-        if (a.KS > 1 && (!workspace || workspace_bytes < (long long)a.KS * M * N * 4)) return MIS_ERR_WORKSPACE;
-        const int st = launch_tn_reg(a, stream);
-        if (st) return st;
-        if (a.KS > 1)
-            hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)mis_cdiv((long long)M * N, 32)), dim3(256), 0, stream, a);
-        return mis_launch_status();
-    }
-    a.KS = pick_ks(M, N, K, trans);
-    if (a.KS > 1) {
-        if (!workspace || workspace_bytes < (long long)a.KS * M * N * 4) return MIS_ERR_WORKSPACE;
-        a.kchunk = (int)(mis_cdiv(mis_cdiv(K, a.KS), BK) * BK);
-        a.KS = (int)mis_cdiv(K, a.kchunk);
-    }
-    const int bt = trans ? tn_tile(M, N) : 0;
-    const int bn = trans ? bt : nt_tile_n(N), bm = trans ? bt : BM;
-    a.tiles_n = (int)mis_cdiv(N, bn);
-    a.tiles_m = (int)mis_cdiv(M, bm);
-    // one linear, XCD-remapped index over (k-slice, tile): slices of a tile and tiles of a row-block are
-    // spread over all XCDs in contiguous runs (a 1-tile split-K dW must not land on a single XCD)
-    const long long nb = (long long)a.tiles_n * a.tiles_m * a.KS;
-    if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    int st;
-    if (trans) {
-        if (bt == 96)
-            hipLaunchKernelGGL(gemm_tn_kernel<96>, dim3(a.n_blocks_padded), dim3(256), 0, stream, a);
-        else
-            hipLaunchKernelGGL(gemm_tn_kernel<128>, dim3(a.n_blocks_padded), dim3(256), 0, stream, a);
-        st = mis_launch_status();
-    } else {
-        st = bn == 96 ? launch_nt<96>(a, stream) : launch_nt<128>(a, stream);
-    }
-    if (st) return st;
-    if (a.KS > 1) {
-        hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)mis_cdiv((long long)M * N, 32)), dim3(256), 0, stream, a);
-    }
-    return mis_launch_status();
+    if (trans) return run_tn(a, N, workspace, workspace_bytes, stream, nullptr);
+    a.vec4 = (N % 4 == 0 && ldc % 4 == 0 && a16(C) && (!bias || a16(bias))) ? 1 : 0;
+    return run_nt(a, workspace, workspace_bytes, stream);
 }
 
-// Weight and bias gradient of nn.Linear in one pass over dy (reference swin_transformer_unet_skip_expand_decoder_sys.py
-// :14,16,107,109 through autograd): dW[M,N] (+)= dy[K,M]^T . x[K,N], db[M] (+)= sum_k dy[k][m] -- mis_gemm's TN form
-// whose first tile column also sums the dy tile it staged (mis_colsum's partial + final launches are gone).
-// Deterministic: fixed slices, fixed-order sums.  workspace >= mis_gemm_dw_workspace_bytes(M, N, K).
-extern "C" long long mis_gemm_dw_workspace_bytes(int M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;
-    int ks = pick_ks(M, N, K, 1);
-    if (M % RT == 0 && N % RT == 0) { const int kr = tn_reg_slices(M, N, K); if (kr > ks) ks = kr; }             // either TN form
-    return ks > 1 ? (long long)ks * M * (N + 1) * 4 : 0;
+// mis_gemm (NT form only) with a fused epilogue (the contracts of the entry points: include/mis_hip.h); epilogue 1: C may be
+// NULL (only C2 = gelu(v): a forward nobody differentiates).  accumulate is not supported here.
+extern "C" int mis_gemm_ex(const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc,
+                           const float* bias, int M, int N, int K, int epilogue, const float* E1, long long lde1,
+                           float* C2, long long ldc2, const float* rowscale, long long rows_per_scale,
+                           float* workspace, long long workspace_bytes, hipStream_t stream) {
+    if (!A || !B || (!C && epilogue != EP_GELU_FWD) || M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;      // epilogue 1: C may be NULL
+    if (epilogue < EP_GELU_FWD || epilogue > EP_RESIDUAL) return MIS_ERR_ARG;
+    if (const int st = check_epilogue(epilogue, E1, lde1, C2, ldc2, rowscale, rows_per_scale, N)) return st;
+    if (!a16(A) || !a16(B) || lda % 4 || ldb % 4 || K % 4) return MIS_ERR_UNSUPPORTED;
+    // the fused epilogues live in the float4 (LDS-staged) epilogue
+    if (N % 4 || ldc % 4 || !a16(C) || (bias && !a16(bias))) return MIS_ERR_UNSUPPORTED;
+    if ((long long)M * lda * 4 >= (1LL << 31) || (long long)N * ldb * 4 >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    GemmArgs a{A, lda, B, ldb, C, ldc, bias, workspace, M, N, K, 1, K, 0};
+    a.ep = epilogue; a.E1 = E1; a.lde1 = lde1; a.C2 = C2; a.ldc2 = ldc2; a.rowscale = rowscale; a.rps = rows_per_scale;
+    a.vec4 = 1;
+    return run_nt(a, workspace, workspace_bytes, stream);
 }
 
-// reduce != 0: dW / db are finished here (gemm_reduce_kernel).  reduce == 0 (mis_gemm_dw_parts): a split contraction leaves its
-// partials in `workspace` -- [KS][M][N] floats, then [KS][M] column sums of dy -- and *slices = KS (0: the contraction was not
-// split and dW / db are complete); the caller sums the slices later (mis_colsum_batch), off the launch sequence of the backward.
+// Weight and bias gradient of nn.Linear in one pass over dy: mis_gemm's TN form whose first tile column also sums the dy tile
+// it staged.  slices == NULL: dW / db are finished here.  Otherwise (mis_gemm_dw_parts, db may be NULL): a split contraction
+// leaves its partials in `workspace` -- [KS][M][N] floats, then [KS][M] column sums of dy -- and *slices = KS (0: not split, dW /
+// db are complete); the caller sums the slices later (mis_colsum_batch), off the launch sequence of the backward.
 static int gemm_dw_impl(const float* dy, long long lddy, const float* x, long long ldx, float* dW, long long lddw,
                         float* db, int M, int N, int K, int accumulate, float* workspace, long long workspace_bytes,
-                        hipStream_t stream, int reduce, int* slices) {
-    if (!dy || !x || !dW || (!db && reduce) || M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;
+                        hipStream_t stream, int* slices) {
+    if (!dy || !x || !dW || (!db && !slices) || M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;
     if (!a16(dy) || !a16(x) || lddy % 4 || ldx % 4 || M % 4 || N % 4) return MIS_ERR_UNSUPPORTED;
     GemmArgs a{dy, lddy, x, ldx, dW, lddw, nullptr, workspace, M, N, K, 1, K, accumulate};
-    a.ex_P = 0;
-    a.ep = EP_NONE;
-    a.vec4 = 0;
     a.dbias = db;
     a.dbias_acc = accumulate;
     if (slices) *slices = 0;
-    const unsigned red_blocks = (unsigned)(mis_cdiv((long long)M * N, 32) + (db ? mis_cdiv(M, 32) : 0));
-    if (tn_reg_ok(dy, lddy, x, ldx, dW, lddw, M, N, K) && (long long)K * lddy * 4 < (1LL << 31) && (long long)K * ldx * 4 < (1LL << 31)) {
-        tn_reg_plan(a);
-        if (a.KS > 1) {
-            if (!workspace || workspace_bytes < (long long)a.KS * M * (N + 1) * 4) return MIS_ERR_WORKSPACE;
-            a.wsb = workspace + (long long)a.KS * M * N;
-        }
-        const int st = launch_tn_reg(a, stream);
-        if (st) return st;
-        if (a.KS > 1) {
-            if (!reduce) { *slices = a.KS; return MIS_OK; }
-            hipLaunchKernelGGL(gemm_reduce_kernel, dim3(red_blocks), dim3(256), 0, stream, a);
-        }
-        return mis_launch_status();
-    }
-    a.KS = pick_ks(M, N, K, 1);
-    if (a.KS > 1) {
-        if (!workspace || workspace_bytes < (long long)a.KS * M * (N + 1) * 4) return MIS_ERR_WORKSPACE;
-        a.kchunk = (int)(mis_cdiv(mis_cdiv(K, a.KS), BK) * BK);
-        a.KS = (int)mis_cdiv(K, a.kchunk);
-        a.wsb = workspace + (long long)a.KS * M * N;
-    }
-    const int bt = tn_tile(M, N);
-    a.tiles_n = (int)mis_cdiv(N, bt);
-    a.tiles_m = (int)mis_cdiv(M, bt);
-    const long long nb = (long long)a.tiles_n * a.tiles_m * a.KS;
-    if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    if (bt == 96)
-        hipLaunchKernelGGL(gemm_tn_kernel<96>, dim3(a.n_blocks_padded), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(gemm_tn_kernel<128>, dim3(a.n_blocks_padded), dim3(256), 0, stream, a);
-    const int st = mis_launch_status();
-    if (st) return st;
-    if (a.KS > 1) {
-        if (!reduce) { *slices = a.KS; return MIS_OK; }
-        hipLaunchKernelGGL(gemm_reduce_kernel, dim3(red_blocks), dim3(256), 0, stream, a);
-    }
-    return mis_launch_status();
+    return run_tn(a, N + 1LL, workspace, workspace_bytes, stream, slices);
 }
 
 extern "C" int mis_gemm_dw(const float* dy, long long lddy, const float* x, long long ldx, float* dW, long long lddw,
                            float* db, int M, int N, int K, int accumulate, float* workspace, long long workspace_bytes,
                            hipStream_t stream) {
-    return gemm_dw_impl(dy, lddy, x, ldx, dW, lddw, db, M, N, K, accumulate, workspace, workspace_bytes, stream, 1, nullptr);
+    return gemm_dw_impl(dy, lddy, x, ldx, dW, lddw, db, M, N, K, accumulate, workspace, workspace_bytes, stream, nullptr);
 }
 
-// mis_gemm_dw without its finishing launch (db may be NULL: weight gradient only).  *slices > 0: `workspace` (the caller's own
-// until the sums have run) holds `*slices` partial matrices [M][N] followed by `*slices` partial rows [M] of the bias gradient;
-// dW / db are untouched (`accumulate` is the final sum's business).  *slices == 0: dW / db are complete.
 extern "C" int mis_gemm_dw_parts(const float* dy, long long lddy, const float* x, long long ldx, float* dW, long long lddw,
                                  float* db, int M, int N, int K, int accumulate, float* workspace, long long workspace_bytes,
                                  int* slices, hipStream_t stream) {
     if (!slices) return MIS_ERR_ARG;
-    return gemm_dw_impl(dy, lddy, x, ldx, dW, lddw, db, M, N, K, accumulate, workspace, workspace_bytes, stream, 0, slices);
+    return gemm_dw_impl(dy, lddy, x, ldx, dW, lddw, db, M, N, K, accumulate, workspace, workspace_bytes, stream, slices);
 }
 
-// ---- the NT form with a pre-split B operand ----------------------------------------------------------------------------
-// mis_gemm_split_b cuts B [N][K] (an nn.Linear weight, or its transpose for the data gradient) into the bf16 piece planes once;
-// mis_gemm_nt_split is mis_gemm (trans = 0) / mis_gemm_ex / mis_gemm_expand on them: same products, same sums, same results
-// bit for bit as the bf16x3 kernels that split B per tile -- minus two thirds of their vector instructions.
-static int split_k3(int K) { return (int)(mis_cdiv(K, BK) * BK); }
-
+// ---- the NT form with a pre-split B operand: mis_gemm_split_b cuts B [N][K] into the bf16 piece planes once, mis_gemm_nt_split
+// is mis_gemm (trans = 0) / mis_gemm_ex / mis_gemm_expand on them, bit for bit the bf16x3 kernels that split B per tile
 extern "C" long long mis_gemm_split_bytes(int N, int K) {
     if (N <= 0 || K <= 0) return MIS_ERR_ARG;
     return 3LL * N * split_k3(K) * 2;
@@ -2457,12 +2452,6 @@ extern "C" long long mis_gemm_split_job(void* job, const float* B, long long ldb
     return mis_gemm_split_job_layout(job, B, ldb, N, K, B3, first, 0);
 }
 
-// 1: mis_gemm_nt_split runs this shape on the register-A kernel, which reads the planes in the NATURAL element order
-// (mis_gemm_split_*_layout with natural = 1, mis_gemm_nt_split_layout with layout = 1); 0: the staged kernels' order
-extern "C" int mis_gemm_nt_split_natural(int M, int N, int K) {
-    return (M > 0 && N > 0 && K > 0 && nt_rega_shape(M, N, K)) ? 1 : 0;
-}
-
 extern "C" int mis_gemm_split_batch(const void* jobs, int n, long long units, hipStream_t stream) {
     if (!jobs || n <= 0 || units <= 0 || units > 0x7fffffffLL) return MIS_ERR_ARG;
     hipLaunchKernelGGL(gemm_split_batch_kernel, dim3((unsigned)units), dim3(256), 0, stream,
@@ -2470,71 +2459,46 @@ extern "C" int mis_gemm_split_batch(const void* jobs, int n, long long units, hi
     return mis_launch_status();
 }
 
-extern "C" long long mis_gemm_nt_split_workspace_bytes(int M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;
-    int bm, bn, ks;
-    if (!b3_choice(M, N, K, bm, bn, ks)) return 0;
-    return ks > 1 ? (long long)ks * M * N * 4 : 0;
+// the A operand and the planes of a pre-split launch: float4 rows, 32-bit offsets
+static int check_split_operands(const float* A, long long lda, const void* B3, long long M, long long N, int K) {
+    if (!a16(A) || !a16(B3) || lda % 4 || K % 4) return MIS_ERR_UNSUPPORTED;
+    if (M * lda * 4 >= (1LL << 31) || mis_gemm_split_bytes((int)N, K) >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    return MIS_OK;
+}
+static void set_planes(GemmArgs& a, const void* B3) {
+    a.B3 = B3; a.K3 = split_k3(a.K); a.b3_plane = (unsigned)((long long)a.N * a.K3 * 2);
 }
 
-// C [M][N] (+)= A [M][K] . B^T + bias with B given as mis_gemm_split_b's planes.  epilogue 0: plain (accumulate allowed);
-// 1 .. 3: the fused epilogues of mis_gemm_ex (E1 / C2 / rowscale as there); ex_P > 0: the pixel-shuffle store of
-// mis_gemm_expand (C dense [B H P W P][ex_c], M = B ex_H ex_W, N = P P ex_c, no bias, no epilogue, no split-K).
-// workspace >= mis_gemm_nt_split_workspace_bytes(M, N, K).  MIS_ERR_UNSUPPORTED (also: contractions the rule leaves to the
-// short-contraction kernel): the caller uses the fp32-B entry points.
-static int gemm_nt_split_impl(const float* A, long long lda, const void* B3, float* C, long long ldc, const float* bias,
-                              int M, int N, int K, int accumulate, int epilogue, const float* E1, long long lde1,
-                              float* C2, long long ldc2, const float* rowscale, long long rows_per_scale, int ex_H,
-                              int ex_W, int ex_P, int ex_c, float* workspace, long long workspace_bytes,
-                              hipStream_t stream, int layout) {
+// C [M][N] (+)= A [M][K] . B^T + bias with B given as mis_gemm_split_b's planes in the layout `layout` (0: the staged kernels'
+// order; 1: natural order -- the register-A kernels).  epilogue 0: plain (accumulate allowed); 1 .. 3: as mis_gemm_ex; ex_P > 0:
+// the pixel-shuffle store of mis_gemm_expand (no bias, no epilogue, no split-K).  MIS_ERR_UNSUPPORTED (also: contractions the
+// rule leaves to the short-contraction kernel): the caller uses the fp32-B entry points.
+extern "C" int mis_gemm_nt_split_layout(const float* A, long long lda, const void* B3, float* C, long long ldc, const float* bias,
+                                        int M, int N, int K, int accumulate, int epilogue, const float* E1, long long lde1,
+                                        float* C2, long long ldc2, const float* rowscale, long long rows_per_scale, int ex_H,
+                                        int ex_W, int ex_P, int ex_c, float* workspace, long long workspace_bytes, int layout,
+                                        hipStream_t stream) {
     if (!A || !B3 || (!C && epilogue != EP_GELU_FWD) || M <= 0 || N <= 0 || K <= 0) return MIS_ERR_ARG;
     if (epilogue < EP_NONE || epilogue > EP_RESIDUAL) return MIS_ERR_ARG;
-    if (!a16(A) || !a16(B3) || lda % 4 || K % 4) return MIS_ERR_UNSUPPORTED;
-    if ((long long)M * lda * 4 >= (1LL << 31) || mis_gemm_split_bytes(N, K) >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    if (const int st = check_split_operands(A, lda, B3, M, N, K)) return st;
     GemmArgs a{A, lda, nullptr, 0, C, ldc, bias, workspace, M, N, K, 1, K, accumulate};
-    a.B3 = B3; a.K3 = split_k3(K); a.b3_plane = (unsigned)((long long)N * a.K3 * 2);
-    a.ex_P = 0;
+    set_planes(a, B3);
     a.ep = epilogue;
     a.vec4 = (N % 4 == 0 && ldc % 4 == 0 && a16(C) && (!bias || a16(bias))) ? 1 : 0;
     if (ex_P > 0) {
         if (epilogue != EP_NONE || bias || accumulate) return MIS_ERR_ARG;
         if (ex_H <= 0 || ex_W <= 0 || ex_c <= 0 || ex_c % 16 || M % (ex_H * ex_W) || N != ex_P * ex_P * ex_c) return MIS_ERR_UNSUPPORTED;
         if ((long long)M * N * 4 >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
-        a.ex_P = ex_P; a.ex_H = ex_H; a.ex_W = ex_W; a.ex_c = ex_c; a.ldc = N;
+        set_expand(a, ex_H, ex_W, ex_P, ex_c);
+        a.ldc = N;
     } else if (epilogue != EP_NONE) {
         if (accumulate) return MIS_ERR_ARG;
-        if (epilogue == EP_GELU_FWD ? (!C2 || ldc2 < N) : (!E1 || lde1 < N)) return MIS_ERR_ARG;
-        if (epilogue == EP_RESIDUAL && rowscale && rows_per_scale <= 0) return MIS_ERR_ARG;
+        if (const int st = check_epilogue(epilogue, E1, lde1, C2, ldc2, rowscale, rows_per_scale, N)) return st;
         if (!a.vec4) return MIS_ERR_UNSUPPORTED;
-        if (epilogue == EP_GELU_FWD ? (ldc2 % 4 || !a16(C2)) : (lde1 % 4 || !a16(E1))) return MIS_ERR_UNSUPPORTED;
         a.E1 = E1; a.lde1 = lde1; a.C2 = C2; a.ldc2 = ldc2; a.rowscale = rowscale; a.rps = rows_per_scale;
     }
-    if (layout) {
-        // natural-order planes: only the register-A kernel reads them (the caller asked mis_gemm_nt_split_natural)
-        if (!nt_rega_shape(M, N, K) || a.ex_P || !a.vec4) return MIS_ERR_UNSUPPORTED;
-        return launch_nt_rega(a, stream);
-    }
-    int bm, bn, ks;
-    if (!b3_choice(M, N, K, bm, bn, ks)) return MIS_ERR_UNSUPPORTED;
-    if (a.ex_P && ks != 1) return MIS_ERR_UNSUPPORTED;
-    a.KS = ks;
-    a.bm_force = bm;
-    if (a.KS > 1) {
-        if (!workspace || workspace_bytes < (long long)a.KS * M * N * 4) return MIS_ERR_WORKSPACE;
-        a.kchunk = (int)(mis_cdiv(mis_cdiv(K, a.KS), BK) * BK);
-        a.KS = (int)mis_cdiv(K, a.kchunk);
-    }
-    a.tiles_n = (int)mis_cdiv(N, bn);
-    a.tiles_m = (int)mis_cdiv(M, BM);
-    const long long nb = (long long)a.tiles_n * a.tiles_m * a.KS;
-    if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    const int st = bn == 96 ? launch_nt<96>(a, stream) : launch_nt<128>(a, stream);
-    if (st) return st;
-    if (a.KS > 1)
-        hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)mis_cdiv((long long)M * N, 32)), dim3(256), 0, stream, a);
-    return mis_launch_status();
+    // natural-order planes: only the register-A kernel reads them (the caller asked mis_gemm_nt_split_natural)
+    return run_nt(a, workspace, workspace_bytes, stream, layout != 0);
 }
 
 extern "C" int mis_gemm_nt_split(const float* A, long long lda, const void* B3, float* C, long long ldc, const float* bias,
@@ -2542,25 +2506,11 @@ extern "C" int mis_gemm_nt_split(const float* A, long long lda, const void* B3, 
                                  float* C2, long long ldc2, const float* rowscale, long long rows_per_scale, int ex_H,
                                  int ex_W, int ex_P, int ex_c, float* workspace, long long workspace_bytes,
                                  hipStream_t stream) {
-    return gemm_nt_split_impl(A, lda, B3, C, ldc, bias, M, N, K, accumulate, epilogue, E1, lde1, C2, ldc2, rowscale, rows_per_scale,
-                              ex_H, ex_W, ex_P, ex_c, workspace, workspace_bytes, stream, 0);
+    return mis_gemm_nt_split_layout(A, lda, B3, C, ldc, bias, M, N, K, accumulate, epilogue, E1, lde1, C2, ldc2, rowscale,
+                                    rows_per_scale, ex_H, ex_W, ex_P, ex_c, workspace, workspace_bytes, 0, stream);
 }
 
-// mis_gemm_nt_split on planes in the layout `layout` (0: as mis_gemm_nt_split; 1: natural order, shapes for which
-// mis_gemm_nt_split_natural says 1 -- the register-A kernel: A straight from HBM into the MFMA operand registers, round 6)
-extern "C" int mis_gemm_nt_split_layout(const float* A, long long lda, const void* B3, float* C, long long ldc, const float* bias,
-                                        int M, int N, int K, int accumulate, int epilogue, const float* E1, long long lde1,
-                                        float* C2, long long ldc2, const float* rowscale, long long rows_per_scale, int ex_H,
-                                        int ex_W, int ex_P, int ex_c, float* workspace, long long workspace_bytes, int layout,
-                                        hipStream_t stream) {
-    return gemm_nt_split_impl(A, lda, B3, C, ldc, bias, M, N, K, accumulate, epilogue, E1, lde1, C2, ldc2, rowscale, rows_per_scale,
-                              ex_H, ex_W, ex_P, ex_c, workspace, workspace_bytes, stream, layout);
-}
-
-// mis_gemm_expand_ln_head on natural-order planes of the expand weight (round 6): the persistent resident-panel register-A kernel
-// -- K <= 96, c = 96, the 16 (p1, p2) column panels of FinalPatchExpand_X4 stay in LDS, a wave's accumulators ARE token rows of
-// the shuffled tensor, so LayerNorm and the output head run in registers.  Same arguments otherwise.  MIS_ERR_UNSUPPORTED:
-// mis_gemm_nt_split_natural(M, N, K) is 0, K > 96, c != 96, NC outside 2 .. 4.
+// mis_gemm_expand_ln_head on natural-order planes of the expand weight: the resident-panel register-A kernel (K <= 96, c = 96)
 extern "C" int mis_gemm_expand_ln_head_split(const float* x, long long lda, const void* B3, float* out, int B, int H, int Wd, int K,
                                              int P, int c, const float* gamma, const float* beta, const float* head_w, int NC,
                                              float eps, float* mean, float* rstd, float* logits, long long logits_bs,
@@ -2570,23 +2520,19 @@ extern "C" int mis_gemm_expand_ln_head_split(const float* x, long long lda, cons
     if (c != 96 || NC < 2 || NC > 4) return MIS_ERR_UNSUPPORTED;
     const long long M = (long long)B * H * Wd, N = (long long)P * P * c;
     if (M * 4 >= (1LL << 31) || !nt_rega_shape((int)M, (int)N, K) || split_k3(K) > 96) return MIS_ERR_UNSUPPORTED;
-    if (!a16(x) || !a16(B3) || lda % 4 || K % 4 || (out && !a16(out))) return MIS_ERR_UNSUPPORTED;
-    if (M * lda * 4 >= (1LL << 31) || mis_gemm_split_bytes((int)N, K) >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    if (out && !a16(out)) return MIS_ERR_UNSUPPORTED;
+    if (const int st = check_split_operands(x, lda, B3, M, N, K)) return st;
     if (logits_bs < (long long)NC * H * P * Wd * P) return MIS_ERR_ARG;
     GemmArgs a{x, lda, nullptr, 0, out, N, nullptr, nullptr, (int)M, (int)N, K, 1, K, 0};
-    a.B3 = B3; a.K3 = split_k3(K); a.b3_plane = (unsigned)(N * a.K3 * 2);
-    a.ex_P = P; a.ex_H = H; a.ex_W = Wd; a.ex_c = c; a.vec4 = 1;
-    a.ep = EP_LNHEAD;
-    a.ln_g = gamma; a.ln_b = beta; a.head_w = head_w; a.ln_mean = mean; a.ln_rstd = rstd; a.logits = logits;
-    a.logits_bs = logits_bs; a.head_nc = NC; a.ln_eps = eps;
-    return launch_nt_rega(a, stream);
+    set_planes(a, B3);
+    set_expand(a, H, Wd, P, c);
+    set_ln_head(a, gamma, beta, head_w, NC, eps, mean, rstd, logits, logits_bs);
+    a.vec4 = 1;
+    return run_nt(a, nullptr, 0, stream, true);
 }
 
-// proj / fc2 of a 96-channel Swin block with everything up to the next LayerNorm in the epilogue (register-A kernels, natural-order
-// planes): X = E1 + rowscale[m / rows_per_scale] * (A . B^T + bias) -> X (the block's residual stream, row stride ldx), and
-// Y = LayerNorm(X) * gamma + beta (row stride ldy), mean / rstd [M] for the backward -- `x = shortcut + self.drop_path(x)` then
-// `self.norm2(x)` (reference ...sys.py:276-281) or the next block's `norm1` (:244-250).  N must be 96 (a row = one tile row).
-// MIS_ERR_UNSUPPORTED: mis_gemm_nt_split_natural(M, 96, K) is 0 or an operand is not float4-addressable.
+// proj / fc2 of a 96-channel Swin block with the residual add and the next LayerNorm in the register-A kernels' epilogue (N = 96:
+// a row is one tile row)
 extern "C" int mis_gemm_nt_residual_ln(const float* A, long long lda, const void* B3, const float* bias, int M, int N, int K,
                                        const float* E1, long long lde1, const float* rowscale, long long rows_per_scale,
                                        float* X, long long ldx, const float* gamma, const float* beta, float eps, float* Y,
@@ -2594,50 +2540,40 @@ extern "C" int mis_gemm_nt_residual_ln(const float* A, long long lda, const void
     if (!A || !B3 || !E1 || !X || !gamma || !beta || !Y || !mean || !rstd || M <= 0 || K <= 0) return MIS_ERR_ARG;
     if (rowscale && rows_per_scale <= 0) return MIS_ERR_ARG;
     if (N != 96 || !nt_rega_shape(M, N, K)) return MIS_ERR_UNSUPPORTED;
-    if (!a16(A) || !a16(B3) || !a16(E1) || !a16(X) || !a16(Y) || (bias && !a16(bias)) || lda % 4 || lde1 % 4 || ldx % 4 || ldy % 4 || K % 4)
-        return MIS_ERR_UNSUPPORTED;
-    if ((long long)M * lda * 4 >= (1LL << 31) || mis_gemm_split_bytes(N, K) >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    if (!a16(E1) || !a16(X) || !a16(Y) || (bias && !a16(bias)) || lde1 % 4 || ldx % 4 || ldy % 4) return MIS_ERR_UNSUPPORTED;
+    if (const int st = check_split_operands(A, lda, B3, M, N, K)) return st;
     GemmArgs a{A, lda, nullptr, 0, X, ldx, bias, nullptr, M, N, K, 1, K, 0};
-    a.B3 = B3; a.K3 = split_k3(K); a.b3_plane = (unsigned)((long long)N * a.K3 * 2);
-    a.ex_P = 0; a.vec4 = 1;
+    set_planes(a, B3);
+    a.vec4 = 1;
     a.ep = EP_RESIDUAL_LN;
     a.E1 = E1; a.lde1 = lde1; a.C2 = Y; a.ldc2 = ldy; a.rowscale = rowscale; a.rps = rowscale ? rows_per_scale : 1;
     a.ln_g = gamma; a.ln_b = beta; a.ln_mean = mean; a.ln_rstd = rstd; a.ln_eps = eps;
-    return launch_nt_rega(a, stream);
+    return run_nt(a, nullptr, 0, stream, true);
 }
 
-// nn.Linear of PatchExpand / FinalPatchExpand_X4 fused with their pixel shuffle (reference
-// swin_transformer_unet_skip_expand_decoder_sys.py:373-380, :401-408): out[(b, h*P + p1, w*P + p2)][c] =
-// sum_k x[(b, h, w)][k] * W[(p1*P + p2)*c + c'][k] -- the GEMM's epilogue writes the shuffled layout, so the expanded
-// token-major tensor never exists in forward.  x [B*H*W][K] (row stride lda), W [P*P*c][K], out [B*H*P*W*P][c] dense.
-// No bias (the reference's expand layers have none), no split-K: MIS_ERR_UNSUPPORTED when mis_gemm would split
-// this shape (callers then use mis_gemm + mis_token_rearrange) or c % 16 != 0.
+// ---- the expand forms on fp32 B
+// x [B*H*W][K] (row stride lda), W [P*P*c][K]: float4 rows, 32-bit offsets, an output the pixel-shuffle store can index
+static int check_expand_operands(const float* x, long long lda, const float* W, long long ldb, long long M, long long N, int K) {
+    if (!a16(x) || !a16(W) || lda % 4 || ldb % 4 || K % 4) return MIS_ERR_UNSUPPORTED;
+    if (M * lda * 4 >= (1LL << 31) || N * ldb * 4 >= (1LL << 31) || M * N * 4 >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    return MIS_OK;
+}
+
+// nn.Linear of PatchExpand / FinalPatchExpand_X4 with their pixel shuffle as the GEMM's store: out[(b, h*P + p1, w*P + p2)][c] =
+// sum_k x[(b, h, w)][k] * W[(p1*P + p2)*c + c'][k].  No bias, no split-K (the plan refuses a shape mis_gemm would split).
 extern "C" int mis_gemm_expand(const float* x, long long lda, const float* W, long long ldb, float* out, int B, int H,
                                int Wd, int K, int P, int c, hipStream_t stream) {
     if (!x || !W || !out || B <= 0 || H <= 0 || Wd <= 0 || K <= 0 || P <= 0 || c <= 0) return MIS_ERR_ARG;
     const long long M = (long long)B * H * Wd, N = (long long)P * P * c;
-    if (!a16(x) || !a16(W) || lda % 4 || ldb % 4 || K % 4 || c % 16) return MIS_ERR_UNSUPPORTED;
-    if (M * lda * 4 >= (1LL << 31) || N * ldb * 4 >= (1LL << 31) || M * N * 4 >= (1LL << 31))
-        return MIS_ERR_UNSUPPORTED;
-    if (pick_ks((int)M, (int)N, K, 0) != 1) return MIS_ERR_UNSUPPORTED;
+    if (c % 16) return MIS_ERR_UNSUPPORTED;
+    if (const int st = check_expand_operands(x, lda, W, ldb, M, N, K)) return st;
     GemmArgs a{x, lda, W, ldb, out, N, nullptr, nullptr, (int)M, (int)N, K, 1, K, 0};
-    a.ex_P = P; a.ex_H = H; a.ex_W = Wd; a.ex_c = c;
-    const int bn = nt_tile_n((int)N);
-    a.tiles_n = (int)mis_cdiv(N, bn);
-    a.tiles_m = (int)mis_cdiv(M, BM);
-    const long long nb = (long long)a.tiles_n * a.tiles_m;
-    if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    return bn == 96 ? launch_nt<96>(a, stream) : launch_nt<128>(a, stream);
+    set_expand(a, H, Wd, P, c);
+    return run_nt(a, nullptr, 0, stream);
 }
 
-// mis_gemm_expand (P x P pixel shuffle, c = 96) with FinalPatchExpand_X4's LayerNorm and the bias-free 1 x 1 output convolution in
-// the GEMM's epilogue (reference swin_transformer_unet_skip_expand_decoder_sys.py:401-409 `x = self.expand(x); rearrange;
-// x = self.norm(x)`, :749-752 `self.output(x)`): per token of the shuffled tensor mean / rstd (saved for the backward, index =
-// token of the shuffled tensor) and logits [B][NC][H P][W P] (batch stride logits_bs floats).  `out` (the shuffled tokens, dense
-// [B H P W P][96]) is what the backward reads; NULL = not kept (a forward nobody differentiates: the EMA teacher).  Same bits as
-// mis_gemm_expand + mis_ln_head_fwd.  MIS_ERR_UNSUPPORTED: c != 96, NC outside 2 .. 4, or a shape mis_gemm_expand refuses.
+// mis_gemm_expand (c = 96) with FinalPatchExpand_X4's LayerNorm and the bias-free output head in the epilogue; `out` NULL: the
+// shuffled tokens are not kept.  Same bits as mis_gemm_expand + mis_ln_head_fwd.
 extern "C" int mis_gemm_expand_ln_head(const float* x, long long lda, const float* W, long long ldb, float* out, int B, int H,
                                        int Wd, int K, int P, int c, const float* gamma, const float* beta, const float* head_w,
                                        int NC, float eps, float* mean, float* rstd, float* logits, long long logits_bs,
@@ -2646,21 +2582,12 @@ extern "C" int mis_gemm_expand_ln_head(const float* x, long long lda, const floa
         return MIS_ERR_ARG;
     if (c != 96 || NC < 2 || NC > 4) return MIS_ERR_UNSUPPORTED;
     const long long M = (long long)B * H * Wd, N = (long long)P * P * c;
-    if (!a16(x) || !a16(W) || lda % 4 || ldb % 4 || K % 4 || (out && !a16(out)) || !a16(gamma) || !a16(beta) || !a16(head_w))
-        return MIS_ERR_UNSUPPORTED;
-    if (M * lda * 4 >= (1LL << 31) || N * ldb * 4 >= (1LL << 31) || M * N * 4 >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    if ((out && !a16(out)) || !a16(gamma) || !a16(beta) || !a16(head_w)) return MIS_ERR_UNSUPPORTED;
+    if (const int st = check_expand_operands(x, lda, W, ldb, M, N, K)) return st;
     if (logits_bs < (long long)NC * H * P * Wd * P) return MIS_ERR_ARG;
-    if (pick_ks((int)M, (int)N, K, 0) != 1) return MIS_ERR_UNSUPPORTED;
     GemmArgs a{x, lda, W, ldb, out, N, nullptr, nullptr, (int)M, (int)N, K, 1, K, 0};
-    a.ex_P = P; a.ex_H = H; a.ex_W = Wd; a.ex_c = c;
-    a.ep = EP_LNHEAD;
-    a.ln_g = gamma; a.ln_b = beta; a.head_w = head_w; a.ln_mean = mean; a.ln_rstd = rstd; a.logits = logits;
-    a.logits_bs = logits_bs; a.head_nc = NC; a.ln_eps = eps;
-    a.tiles_n = (int)(N / 96);
-    a.tiles_m = (int)mis_cdiv(M, 64);
-    const long long nb = (long long)a.tiles_n * a.tiles_m;
-    if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
-    a.n_blocks = (unsigned)nb;
-    a.n_blocks_padded = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-    return gemm_bf3() ? launch_nt_prec<64, 96, EP_LNHEAD, 1>(a, stream) : launch_nt_prec<64, 96, EP_LNHEAD, 0>(a, stream);
+    set_expand(a, H, Wd, P, c);
+    set_ln_head(a, gamma, beta, head_w, NC, eps, mean, rstd, logits, logits_bs);
+    return run_nt(a, nullptr, 0, stream);
 }
+

@@ -25,19 +25,40 @@ def _mat(t):
     return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
 
 
-def _nt_name(L, M, N, K, epilogue):
-    """NT instantiation mis_gemm / mis_gemm_ex pick, as rocprofv3 names it."""
+def _kernel_name(query, *args):
+    """The kernel a launch runs, as rocprofv3 names it: ``query`` is one of the library's ``mis_gemm_*_kernel_name`` entry
+    points, which print the plan the launcher itself runs."""
     buf = ctypes.create_string_buffer(96)
-    _l.check(L.mis_gemm_nt_kernel_name(M, N, K, epilogue, buf, 96), "mis_gemm_nt_kernel_name")
+    _l.check(getattr(_l.load(), query)(*args, buf, 96), query)
     return buf.value.decode()
+
+
+def _nt_name(L, M, N, K, epilogue):
+    """NT instantiation mis_gemm / mis_gemm_ex pick."""
+    return _kernel_name("mis_gemm_nt_kernel_name", M, N, K, epilogue)
 
 
 def _tn_name(L, A, lda, B, ldb, C, ldc, M, N, K):
-    """TN kernel mis_gemm(trans) / mis_gemm_dw pick for these operands, as rocprofv3 names it."""
-    buf = ctypes.create_string_buffer(96)
-    _l.check(L.mis_gemm_tn_kernel_name(_l.ptr(A), lda, _l.ptr(B), ldb, _l.ptr(C), ldc, M, N, K, buf, 96),
-             "mis_gemm_tn_kernel_name")
-    return buf.value.decode()
+    """TN kernel mis_gemm(trans) / mis_gemm_dw pick for these operands."""
+    return _kernel_name("mis_gemm_tn_kernel_name", _l.ptr(A), lda, _l.ptr(B), ldb, _l.ptr(C), ldc, M, N, K)
+
+
+def _prof_begin():
+    """Opens a row of bench.py's live roofline list (``ops.PROFILE``, the same list as ops.conv_fwd; None: not measuring)."""
+    prof = _ops.PROFILE
+    if prof is None:
+        return None
+    e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    e0.record()
+    return prof, e0, e1
+
+
+def _prof_end(row, name, flops, nbytes):
+    """Closes it after the launch: ``name`` is a thunk (a ``_kernel_name`` query), so nothing is asked when nothing is measured."""
+    if row is not None:
+        prof, e0, e1 = row
+        e1.record()
+        prof.append((name(), flops, e0, e1, nbytes))
 
 
 class SplitB:
@@ -110,10 +131,7 @@ def _nt_split(A, b3, C, bias=None, accumulate=False, epilogue=0, E1=None, C2=Non
     ldc2 = _mat(C2)[2] if C2 is not None else 0
     nb = L.mis_gemm_nt_split_workspace_bytes(M, N, K)
     ws = scratch(nb, "gemm") if nb > 0 else None
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     if b3.natural and b3.rows != M:
         raise RuntimeError(f"natural-order planes were cut for {b3.rows} token rows, the GEMM has {M}")
     st = L.mis_gemm_nt_split_layout(_l.ptr(A), lda, _l.ptr(b3.t), _l.ptr(C), ldc, _l.ptr(bias), M, N, K, int(accumulate),
@@ -124,11 +142,8 @@ def _nt_split(A, b3, C, bias=None, accumulate=False, epilogue=0, E1=None, C2=Non
             raise RuntimeError("natural-order planes, but the register-A kernel refuses this call (the staged kernels cannot read them)")
         return False
     _l.check(st, "mis_gemm_nt_split_layout")
-    if prof is not None:
-        e1.record()
-        buf = ctypes.create_string_buffer(96)
-        _l.check(L.mis_gemm_nt_split_layout_kernel_name(M, N, K, int(epilogue), int(b3.natural), buf, 96), "mis_gemm_nt_split_layout_kernel_name")
-        prof.append((buf.value.decode(), 2.0 * M * N * K, e0, e1, 4.0 * (M * K + M * N) + 6.0 * N * K))
+    _prof_end(prof, lambda: _kernel_name("mis_gemm_nt_split_layout_kernel_name", M, N, K, int(epilogue), int(b3.natural)),
+              2.0 * M * N * K, 4.0 * (M * K + M * N) + 6.0 * N * K)
     return True
 
 
@@ -148,21 +163,12 @@ def gemm(A, B, C, bias=None, trans=False, accumulate=False, b3=None):
     assert K == K2 and (Mc, Nc) == (M, N), (A.shape, B.shape, C.shape, trans)
     nb = L.mis_gemm_workspace_bytes(M, N, K, int(trans))
     ws = scratch(nb, "gemm") if nb > 0 else None
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _l.check(L.mis_gemm(_l.ptr(A), lda, _l.ptr(B), ldb, _l.ptr(C), ldc, _l.ptr(bias), M, N, K, int(trans),
                         int(accumulate), _l.ptr(ws), ws.numel() if ws is not None else 0, _l.stream_ptr()),
              "mis_gemm")
-    if prof is not None:   # bench.py's live roofline measurement (same list as ops.conv_fwd)
-        e1.record()
-        # kernel instantiation mis_gemm picks (gemm.hip: tn_tile / nt_tile_n), as rocprofv3 names it
-        if trans:
-            name = _tn_name(L, A, lda, B, ldb, C, ldc, M, N, K)
-        else:
-            name = _nt_name(L, M, N, K, 0)
-        prof.append((name, 2.0 * M * N * K, e0, e1, 4.0 * (M * K + N * K + M * N)))
+    _prof_end(prof, lambda: _tn_name(L, A, lda, B, ldb, C, ldc, M, N, K) if trans else _nt_name(L, M, N, K, 0),
+              2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
 
 
 def set_split_precision(mask):
@@ -180,15 +186,10 @@ def gemm_dw(dy, x, dW, db, accumulate=False):
     assert K == K2 and (Mc, Nc) == (M, N) and db.numel() == M and db.is_contiguous(), (dy.shape, x.shape, dW.shape)
     nb = L.mis_gemm_dw_workspace_bytes(M, N, K)
     ws = scratch(nb, "gemm") if nb > 0 else None
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _l.check(L.mis_gemm_dw(_l.ptr(dy), lddy, _l.ptr(x), ldx, _l.ptr(dW), ldw, _l.ptr(db), M, N, K, int(accumulate),
                            _l.ptr(ws), ws.numel() if ws is not None else 0, _l.stream_ptr()), "mis_gemm_dw")
-    if prof is not None:
-        e1.record()
-        prof.append((_tn_name(L, dy, lddy, x, ldx, dW, ldw, M, N, K), 2.0 * M * N * K, e0, e1, 4.0 * (M * K + N * K + M * N)))
+    _prof_end(prof, lambda: _tn_name(L, dy, lddy, x, ldx, dW, ldw, M, N, K), 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
 
 
 def gemm_dw_parts(dy, x, dW, db, ws, accumulate=False):
@@ -200,17 +201,12 @@ def gemm_dw_parts(dy, x, dW, db, ws, accumulate=False):
     K2, N, ldx = _mat(x)
     Mc, Nc, ldw = _mat(dW)
     assert K == K2 and (Mc, Nc) == (M, N) and (db is None or (db.numel() == M and db.is_contiguous())), (dy.shape, x.shape, dW.shape)
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     slices = ctypes.c_int(0)
     _l.check(L.mis_gemm_dw_parts(_l.ptr(dy), lddy, _l.ptr(x), ldx, _l.ptr(dW), ldw, _l.ptr(db), M, N, K, int(accumulate),
                                  _l.ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, ctypes.byref(slices),
                                  _l.stream_ptr()), "mis_gemm_dw_parts")
-    if prof is not None:
-        e1.record()
-        prof.append((_tn_name(L, dy, lddy, x, ldx, dW, ldw, M, N, K), 2.0 * M * N * K, e0, e1, 4.0 * (M * K + N * K + M * N)))
+    _prof_end(prof, lambda: _tn_name(L, dy, lddy, x, ldx, dW, ldw, M, N, K), 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
     return slices.value
 
 
@@ -298,20 +294,15 @@ def gemm_ex(A, B, C, epilogue, bias=None, E1=None, C2=None, rowscale=None, rows_
     ldc2 = _mat(C2)[2] if C2 is not None else 0
     nb = L.mis_gemm_workspace_bytes(M, N, K, 0)
     ws = scratch(nb, "gemm") if nb > 0 else None
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     st = L.mis_gemm_ex(_l.ptr(A), lda, _l.ptr(B), ldb, _l.ptr(C), ldc, _l.ptr(bias), M, N, K, int(epilogue),
                        _l.ptr(E1), lde1, _l.ptr(C2), ldc2, _l.ptr(rowscale), int(rows_per_scale), _l.ptr(ws),
                        ws.numel() if ws is not None else 0, _l.stream_ptr())
     if st == -2:
         return False
     _l.check(st, "mis_gemm_ex")
-    if prof is not None:
-        e1.record()
-        # (split-K shapes run the plain instantiation + the reduce kernel; the label keeps the requested epilogue)
-        prof.append((_nt_name(L, M, N, K, epilogue), 2.0 * M * N * K, e0, e1, 4.0 * (M * K + N * K + M * N)))
+    # (split-K shapes run the plain instantiation + the reduce kernel, and that is the label)
+    _prof_end(prof, lambda: _nt_name(L, M, N, K, epilogue), 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
     return True
 
 
@@ -327,21 +318,15 @@ def gemm_residual_ln(A, b3, X, E1, gamma, beta, Y, mean, rstd, bias=None, rowsca
     _, _, ldy = _mat(Y)
     if N != 96 or b3.N != 96 or b3.K != K or Mx != M or b3.rows != M:
         return False
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     st = L.mis_gemm_nt_residual_ln(_l.ptr(A), lda, _l.ptr(b3.t), _l.ptr(bias), M, N, K, _l.ptr(E1), lde1, _l.ptr(rowscale),
                                    int(rows_per_scale), _l.ptr(X), ldx, _l.ptr(gamma), _l.ptr(beta), eps, _l.ptr(Y), ldy,
                                    _l.ptr(mean), _l.ptr(rstd), _l.stream_ptr())
     if st == -2:
         return False
     _l.check(st, "mis_gemm_nt_residual_ln")
-    if prof is not None:
-        e1.record()
-        buf = ctypes.create_string_buffer(96)
-        _l.check(L.mis_gemm_nt_split_layout_kernel_name(M, N, K, 5, 1, buf, 96), "mis_gemm_nt_split_layout_kernel_name")
-        prof.append((buf.value.decode(), 2.0 * M * N * K, e0, e1, 4.0 * (M * K + 3 * M * N) + 6.0 * N * K))
+    _prof_end(prof, lambda: _kernel_name("mis_gemm_nt_split_layout_kernel_name", M, N, K, 5, 1), 2.0 * M * N * K,
+              4.0 * (M * K + 3 * M * N) + 6.0 * N * K)
     return True
 
 
@@ -362,17 +347,13 @@ def gemm_expand(x, w, out, B, H, W, P, c, b3=None):
     M, K, lda = _mat(x)
     N, K2, ldb = _mat(w)
     assert K == K2 and M == B * H * W and N == P * P * c and out.is_contiguous() and out.numel() == M * N
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     st = L.mis_gemm_expand(_l.ptr(x), lda, _l.ptr(w), ldb, _l.ptr(out), B, H, W, K, P, c, _l.stream_ptr())
     if st == -2:        # MIS_ERR_UNSUPPORTED: shape outside the fused form
         return False
     _l.check(st, "mis_gemm_expand")
-    if prof is not None:
-        e1.record()
-        prof.append((_nt_name(L, M, N, K, 0), 2.0 * M * N * K, e0, e1, 4.0 * (M * K + N * K + M * N)))
+    _prof_end(prof, lambda: _kernel_name("mis_gemm_expand_kernel_name", B, H, W, K, P, c, 0, 0), 2.0 * M * N * K,
+              4.0 * (M * K + N * K + M * N))
     return True
 
 
@@ -387,19 +368,14 @@ def gemm_expand_ln_head(x, w, out, B, H, W, P, c, gamma, beta, head_w, mean, rst
     NC = logits5.shape[1]
     assert K == K2 and M == B * H * W and N == P * P * c and (out is None or (out.is_contiguous() and out.numel() == M * N))
     assert mean.numel() == M * P * P and rstd.numel() == M * P * P and tuple(head_w.shape) == (NC, c) and head_w.is_contiguous()
-    prof = _ops.PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     if b3 is not None and b3.natural and b3.rows == M and split_active():
         st = L.mis_gemm_expand_ln_head_split(_l.ptr(x), lda, _l.ptr(b3.t), _l.ptr(out), B, H, W, K, P, c, _l.ptr(gamma), _l.ptr(beta),
                                              _l.ptr(head_w), NC, eps, _l.ptr(mean), _l.ptr(rstd), _l.ptr(logits5),
                                              logits5.stride(0), _l.stream_ptr())
         if st == 0:
-            if prof is not None:
-                e1.record()
-                prof.append(("gemm_nt_rega_res_kernel<4>", 2.0 * M * N * K, e0, e1,
-                             4.0 * (M * K + (M * N if out is not None else 0)) + 6.0 * N * K))
+            _prof_end(prof, lambda: _kernel_name("mis_gemm_expand_kernel_name", B, H, W, K, P, c, 1, 2), 2.0 * M * N * K,
+                      4.0 * (M * K + (M * N if out is not None else 0)) + 6.0 * N * K)
             return True
         if st != -2:
             _l.check(st, "mis_gemm_expand_ln_head_split")
@@ -409,10 +385,8 @@ def gemm_expand_ln_head(x, w, out, B, H, W, P, c, gamma, beta, head_w, mean, rst
     if st == -2:
         return False
     _l.check(st, "mis_gemm_expand_ln_head")
-    if prof is not None:
-        e1.record()
-        prec = 1 if (set_split_precision(-1) & 1) else 0
-        prof.append((f"gemm_nt_kernel<64, 96, 4, {prec}, 4>", 2.0 * M * N * K, e0, e1, 4.0 * (M * K + N * K + (M * N if out is not None else 0))))
+    _prof_end(prof, lambda: _kernel_name("mis_gemm_expand_kernel_name", B, H, W, K, P, c, 1, 0), 2.0 * M * N * K,
+              4.0 * (M * K + N * K + (M * N if out is not None else 0)))
     return True
 
 

@@ -622,6 +622,10 @@ int mis_gemm_nt_residual_ln(const float* A, long long lda, const void* B3, const
                             long long ldx, const float* gamma, const float* beta, float eps, float* Y, long long ldy,
                             float* mean, float* rstd, mis_stream_t stream);
 int mis_gemm_nt_split_kernel_name(int M, int N, int K, int epilogue, char* name, int name_len);
+/* the kernel of the expand forms, as a profiler names it: mis_gemm_expand (ln_head = 0) / mis_gemm_expand_ln_head (1) on fp32 B
+ * (planes = 0), mis_gemm_nt_split with ex_P on staged planes (planes = 1, ln_head = 0), mis_gemm_expand_ln_head_split on
+ * natural-order planes (planes = 2, ln_head = 1).  MIS_ERR_UNSUPPORTED where that entry point refuses the shape. */
+int mis_gemm_expand_kernel_name(int B, int H, int W, int K, int P, int c, int ln_head, int planes, char* name, int name_len);
 /* nn.Linear of PatchExpand / FinalPatchExpand_X4 fused with their pixel shuffle
  * 'b h w (p1 p2 c) -> b (h p1) (w p2) c' (swin_transformer_unet_skip_expand_decoder_sys.py:373-380, :401-408):
  * x [B*H*W][K] (row stride lda), W [P*P*c][K] (row stride ldb), out [B*H*P*W*P][c] dense.  No bias.

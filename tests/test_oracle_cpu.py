@@ -277,7 +277,7 @@ def test_c_abi_library_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(mis_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", header, flags=re.S)))
     assert declared, "no declarations parsed from include/mis_hip.h"
     assert declared == set(lib.PROTOTYPES), declared ^ set(lib.PROTOTYPES)
-    assert len(declared) == 187
+    assert len(declared) == 188
     for name in declared:
         assert hasattr(L, name), name
     P, CH, I, LL, ULL = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong
@@ -317,6 +317,85 @@ def test_c_abi_header_compiles_alone():
     for cc, lang in (("cc", "c"), (shutil.which("c++") and "c++" or "cc", "c++")):
         r = subprocess.run([cc, "-fsyntax-only", "-Wall", "-x", lang, path], capture_output=True, text=True)
         assert r.returncode == 0 and not r.stderr, (lang, r.stderr)
+
+
+_EP_FIELD = {"nt": 2, "nt_short": 1, "nt_rega": 1, "nt_rega_res": 0}      # where a kernel name carries its epilogue
+
+
+def _name_group(names):
+    """The answers of one name query for epilogues 0, 1, ..: one string when they agree (an ``e`` in the epilogue's place: answer
+    i carries epilogue i), else the answers joined by ``/``."""
+    def generic(i, s):
+        family, _, rest = s.partition("<")
+        fields, j = rest.rstrip(">").split(","), _EP_FIELD.get(family)
+        if j is None or j >= len(fields) or fields[j] != str(i):
+            return None
+        return family + "<" + ",".join(fields[:j] + ["e"] + fields[j + 1:]) + ">"
+    forms = {generic(i, s) for i, s in enumerate(names)}
+    if len(forms) == 1 and None not in forms:
+        return forms.pop()
+    return names[0] if len(set(names)) == 1 else "/".join(names)
+
+
+def _gemm_dispatch_row(L, mask, M, N, K):
+    """One line of tests/golden/gemm_dispatch.txt: what every dispatch query of csrc/gemm.hip answers for (mask, M, N, K).
+    Kernel names without ``gemm_`` / ``_kernel`` / blanks, a status code where a query refuses; then the byte counts."""
+    import ctypes
+    buf = ctypes.create_string_buffer(96)
+
+    def name(fn, *args):
+        st = fn(*args, buf, 96)
+        return buf.value.decode().replace("gemm_", "").replace("_kernel", "").replace(" ", "") if st == 0 else str(st)
+    nt = _name_group([name(L.mis_gemm_nt_kernel_name, M, N, K, e) for e in range(4)])
+    split = _name_group([name(L.mis_gemm_nt_split_kernel_name, M, N, K, e) for e in range(5)])
+    staged = _name_group([name(L.mis_gemm_nt_split_layout_kernel_name, M, N, K, e, 0) for e in range(5)])
+    natural = _name_group([name(L.mis_gemm_nt_split_layout_kernel_name, M, N, K, e, 1) for e in range(6)])
+    # dW = dy[K, M]^T . x[K, N]: operands on 16-byte boundaries, then 4 bytes off them
+    tn = "/".join(name(L.mis_gemm_tn_kernel_name, 4096 + o, M, 8192 + o, N, 12288 + o, N, M, N, K) for o in (0, 4))
+    nbytes = [L.mis_gemm_workspace_bytes(M, N, K, 0), L.mis_gemm_workspace_bytes(M, N, K, 1), L.mis_gemm_dw_workspace_bytes(M, N, K),
+              L.mis_gemm_nt_split_workspace_bytes(M, N, K), L.mis_gemm_nt_split_natural(M, N, K), L.mis_gemm_split_bytes(N, K)]
+    return f"{mask} {M} {N} {K}|{nt}|{split}|{staged if staged != split else '='}|{natural}|{tn}|" + " ".join(str(int(b)) for b in nbytes)
+
+
+def test_gemm_dispatch_matches_the_recorded_table():
+    """tests/golden/gemm_dispatch.txt was recorded from the library BEFORE its host dispatch became one plan per launch: every
+    kernel-name and workspace query for the Linear shapes of SwinUnet (224 x 224, batches 2 / 24 / 48), of UNETR's ViT and of
+    the GEMM tests, under precision masks 0 and 7.  The queries print the plan the launcher runs, so a tile rule, threshold or
+    slice count that moves shows here, without a GPU.  mis_gemm_expand_kernel_name is newer than the table: pinned by hand."""
+    import ctypes
+    from mis_hip import lib
+    L = lib.load()
+    rows = [r for r in open(os.path.join(GOLD, "gemm_dispatch.txt")).read().splitlines() if r and not r.startswith("#")]
+    assert len(rows) > 300
+    buf = ctypes.create_string_buffer(96)
+
+    def expand(B, H, W, K, P, c, ln_head, planes):
+        st = L.mis_gemm_expand_kernel_name(B, H, W, K, P, c, ln_head, planes, buf, 96)
+        return buf.value.decode() if st == 0 else st
+    prev = L.mis_gemm_set_split_precision(-1)
+    try:
+        for want in rows:
+            mask, M, N, K = (int(v) for v in want.split("|")[0].split())
+            L.mis_gemm_set_split_precision(mask)
+            assert _gemm_dispatch_row(L, mask, M, N, K) == want
+        for mask, p in ((0, 0), (7, 1)):
+            L.mis_gemm_set_split_precision(mask)
+            # FinalPatchExpand_X4 at 24 images: the pixel-shuffle store keeps it off the short-contraction kernel, whose name the
+            # profile row used to carry; on staged planes K < 97 stays with the fp32-B path; (1, 1) / (0, 2): no such entry point
+            assert expand(24, 56, 56, 96, 4, 96, 0, 0) == f"gemm_nt_kernel<64, 128, 0, {p}, 4>"
+            assert expand(24, 56, 56, 96, 4, 96, 1, 0) == f"gemm_nt_kernel<64, 96, 4, {p}, 4>"
+            assert expand(24, 56, 56, 96, 4, 96, 0, 1) == -2 and expand(24, 56, 56, 96, 4, 96, 1, 1) == -2 and expand(24, 56, 56, 96, 4, 96, 0, 2) == -2
+            natural = L.mis_gemm_nt_split_natural(24 * 56 * 56, 16 * 96, 96)
+            assert natural == (1 if mask else 0)
+            assert expand(24, 56, 56, 96, 4, 96, 1, 2) == ("gemm_nt_rega_res_kernel<4>" if natural else -2)
+            assert expand(24, 56, 56, 192, 4, 96, 1, 2) == -2           # K > 96: the panel does not stay resident
+            # PatchExpand of the decoder (P = 2) on staged planes: the launch mis_gemm_nt_split_kernel_name names
+            assert L.mis_gemm_nt_split_kernel_name(24 * 28 * 28, 384, 192, 0, buf, 96) == 0
+            staged = buf.value.decode()
+            assert expand(24, 28, 28, 192, 2, 96, 0, 1) == staged and staged.startswith("gemm_nt_kernel<")
+            assert expand(24, 28, 28, 192, 2, 100, 0, 0) == -2 and expand(0, 28, 28, 192, 2, 96, 0, 0) == -1
+    finally:
+        L.mis_gemm_set_split_precision(prev)
 
 
 def test_c_abi_header_parser_refuses_what_it_does_not_know():
