@@ -1,4 +1,4 @@
-// Building blocks shared by the fused loss tails (loss_tail.hip, uamt_tail.hip, ict.hip, dct.hip, triple_tail.hip) and
+// Building blocks shared by the fused loss tails (loss_tail.hip, uamt_tail.hip, ict.hip, dct.hip, triple_tail.hip, fixmatch.hip) and
 // the stand-alone Dice operator (losses.hip).  Every tail has the same three stages: pass 1 leaves fixed-order partial
 // sums per workgroup, a one-workgroup finalize sums them in double and writes the scalars and the per-class Dice
 // gradient coefficients, pass 2 writes dlogits.  What is here is the half every tail shares, CE + Dice on the labeled

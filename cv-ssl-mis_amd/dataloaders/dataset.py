@@ -160,6 +160,8 @@ class RandomGenerator:
 def augment_batch(pool, indices, gen, recs=None, out=None):
     """One launch: slices ``indices`` of ``pool`` -> (image [B,1,h,w] f32, label [B,h,w] u8) on the device.
     ``recs``: pinned uint8 staging tensor of >= B records (allocated if None); ``out``: reusable output pair."""
+    if hasattr(gen, "augment"):            # a transform of more than one launch (WeakStrongAugment)
+        return gen.augment(pool, indices, recs=recs, out=out)
     L = _l.load()
     B = len(indices)
     h, w = gen.output_size
@@ -176,6 +178,80 @@ def augment_batch(pool, indices, gen, recs=None, out=None):
     _l.check(L.mis_augment2d(_l.ptr(pool.img), _l.ptr(pool.lab), _l.ptr(dev), B, h, w, _l.ptr(out[0]), _l.ptr(out[1]),
                              _l.stream_ptr()), "mis_augment2d")
     return out
+
+
+class _Resize:
+    """``zoom(.., order=0)`` to ``output_size`` alone (MisAug2D mode 0)."""
+
+    def __init__(self, output_size):
+        self.output_size = output_size
+
+    def fill(self, rec, pool, idx):
+        H, W = pool.shapes[idx]
+        rec["img_off"] = rec["lab_off"] = pool.offsets[idx]
+        rec["H"], rec["W"] = H, W
+
+
+class _RotFlip(_Resize):
+    """``random_rot_flip`` (MisAug2D mode 1) with the reference's draws, on slices that already have the output size."""
+
+    def fill(self, rec, pool, idx):
+        super().fill(rec, pool, idx)
+        k = np.random.randint(0, 4)                    # dataset.py:80
+        axis = np.random.randint(0, 2)                 # dataset.py:82
+        rec["mode"], rec["k"], rec["axis"] = 1, int(k), int(axis)
+
+
+class _ResizedPool:
+    """A batch of equally sized device slices (image [B,1,h,w] f32, label [B,h,w] u8) seen as a slice pool."""
+
+    def __init__(self, image, label):
+        B, _, h, w = image.shape
+        self.img, self.lab = image.reshape(-1), label.reshape(-1)
+        self.shapes, self.offsets = [(h, w)] * B, [b * h * w for b in range(B)]
+
+
+class WeakStrongAugment:
+    """The reference's WeakStrongAugment (dataset.py:211-245) on the device.  Per slice, in the reference's order: resize
+    (``zoom(order=0)``), then the weak augmentation ``random_rot_flip`` -- always, never the +-20 degree rotation -- with host
+    draws in the reference's call order (``k = np.random.randint(0, 4)``, ``axis = np.random.randint(0, 2)``): two launches
+    of ``mis_augment2d`` per batch (resize, then rotate / flip the resized slices; a non-square patch is resized once more
+    after an odd rotation, where the reference would return a transposed image).  The strong augmentation is colour jitter
+    (``mis_color_jitter``): as a batch transform of the training loader this class yields the weak batch and the labels, and
+    ``FixMatchTrainer`` draws the jitter factors on the device; as an item transform it draws them on the host in
+    torchvision's order (``ColorJitter.get_params``: a permutation of the four adjustments from torch's generator, then one
+    uniform factor each) and returns ``image``, ``image_weak``, ``image_strong`` (f32 [1,h,w]) and ``label_aug`` (u8 [h,w])
+    device tensors."""
+
+    def __init__(self, output_size):
+        self.output_size = tuple(int(v) for v in output_size)
+
+    def augment(self, pool, indices, recs=None, out=None, keep_resized=False):
+        B = len(indices)
+        resized = augment_batch(pool, indices, _Resize(self.output_size), recs=recs)
+        # pageable staging of its own: the first launch's records may still be in flight in ``recs``
+        staged = torch.zeros(B * _l.AUG2D_BYTES, dtype=torch.uint8)
+        weak = augment_batch(_ResizedPool(*resized), list(range(B)), _RotFlip(self.output_size), recs=staged, out=out)
+        return (weak, resized) if keep_resized else weak
+
+    @staticmethod
+    def draw_jitter():
+        """(beta, gamma, order) with the generator consumption of torchvision's ColorJitter.get_params."""
+        fn_idx = torch.randperm(4).tolist()
+        beta = float(torch.empty(1).uniform_(0.2, 1.8))        # brightness 0.8
+        gamma = float(torch.empty(1).uniform_(0.2, 1.8))       # contrast 0.8
+        torch.empty(1).uniform_(0.2, 1.8)                      # saturation 0.8: no effect on one channel
+        torch.empty(1).uniform_(-0.2, 0.2)                     # hue 0.2: no effect on one channel
+        return beta, gamma, int(fn_idx.index(1) < fn_idx.index(0))
+
+    def __call__(self, sample):
+        from mis_hip import ops
+        pool = DeviceSlicePool([(sample["image"], sample["label"])])
+        (weak, label), (image, _) = self.augment(pool, [0], keep_resized=True)
+        params = torch.tensor([self.draw_jitter()], dtype=torch.float32, device="cuda")
+        strong = torch.empty_like(weak)
+        ops.color_jitter(weak, strong, params=params)
+        return {"image": image[0], "image_weak": weak[0], "image_strong": strong[0], "label_aug": label[0]}
 
 
 class TwoStreamBatchSampler:

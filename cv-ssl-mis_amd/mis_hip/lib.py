@@ -69,15 +69,18 @@ def parse_header(text):
     return protos
 
 
-def _read_header():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes prototypes are read from the C header of the checkout.")
-    with open(HEADER_PATH) as f:
+def _read_header(path=HEADER_PATH):
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: the ctypes prototypes are read from the C header of the checkout.")
+    with open(path) as f:
         return parse_header(f.read())
 
 
 # name -> (restype, argtypes), read from include/mis_hip.h -- the same text the library's definitions are compiled against
 PROTOTYPES = _read_header()
+# headers beside mis_hip.h that declare one kernel family each (same conventions, same parser): file name -> prototypes
+EXTRA_HEADERS = ("mis_hip_fixmatch.h",)
+EXTRA_PROTOTYPES = {h: _read_header(os.path.join(os.path.dirname(HEADER_PATH), h)) for h in EXTRA_HEADERS}
 
 STEP_STATE_BYTES = 40  # sizeof(MisStepState): static_assert in csrc/common.h
 AUG2D_BYTES = 88       # sizeof(MisAug2D): static_assert in csrc/augment.hip
@@ -177,7 +180,12 @@ def load():
             f"{LIB_PATH} is missing: build it with `make -C cv-ssl-mis_amd/csrc` "
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    protos = dict(PROTOTYPES)
+    for extra in EXTRA_PROTOTYPES.values():
+        if set(extra) & set(protos):
+            raise RuntimeError(f"declared twice: {sorted(set(extra) & set(protos))}")
+        protos.update(extra)
+    for name, (res, args) in protos.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

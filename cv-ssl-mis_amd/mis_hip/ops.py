@@ -862,6 +862,59 @@ def grad_combine(dst, src, accumulate):
              "mis_grad_combine")
 
 
+FIXMATCH_JITTER_SALT = 0xF1A7C401
+FIXMATCH_OUT = ("loss", "sup_ce", "sup_dice", "unsup", "consistency_weight", "ce_u", "dice_u", "ce_comp", "as_weight",
+                "masked_in_fraction")
+
+
+def color_jitter(x, out, params=None, state=None, drawn=None, salt=FIXMATCH_JITTER_SALT):
+    """out = ColorJitter(0.8, 0.8, 0.8, 0.2)(x) for one-channel images x [B, 1, ...] (free batch stride, dense planes):
+    brightness and contrast per image, in the order of that image.  ``params`` ([B, 3] fp32: beta, gamma, order; order 0 =
+    brightness first) gives the factors; without it they are drawn on the device from ``state`` (seed, iter_num) under
+    ``salt``.  ``drawn`` ([B, 3] fp32) receives the factors used."""
+    L = _l.load()
+    _l.require_gpu(x, out, params, state, drawn)
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or x.dim() < 3 or x.shape[1] != 1:
+        raise RuntimeError(f"color_jitter takes fp32 [B,1,...] images, got {tuple(x.shape)} {x.dtype}")
+    B = x.shape[0]
+    assert tuple(out.shape) == tuple(x.shape) and x[0].is_contiguous() and out[0].is_contiguous()
+    S = x[0].numel()
+    for t in (params, drawn):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 3 * B)
+    if params is None and state is None:
+        raise ValueError("color_jitter needs the factors (params) or a step state to draw them from")
+    xbs = x.stride(0) if B > 1 else S
+    ybs = out.stride(0) if B > 1 else S
+    ws = scratch(L.mis_color_jitter_workspace_bytes(B, S), "jitter")
+    _l.check(L.mis_color_jitter(_l.ptr(x), xbs, _l.ptr(out), ybs, B, S, _l.ptr(params), _l.ptr(state),
+                                int(salt) & 0xFFFFFFFF, _l.ptr(drawn), _l.ptr(ws), ws.numel(), _l.stream_ptr()),
+             "mis_color_jitter")
+
+
+def fixmatch_tail(weak, strong, label, labeled_bs, out, d_weak=None, d_strong=None, conf_thresh=0.8, cons_weight=0.0,
+                  state=None, pseudo=None, comp=None):
+    """FixMatch loss tail over the logits of one network on the weak and on the strong batch (both [B,C,D,H,W]).
+    ``out`` (>= 10 floats): FIXMATCH_OUT.  ``d_weak`` / ``d_strong``: the logits gradients (either may be None).
+    ``pseudo`` ([B-L, S] uint8) / ``comp`` ([B, S] uint8) receive the kernel's pseudo and complementary labels."""
+    L = _l.load()
+    B, C, D, H, W, S, wbs = _geom(weak)
+    Bs, Cs, _, _, _, Ss, sbs = _geom(strong)
+    assert (Bs, Cs, Ss) == (B, C, S)
+    _l.require_gpu(label, state, out, pseudo, comp)
+    assert label.is_contiguous() and label.dtype in (torch.uint8, torch.int64) and label.numel() >= labeled_bs * S
+    lb = 1 if label.dtype == torch.uint8 else 8
+    assert out.dtype == torch.float32 and out.numel() >= len(FIXMATCH_OUT)
+    dwbs = _geom(d_weak)[6] if d_weak is not None else 0
+    dsbs = _geom(d_strong)[6] if d_strong is not None else 0
+    for t, n in ((pseudo, (B - labeled_bs) * S), (comp, B * S)):
+        assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n)
+    ws = scratch(max(L.mis_fixmatch_tail_workspace_bytes(B, C, S), 0), "tail")
+    _l.check(L.mis_fixmatch_tail(_l.ptr(weak), wbs, _l.ptr(strong), sbs, _l.ptr(label), lb, B, labeled_bs, C, S,
+                                 float(conf_thresh), cons_weight, _l.ptr(state), _l.ptr(out), _l.ptr(d_weak), dwbs,
+                                 _l.ptr(d_strong), dsbs, _l.ptr(pseudo), _l.ptr(comp), _l.ptr(ws), ws.numel(),
+                                 _l.stream_ptr()), "mis_fixmatch_tail")
+
+
 def cross_teaching_tail(own, other, label, labeled_bs, out, dlogits=None, cons_weight=0.0, state=None,
                         pseudo_ce=False, teacher=None, mt_weight=0.0):
     """0.5*(CE+Dice) on the labeled half + w * Dice (``pseudo_ce``: cross-entropy, CPS) against the other network's

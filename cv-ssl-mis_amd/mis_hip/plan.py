@@ -1131,6 +1131,16 @@ class HipNet(nn.Module):
     def _ctx(self):
         return Ctx(self.training, self.step_state, self.drop_masks, self.dropout_enabled, self.rng_stream)
 
+    CHECKPOINT_KEYS = frozenset(("epoch", "state_dict", "optimizer_state_dict", "loss"))
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        """``nn.Module.load_state_dict``; a checkpoint in the shape of the reference's ``util.save_checkpoint`` (exactly the
+        keys ``epoch`` / ``state_dict`` / ``optimizer_state_dict`` / ``loss``, what train_Fixmatch_CNN_2D.py writes) is
+        unwrapped first, so ``net.load_state_dict(torch.load(path))`` of the inference command lines reads both forms."""
+        if isinstance(state_dict, dict) and set(state_dict) == self.CHECKPOINT_KEYS:
+            state_dict = state_dict["state_dict"]
+        return super().load_state_dict(state_dict, *args, **kwargs)
+
     def named_flat(self, flat):
         """Yield (parameter name, view into ``flat`` with that parameter's shape) in parameter order."""
         for name, (off, n, shape) in self._offsets.items():

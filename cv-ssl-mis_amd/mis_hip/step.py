@@ -1,11 +1,12 @@
 """The training steps, each one fused device-side sequence replacing a loop body of the reference.
 
-Seven methods share one skeleton (``_Step``); DESIGN.md has a section per method:
+Eight methods share one skeleton (``_Step``); DESIGN.md has a section per method:
 
     MeanTeacherTrainer      student + EMA teacher on the noised unlabeled half (code/train_mean_teacher_{2D,3D}.py)
     UAMTTrainer             + T = 8 MC-dropout teacher passes, the entropy of their mean masks the consistency term
     ICTTrainer              student on mixed unlabeled samples, pulled towards the mix of two teacher predictions
     DeepCoTrainingTrainer   one network, a pass on the batch and one on its rotated unlabeled half
+    FixMatchTrainer         one network, a pass on the weak batch and one on its colour-jittered copy; pseudo + complementary labels
     CrossTeachingTrainer    two students teach each other through arg-max pseudo labels (``pseudo_ce``: CPS)
     CnnMeetVitTrainer       cross teaching + an EMA teacher of the second student
     TripleViewTrainer       three students, each taught by the arg-max pseudo labels of both others; one joint loss tail
@@ -448,6 +449,88 @@ class ICTTrainer(_TeacherStudentStep):
         if mix_factors is not None and mix_factors.numel() != M:
             raise ValueError(f"mix_factors must hold labeled_bs // 2 = {M} values, got {mix_factors.numel()}")
         return self._step(volume_batch, label_batch, mix_factors)
+
+
+def fixmatch_split(batch_size, labeled_bs):
+    """U = batch_size - labeled_bs, the unlabeled samples of a FixMatch step.  ValueError unless 1 <= labeled_bs <
+    batch_size: the supervised CE / Dice need a labeled sample and the pseudo-label terms an unlabeled one (the reference's
+    CrossEntropyLoss of an empty slice is NaN)."""
+    B, L = int(batch_size), int(labeled_bs)
+    if not 1 <= L < B:
+        raise ValueError(f"FixMatch needs 1 <= labeled_bs < batch_size; got batch_size={B}, labeled_bs={L}")
+    return B - L
+
+
+class FixMatchTrainer(_TeacherStudentStep):
+    """FixMatch with complementary learning (reference code/train_Fixmatch_CNN_2D.py:247-301): ONE network, two train-mode
+    forwards per step -- on the weak batch, then on its colour-jittered (strong) copy, so BatchNorm running statistics are
+    updated twice, in that order -- and the loss of ``mis_fixmatch_tail``: CE + Dice on the labeled weak rows, and, times
+    w = consistency * sigmoid_rampup(iter // 150) (no ``iter_num < 1000`` gate), CE + Dice of the strong unlabeled rows
+    against confidence-masked pseudo labels of the weak pass plus the complementary cross-entropy scaled by the squared
+    adaptive weight, which is differentiated through.  SGD (momentum 0.9, wd 1e-4), poly LR and the EMA of the student into
+    ``ema_model`` in the Mean-Teacher order; the reference updates ``ema_model`` and never runs it, so neither does this step.
+
+    The strong batch is made inside the step (``mis_color_jitter``) from factors drawn on the device under (seed, iter_num),
+    so a replayed launch tape jitters every iteration anew; ``jitter_factors`` ([B, 3]: beta, gamma, order) holds the last
+    step's.  The two passes run on two plans (strong on ``slot=1``); the strong backward's flat gradient is stashed and
+    added to the weak one's (``mis_grad_combine``).  With a process group the sum is exchanged once, after the second
+    backward, by a blocking all-reduce."""
+
+    PASS_STREAMS = (1, 2)           # Philox dropout sub-streams of the weak and the strong pass
+    TRAIN_MODE = "FixMatch runs both passes in train mode (the reference never calls .eval() inside the loop)"
+    _strong_in = None
+
+    def __init__(self, model, ema_model, *, conf_thresh=0.8, use_graph=False, **kw):
+        kw.pop("cons_start_iter", None)           # (run_training-style callers pass it; FixMatch has no gate)
+        super().__init__(model, ema_model, **kw)  # (use_graph: accepted, replays go through the tape)
+        self._bucketer = None                     # two backwards fill the flat gradient: one exchange after the second
+        self.conf_thresh = float(conf_thresh)
+        self.jitter_factors = None                # [B, 3] device tensor: (beta, gamma, order) of the last step
+        self._stash = torch.zeros_like(model.flat_grad)
+
+    def _run(self, volume, label, strong, jitter):
+        L, m = self.labeled_bs, self.model
+        B = volume.shape[0]
+        if strong is None:
+            strong = self._scratch("_strong_in", volume)
+            if self.jitter_factors is None or self.jitter_factors.shape[0] != B:
+                self.jitter_factors = torch.zeros((B, 3), dtype=torch.float32, device=volume.device)
+            params = None if jitter is None else jitter.to(device=volume.device, dtype=torch.float32).reshape(B, 3).contiguous()
+            ops.color_jitter(volume, strong, params=params, state=self.state, drawn=self.jitter_factors)
+        m.rng_stream = self.PASS_STREAMS[0]
+        zw = m.forward_raw(volume)
+        pw = m.last_pass()
+        m.rng_stream = self.PASS_STREAMS[1]
+        zs = m.forward_raw(strong, slot=1)         # a plan of its own: the weak pass's activations and logits survive it
+        ps = m.last_pass()
+        m.rng_stream = self.PASS_STREAMS[0]
+        ops.fixmatch_tail(zw, zs, label[:L].contiguous(), L, self.out, d_weak=m.logits_grad_buffer(pw),
+                          d_strong=m.logits_grad_buffer(ps), conf_thresh=self.conf_thresh, state=self.state)
+        # each backward writes (does not add to) the flat gradient buffer: see DeepCoTrainingTrainer._run for the ordering
+        m.backward_raw(pass_=ps)
+        ops.grad_combine(self._stash, m.flat_grad, accumulate=False)
+        m.backward_raw(pass_=pw)
+        ops.grad_combine(m.flat_grad, self._stash, accumulate=True)
+        grad_scale = _lib.tape_call(dist.sync_gradients, m.flat_grad, self.pg)     # the step's only exchange
+        self._finish_step((m, self.momentum_buf, self.ema_model.flat_param, grad_scale))
+
+    def step(self, weak_batch, label_batch, strong=None, jitter=None):
+        """One iteration on device tensors [B, 1, H, W] / [B, H, W].  ``strong`` ([B, 1, H, W]) replaces the strong batch,
+        ``jitter`` ([B, 3]: beta, gamma, order) the drawn factors; either keeps the step eager (parity tests, or a loader
+        that augments per item).  Returns the device scalar buffer, ``ops.FIXMATCH_OUT`` by position (no host sync)."""
+        if weak_batch.dim() != 4 or weak_batch.shape[1] != 1:
+            raise ValueError(f"FixMatch runs the 2-D networks on [B, 1, H, W]; got {tuple(weak_batch.shape)}")
+        B = weak_batch.shape[0]
+        fixmatch_split(B, self.labeled_bs)
+        if strong is not None and (jitter is not None or tuple(strong.shape) != tuple(weak_batch.shape)):
+            raise ValueError("strong must have the weak batch's shape and excludes jitter")
+        if jitter is not None and jitter.numel() != 3 * B:
+            raise ValueError(f"jitter must hold (beta, gamma, order) per sample: {3 * B} values, got {jitter.numel()}")
+        return self._step(weak_batch, label_batch, strong, jitter)
+
+    def losses(self):
+        o = self.out.cpu()
+        return {k: o[i].item() for i, k in enumerate(ops.FIXMATCH_OUT)}
 
 
 def rotation_schedule(seed, n):

@@ -63,8 +63,9 @@ def check_shards(n_labeled, n_unlabeled, labeled_bs, unlabeled_bs, world):
             f"--labeled_bs / --batch_size, or more labeled data (--labeled_num).")
 
 
-def make_loader(args, label_dtype, rank, world=1):
-    """The training batches: the dataset under ``--root_path`` resident in HBM with the reference's two-stream sampler
+def make_loader(args, label_dtype, rank, world=1, transform="random_generator"):
+    """``transform`` (2-D): "random_generator" (the reference's RandomGenerator) or "weak_strong" (its WeakStrongAugment: the
+    batches are the weakly augmented ones, FixMatchTrainer makes the strong ones).  The training batches: the dataset under ``--root_path`` resident in HBM with the reference's two-stream sampler
     and augmentation as one gather launch per batch (dataloaders/), or -- when no dataset is there (the list file
     ``train_slices.list`` / ``train.txt`` is missing) -- synthetic resident batches of the same shapes/dtypes."""
     three_d = len(args.patch_size) == 3
@@ -90,7 +91,9 @@ def make_loader(args, label_dtype, rank, world=1):
                                          RandomRotFlipCrop(args.patch_size), label_dtype=label_dtype)
     else:
         from dataloaders.dataset import (BaseDataSets, DeviceSlicePool, DeviceTwoStreamLoader, RandomGenerator,
-                                         TwoStreamBatchSampler)
+                                         TwoStreamBatchSampler, WeakStrongAugment)
+        if transform not in ("random_generator", "weak_strong"):
+            raise ValueError(f"unknown transform {transform!r}")
         db_train = BaseDataSets(base_dir=args.root_path, split="train", num=None)
         labeled_slice = patients_to_slices(args.root_path, args.labeled_num)   # train_mean_teacher_2D.py:172-180
         check_shards(labeled_slice, len(db_train) - labeled_slice, args.labeled_bs,
@@ -99,7 +102,7 @@ def make_loader(args, label_dtype, rank, world=1):
         unlabeled = list(range(labeled_slice, len(db_train)))[rank::world]
         sampler = TwoStreamBatchSampler(labeled, unlabeled, args.batch_size, args.batch_size - args.labeled_bs)
         loader = DeviceTwoStreamLoader(DeviceSlicePool.from_dataset(db_train), sampler,
-                                       RandomGenerator(args.patch_size))
+                                       (WeakStrongAugment if transform == "weak_strong" else RandomGenerator)(args.patch_size))
     return loader, "%d cases of %s resident in HBM, %d labeled" % (len(db_train), args.root_path, len(labeled))
 
 
@@ -490,6 +493,150 @@ def run_triple_view(args, make_models, log_every=1, label_dtype=torch.uint8, sna
     if world > 1:
         torch.distributed.destroy_process_group()
     return "Training Finished!"
+
+
+def save_checkpoint(epoch, model, trainer, loss, path):
+    """A checkpoint in the shape of the reference's ``util.save_checkpoint`` (code/utils/util.py:113-123):
+    ``{"epoch", "state_dict", "optimizer_state_dict", "loss"}``.  ``state_dict`` is ``model.state_dict()``.
+    ``optimizer_state_dict`` is NOT a ``torch.optim`` state dict: the optimizer here is the fused SGD kernel, whose state
+    is the flat momentum buffer and the iteration (the learning rate follows from it): ``{"momentum_buffer", "iter_num"}``."""
+    torch.save({"epoch": int(epoch), "state_dict": model.state_dict(),
+                "optimizer_state_dict": {"momentum_buffer": trainer.momentum_buf.detach().cpu(),
+                                         "iter_num": int(trainer.iter_num)},
+                "loss": torch.as_tensor(float(loss))}, path)
+
+
+def load_checkpoint(path, model):
+    """(epoch, iter_num, momentum buffer, loss) of a ``save_checkpoint`` file; the weights go into ``model``."""
+    ck = torch.load(path, map_location="cpu")
+    model.load_state_dict(ck["state_dict"])
+    opt = ck["optimizer_state_dict"]
+    return int(ck["epoch"]), int(opt["iter_num"]), opt["momentum_buffer"], float(ck["loss"])
+
+
+def newest_checkpoint(snapshot_path):
+    """``model_iter_<n>.pth`` / ``model_iter_<n>_dice_<d>.pth`` with the largest n under ``snapshot_path`` (the search of
+    train_Fixmatch_CNN_2D.py:196-206), or None."""
+    best = None
+    if os.path.isdir(snapshot_path):
+        for name in os.listdir(snapshot_path):
+            if name.startswith("model_iter_") and name.endswith(".pth"):
+                try:
+                    n = int(os.path.splitext(name)[0].split("_")[2])
+                except ValueError:
+                    continue
+                if best is None or n > best[0]:
+                    best = (n, os.path.join(snapshot_path, name))
+    return best[1] if best else None
+
+
+def run_fixmatch(args, make_model, log_every=1, label_dtype=torch.uint8, snapshot_fmt="../model/{}_{}/{}"):
+    """Hot loop of train_Fixmatch_CNN_2D.py:243-372: one network and the EMA copy the reference keeps updated,
+    ``FixMatchTrainer.step`` on the weakly augmented batches (the strong ones are made inside the step), the reference's
+    scalar tags (:303-305, :328-344) and log line, validation every 200 iterations with ``model_iter_{n}_dice_{d}.pth`` /
+    ``{model}_best_model.pth`` and the periodic ``model_iter_{n}.pth`` every 3000, all in the ``util.save_checkpoint`` shape.
+    ``--load`` resumes from the newest ``model_iter_*.pth``: weights, momentum buffer, iteration and epoch."""
+    from .step import FixMatchTrainer, fixmatch_split
+    fixmatch_split(args.batch_size, args.labeled_bs)
+    rank, world, _ = setup_distributed()
+    seed_everything(args)
+    snapshot_path = open_snapshot(args, rank, snapshot_fmt)
+    model, ema_model = make_model(), make_model()
+    for p in ema_model.parameters():
+        p.detach_()
+    iter_num, start_epoch, momentum = 0, 0, None
+    if args.load:
+        path = newest_checkpoint(snapshot_path)
+        if path is None:
+            logging.warning("no model_iter_*.pth under %s: using a new model" % snapshot_path)
+        else:
+            start_epoch, iter_num, momentum, _ = load_checkpoint(path, model)
+            logging.info("Models restored from iteration %d (%s)" % (iter_num, path))
+    if world > 1:
+        broadcast_model_state(model, ema_model)
+    model.train()
+    ema_model.train()
+    trainer = FixMatchTrainer(model, ema_model, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
+                              base_lr=args.base_lr, max_iterations=args.max_iterations, ema_decay=args.ema_decay,
+                              consistency=args.consistency, consistency_rampup=args.consistency_rampup,
+                              conf_thresh=args.conf_thresh, seed=args.seed + rank, iter_num=iter_num)
+    if momentum is not None:
+        trainer.momentum_buf.copy_(momentum)
+    loader, source = make_loader(args, label_dtype, rank, world, transform="weak_strong")
+    if rank == 0:
+        logging.info("{} iterations per epoch ({})".format(len(loader), source))
+    scalars = ScalarLog(snapshot_path, enabled=(rank == 0))
+    validator = FixMatchValidator(args, snapshot_path, scalars, rank, world, process_group=trainer.pg)
+    validator.trainer = trainer
+    val_models = [('model_', 'model_', 'best_model', model)]
+    max_epoch = args.max_iterations // len(loader) + 1
+    t0, done = time.time(), 0
+    for epoch_num in range(start_epoch, max_epoch):
+        validator.epoch = epoch_num
+        for sampled_batch in loader:
+            lr_ = args.base_lr * (1.0 - iter_num / args.max_iterations) ** 0.9      # :297, before iter_num += 1
+            trainer.step(sampled_batch["image"], sampled_batch["label"])
+            iter_num += 1
+            done += 1
+            if rank == 0 and iter_num % log_every == 0:
+                s = trainer.losses()
+                validator.loss = s["loss"]
+                scalars.add_scalar('lr', lr_, iter_num)
+                scalars.add_scalar('consistency_weight/consistency_weight', s["consistency_weight"], iter_num)
+                scalars.add_scalar('loss/model_loss', s["loss"], iter_num)
+                logging.info('iteration %d : model loss : %f' % (iter_num, s["loss"]))
+            validator(iter_num, val_models)
+            if rank == 0 and iter_num % 3000 == 0:
+                path = os.path.join(snapshot_path, 'model_iter_' + str(iter_num) + '.pth')
+                save_checkpoint(epoch_num, model, trainer, trainer.losses()["loss"], path)
+                logging.info("save model to {}".format(path))
+            if iter_num >= args.max_iterations:
+                break
+        if iter_num >= args.max_iterations:
+            break
+    torch.cuda.synchronize()
+    if rank == 0:
+        dt = time.time() - t0
+        logging.info("%d iterations in %.2f s (%.1f samples/s over %d GPU(s))" %
+                     (done, dt, done * args.batch_size * world / max(dt, 1e-9), world))
+        path = os.path.join(snapshot_path, '{}_best_model.pth'.format(args.model))
+        if not os.path.exists(path):          # no validation score was recorded: the inference CLI still finds its file
+            save_checkpoint(max(start_epoch, 0), model, trainer, trainer.losses()["loss"], path)
+            logging.info("no validation score was recorded: final weights saved as %s" % path)
+        scalars.close()
+    if world > 1:
+        torch.distributed.destroy_process_group()
+    return "Training Finished!"
+
+
+class FixMatchValidator(Validator):
+    """The Validator with the FixMatch script's files: a new best mean Dice writes ``model_iter_{n}_dice_{d}.pth`` and
+    ``{model}_best_model.pth`` as ``save_checkpoint`` dictionaries (train_Fixmatch_CNN_2D.py:346-354)."""
+
+    trainer, epoch, loss = None, 0, 0.0
+
+    def __call__(self, iter_num, models):
+        if not self.available or iter_num <= 0 or iter_num % 200:
+            return
+        (tag, _, best_name, model), = models
+        was_training = model.training
+        model.eval()
+        perf, hd95, m = self.score(model)
+        model.train(was_training)
+        if self.rank != 0:
+            return
+        if self.scalars is not None:
+            for c in range(m.shape[0]):
+                self.scalars.add_scalar('info/%sval_%d_dice' % (tag, c + 1), m[c, 0], iter_num)
+                self.scalars.add_scalar('info/%sval_%d_hd95' % (tag, c + 1), m[c, 1], iter_num)
+            self.scalars.add_scalar('info/%sval_mean_dice' % tag, perf, iter_num)
+            self.scalars.add_scalar('info/%sval_mean_hd95' % tag, hd95, iter_num)
+        if perf > self.best.get(best_name, 0.0):
+            self.best[best_name] = perf
+            for path in (os.path.join(self.snapshot_path, 'model_iter_%d_dice_%s.pth' % (iter_num, round(perf, 4))),
+                         os.path.join(self.snapshot_path, '%s_best_model.pth' % self.args.model)):
+                save_checkpoint(self.epoch, model, self.trainer, self.loss, path)
+        logging.info('iteration %d : model_mean_dice : %f model_mean_hd95 : %f' % (iter_num, perf, hd95))
 
 
 def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, log_every=1, trainer_cls=None,
