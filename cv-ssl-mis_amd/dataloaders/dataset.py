@@ -192,6 +192,20 @@ class _Resize:
         rec["H"], rec["W"] = H, W
 
 
+class RandomGenerator_w(_Resize):
+    """The reference's RandomGenerator_w (dataset.py:196-208), the weak transform of the contrastive cross-teaching
+    scripts: ``zoom(.., order=0)`` of image and label to ``output_size`` and nothing else -- no draw, no rotation, no flip."""
+
+    def __init__(self, output_size):
+        super().__init__(tuple(int(v) for v in output_size))
+
+    def __call__(self, sample):
+        """Drop-in item transform (device tensors ``image`` f32 [1,h,w] and ``label`` u8 [h,w])."""
+        pool = DeviceSlicePool([(sample["image"], sample["label"])])
+        image, label = augment_batch(pool, [0], self)
+        return {"image": image[0], "label": label[0]}
+
+
 class _RotFlip(_Resize):
     """``random_rot_flip`` (MisAug2D mode 1) with the reference's draws, on slices that already have the output size."""
 

@@ -1029,6 +1029,74 @@ def patch_nce(feat_q, feat_k, out, dfeat=None, temperature=0.07, grad_scale=1.0)
                              _l.ptr(out), _l.ptr(dfeat), dbs, _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_patch_nce")
 
 
+CONTRASTIVE_OUT = ("weighted_loss", "loss_ce", "loss_dice", "pseudo_supervision", "consistency_weight", "model_loss")
+
+
+def contrastive_cross_tail(own, other, label, labeled_bs, out, dlogits=None, extra_l=None, extra_u=None, sup_scale=2.0,
+                           pseudo_scale=1.25, extra_scale=1.0, cons_weight=0.0, state=None):
+    """One student's loss tail of contrastive cross teaching (mis_contrastive_cross_tail): ``out`` (>= 6 floats,
+    CONTRASTIVE_OUT) with out[0] = sup_scale * 0.5 * (CE + Dice) + pseudo_scale * w * Dice(own[L:], argmax other[L:]);
+    ``dlogits`` = d out[0] / d own + extra_scale * the head gradients ``extra_l`` ([L/2, C, ...]: labeled rows 0, 2, ...)
+    and ``extra_u`` ([B-L, C, ...]: the unlabeled rows), each optional, added in the pass that writes dlogits."""
+    L = _l.load()
+    B, C, D, H, W, S, sbs = _geom(own)
+    Bo, Co, _, _, _, So, obs = _geom(other)
+    assert (Bo, Co, So) == (B, C, S)
+    _l.require_gpu(label, state, out)
+    assert label.is_contiguous() and label.dtype in (torch.uint8, torch.int64) and label.numel() >= labeled_bs * S
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= len(CONTRASTIVE_OUT)
+    lb = 1 if label.dtype == torch.uint8 else 8
+    dbs = elbs = eubs = 0
+    if dlogits is not None:
+        Bd, Cd, _, _, _, Sd, dbs = _geom(dlogits)
+        assert (Bd, Cd, Sd) == (B, C, S)
+    if extra_l is not None:
+        Be, Ce, _, _, _, Se, elbs = _geom(extra_l)
+        assert (2 * Be, Ce, Se) == (labeled_bs, C, S), (tuple(extra_l.shape), labeled_bs)
+    if extra_u is not None:
+        Be, Ce, _, _, _, Se, eubs = _geom(extra_u)
+        assert (Be, Ce, Se) == (B - labeled_bs, C, S), (tuple(extra_u.shape), B - labeled_bs)
+    ws = scratch(max(L.mis_contrastive_cross_tail_workspace_bytes(B, C, S), 0), "tail")
+    _l.check(L.mis_contrastive_cross_tail(_l.ptr(own), sbs, _l.ptr(other), obs, _l.ptr(label), lb, B, labeled_bs, C, S,
+                                          float(sup_scale), float(pseudo_scale), float(cons_weight), _l.ptr(state),
+                                          _l.ptr(extra_l), elbs, _l.ptr(extra_u), eubs, float(extra_scale), _l.ptr(out),
+                                          _l.ptr(dlogits), dbs, _l.ptr(ws), ws.numel(), _l.stream_ptr()),
+             "mis_contrastive_cross_tail")
+
+
+def contrastive_step_init(state, seed, iter_num, base_lr, max_iterations, consistency, rampup, iters_per_epoch):
+    L = _l.load()
+    _l.check(L.mis_contrastive_step_init(_l.ptr(state), seed, iter_num, base_lr, float(max_iterations), consistency,
+                                         float(rampup), int(iters_per_epoch), _l.stream_ptr()),
+             "mis_contrastive_step_init")
+
+
+def contrastive_step_advance(state, base_lr, max_iterations, consistency, rampup, iters_per_epoch):
+    L = _l.load()
+    _l.check(L.mis_contrastive_step_advance(_l.ptr(state), base_lr, float(max_iterations), consistency, float(rampup),
+                                            int(iters_per_epoch), _l.stream_ptr()), "mis_contrastive_step_advance")
+
+
+def contrastive_schedule(k, base_lr, max_iterations, consistency, rampup, iters_per_epoch):
+    """Host restatement of the device schedule: (lr, consistency weight) of the step that runs at iteration ``k``
+    (reference code/train_Contrastive_Cross_CNN_2D.py:107-110, :274-278; the lr of step k was computed after step k - 1
+    from iter_num = k - 1, before the increment)."""
+    import math
+    lr = float(base_lr)
+    if k >= 1:
+        it = k - 1
+        if it / max_iterations > 0.5:
+            lr = 0.0001 * max(1.0 - (it - max_iterations * 0.5) / max_iterations * 0.5, 0.0) ** 0.9
+        else:
+            lr = base_lr * max(1.0 - it / max_iterations, 0.0) ** 0.9
+    epoch = k // iters_per_epoch
+    ramp = 1.0
+    if epoch < rampup:
+        p = 1.0 - max(0.0, float(epoch)) / float(rampup)
+        ramp = math.exp(-p * p * 5.0)
+    return lr, consistency * ramp
+
+
 # ------------------------------------------------------------ optimizer / rng
 def sgd_ema_step(param, grad, momentum_buf, ema_param, lr=0.0, momentum=0.9, weight_decay=1e-4, ema_alpha=0.99,
                  grad_scale=1.0, state=None):

@@ -169,6 +169,8 @@ class ConvOp:
         self.fused_into = None   # NormActOp that computes this 1x1x1 classifier in its own pass (Plan._fuse_head)
         self.norm_bwd = None     # NormActOp whose backward apply pass runs on this (first) conv's wgrad load path
         self.dgrad_norm = None   # NormActOp producing x whose backward partial sums this conv's data gradient forms
+        self.frozen = False      # True (Plan.conv, from HipNet.frozen): the parameters are in no optimizer -- the backward forms
+                                 # the data gradient only, no weight or bias gradient launch
 
     def fwd(self, ctx):
         if self.fused_into is not None:
@@ -184,6 +186,9 @@ class ConvOp:
     def bwd(self, ctx):
         if self.fused_into is not None:
             return               # the NormActOp's backward writes w.grad / b.grad / its own input gradient
+        if self.frozen:
+            self._bwd_data_only()
+            return
         if self.norm_bwd is not None:      # need_dx False, bias gradient exactly 0: the weight gradient is all there is
             n = self.norm_bwd
             ops.conv_wgrad_cin1_norm(self.x.t, n.y.grad(), self.y.t, n.per_sample, n.mean, n.rstd, *n._affine(), n.sums,
@@ -225,6 +230,19 @@ class ConvOp:
             self.x.mark_written()
 
 
+    def _bwd_data_only(self):
+        """The backward of a frozen network's conv: the data gradient, written (a frozen head is a chain: its activations
+        have one reader each, so there is nothing to accumulate into)."""
+        if not self.need_dx:
+            return
+        assert self.norm_bwd is None and self.dgrad_norm is None and not self.x.written
+        if not self.batched:
+            self.wpd = ops.conv_pack(self.w.data, ops.conv_wino_pack_mode(self.wino_b, True) if self.wino_b >= 0 else 1,
+                                     out=self.wpd)
+        ops.conv_fwd(self.y.grad(), self.wpd, None, self.x.grad(), self.cout, self.cin, self.ksize, wino=self.wino_b)
+        self.x.mark_written()
+
+
 class NormActOp:
     """BatchNorm(train/eval), InstanceNorm or GroupNorm (``per_sample`` with ``cg`` channels per group and a per-channel
     affine), or no normalisation at all (``no_norm``), then (Leaky)ReLU, then inverted dropout."""
@@ -252,6 +270,7 @@ class NormActOp:
         self.res_post = False    # True: added behind the activation instead (Plan.add's fusion of V-Net's x_up + skip)
         self.head = None         # 1x1x1 classifier ConvOp computed in this op's pass (Plan._fuse_head); head_w / head_b:
         self.head_w = self.head_b = None     # its parameters (their gradients are written by THIS op: dist.param_progress)
+        self.frozen = False
 
     def _affine(self):
         """(gamma.data, beta.data) for a launch, each None when the normalisation has no such parameter.  A method, not a
@@ -259,6 +278,8 @@ class NormActOp:
         return (None if self.gamma is None else self.gamma.data, None if self.beta is None else self.beta.data)
 
     def _affine_grad(self):
+        if self.frozen:          # (Plan.norm_act, from HipNet.frozen) the kernels take NULL for "no affine gradient wanted"
+            return (None, None)
         return (None if self.gamma is None else self.gamma.grad, None if self.beta is None else self.beta.grad)
 
     def fwd(self, ctx):
@@ -668,7 +689,7 @@ class PlanBase:
         ctx.b3_bwd = self._split_weights(True)
         main = torch.cuda.current_stream()
         side = None
-        if WGRAD_STREAM:
+        if WGRAD_STREAM and not getattr(self.net, "frozen", False):
             if self._wgrad_stream is None:
                 self._wgrad_stream = _lib.side_stream("wgrad")
             side = self._wgrad_stream
@@ -702,6 +723,7 @@ class Plan(PlanBase):
         self.acts.append(self.inp)
         self._salt = itertools.count(0)
         self._packs = None
+        self._packed_version = [None, None]      # frozen networks: net.weights_version the packed filters were made from
         self._head_checked = False
 
     # ---- builders used by the networks ----
@@ -717,12 +739,14 @@ class Plan(PlanBase):
 
     def conv(self, x, y, w, b, ksize, need_dx=True, bias_grad=True):
         self.ops.append(ConvOp(x, y, w, b, ksize, need_dx, bias_grad))
+        self.ops[-1].frozen = bool(getattr(self.net, "frozen", False))
         return y
 
     def norm_act(self, x, y, per_sample, gamma=None, beta=None, running=None, slope=0.0, drop_p=0.0, drop3d=False,
                  cg=1, no_norm=False):
         op = NormActOp(x, y, per_sample, gamma, beta, running, slope, drop_p, next(self._salt), cg=cg, no_norm=no_norm)
         op.drop3d = drop3d
+        op.frozen = bool(getattr(self.net, "frozen", False))
         # conv -> norm: let the conv epilogue produce the statistics (no separate pass over the conv output)
         prev = self.ops[-1] if self.ops else None
         if FUSE_CONV_STATS and not no_norm and type(prev) is ConvOp and prev.y is x:
@@ -828,6 +852,11 @@ class Plan(PlanBase):
                 op.batched = True
             self._packs = (ops.PackBatch(fj) if fj else None, ops.PackBatch(bj) if bj else None)
         if self._packs[mode] is not None:
+            if getattr(self.net, "frozen", False):
+                # nothing updates a frozen network's weights between passes: pack when they were (re)loaded, not every pass
+                if self._packed_version[mode] == self.net.weights_version:
+                    return
+                self._packed_version[mode] = self.net.weights_version
             self._packs[mode].run()
 
     def _fuse_dgrad_norm(self):
@@ -1033,9 +1062,17 @@ class HipNet(nn.Module):
     """
 
     ndim_spatial = 2
+    # True: the parameters are in no optimizer (the contrastive heads, reference networks/projector.py).  A backward then
+    # forms the data gradient only -- flat_grad is never written -- and the conv filters are packed once per
+    # ``weights_version`` instead of once per pass.  Whoever writes the parameters in place calls ``weights_changed()``.
+    # Read when a plan is built (its ops carry the flag): set it before the first forward.
+    frozen = False
+    # True: forward_raw binds a batch-strided input view as it is (the kernels take batch strides) instead of copying it
+    strided_input = False
 
     def __init__(self):
         super().__init__()
+        self.weights_version = 0
         self.net_id = next(_net_ids)
         self._specs = []       # (dotted name, shape, kind, init tensor)
         self._refs = {}
@@ -1131,6 +1168,10 @@ class HipNet(nn.Module):
     def _ctx(self):
         return Ctx(self.training, self.step_state, self.drop_masks, self.dropout_enabled, self.rng_stream)
 
+    def weights_changed(self):
+        """The parameters were written in place (a load, a broadcast): a frozen network packs its filters again."""
+        self.weights_version += 1
+
     CHECKPOINT_KEYS = frozenset(("epoch", "state_dict", "optimizer_state_dict", "loss"))
 
     def load_state_dict(self, state_dict, *args, **kwargs):
@@ -1139,6 +1180,7 @@ class HipNet(nn.Module):
         unwrapped first, so ``net.load_state_dict(torch.load(path))`` of the inference command lines reads both forms."""
         if isinstance(state_dict, dict) and set(state_dict) == self.CHECKPOINT_KEYS:
             state_dict = state_dict["state_dict"]
+        self.weights_changed()
         return super().load_state_dict(state_dict, *args, **kwargs)
 
     def named_flat(self, flat):
@@ -1150,7 +1192,9 @@ class HipNet(nn.Module):
     def forward_raw(self, x, no_backward=False, slot=0):
         """``no_backward``: nobody will differentiate this pass (the EMA teacher, validation): ops may skip what only a
         backward reads -- backward_raw() after such a pass fails loudly.  ``slot``: see plan_for."""
-        x5 = self._as5(x.contiguous())
+        if not (self.strided_input and x.dim() >= 2 and x[0].is_contiguous()):
+            x = x.contiguous()
+        x5 = self._as5(x)
         plan = self.plan_for(x5.shape, slot)
         ctx = self._ctx()
         ctx.no_backward = bool(no_backward)
@@ -1185,6 +1229,11 @@ class HipNet(nn.Module):
 
     def logits_grad_buffer(self, pass_=None):
         return self._pass(pass_)[0].out.grad()
+
+    def input_grad_buffer(self, pass_=None):
+        """The gradient at the network's input, [N, C, D, H, W] contiguous: valid after ``backward_raw`` of a plan whose first
+        op forms a data gradient (a first conv built with ``need_dx=True``)."""
+        return self._pass(pass_)[0].inp.grad()
 
     # nn.Module surface: logits = model(x); loss.backward() works through _NetFn
     def forward(self, x):

@@ -1,6 +1,6 @@
 """The training steps, each one fused device-side sequence replacing a loop body of the reference.
 
-Eight methods share one skeleton (``_Step``); DESIGN.md has a section per method:
+Nine methods share one skeleton (``_Step``); DESIGN.md has a section per method:
 
     MeanTeacherTrainer      student + EMA teacher on the noised unlabeled half (code/train_mean_teacher_{2D,3D}.py)
     UAMTTrainer             + T = 8 MC-dropout teacher passes, the entropy of their mean masks the consistency term
@@ -8,6 +8,7 @@ Eight methods share one skeleton (``_Step``); DESIGN.md has a section per method
     DeepCoTrainingTrainer   one network, a pass on the batch and one on its rotated unlabeled half
     FixMatchTrainer         one network, a pass on the weak batch and one on its colour-jittered copy; pseudo + complementary labels
     CrossTeachingTrainer    two students teach each other through arg-max pseudo labels (``pseudo_ce``: CPS)
+    ContrastiveCrossTrainer cross teaching + two pixel-wise contrastive terms through frozen projector / classifier heads
     CnnMeetVitTrainer       cross teaching + an EMA teacher of the second student
     TripleViewTrainer       three students, each taught by the arg-max pseudo labels of both others; one joint loss tail
 
@@ -226,6 +227,11 @@ class _Step(_TapedStep):
         for net, mom, ema_param, grad_scale in updates:
             ops.sgd_ema_step(net.flat_param, net.flat_grad, mom, ema_param, momentum=self.momentum,
                              weight_decay=self.weight_decay, grad_scale=grad_scale, state=self.state)
+        self._advance_schedule()
+
+    def _advance_schedule(self):
+        """The device-side schedule after the optimizer: the Mean-Teacher family's rule (a trainer whose script has another
+        one overrides this)."""
         ops.step_advance(self.state, **self.hyper)
 
     def _pair_losses(self):
@@ -668,6 +674,118 @@ class CrossTeachingTrainer(_Step):
 
     def losses(self):
         return self._pair_losses()[2]
+
+
+def contrastive_split(batch_size, labeled_bs):
+    """U = batch_size - labeled_bs, the unlabeled samples of a contrastive cross-teaching step.  ValueError unless
+    labeled_bs is even and 2 <= labeled_bs < batch_size: the supervised contrastive term pairs the labeled rows 0::2 of one
+    student with the rows 1::2 of the other (the reference asserts equal feature shapes), and ConLoss needs an unlabeled row."""
+    B, L = int(batch_size), int(labeled_bs)
+    if L < 2 or L % 2 or not L < B:
+        raise ValueError(f"contrastive cross teaching needs an even labeled_bs with 2 <= labeled_bs < batch_size; got "
+                         f"batch_size={B}, labeled_bs={L}")
+    return B - L
+
+
+class ContrastiveCrossTrainer(_Step):
+    """Contrastive cross teaching (reference code/train_Contrastive_Cross_CNN_2D.py:212-283; _CNN_ViT_2D.py is the same
+    step with the SwinUnet as ``model2``): cross teaching through Dice on each other's arg-max pseudo labels, plus two
+    pixel-wise contrastive terms between the students' logits seen through small frozen heads --
+
+        Lc_l = contrastive_loss_sup(classifier_1(z1[:L][0::2]), classifier_2(z2[:L][1::2]))
+        Lc_u = ConLoss(projector_1(z1[L:]), projector_2(z2[L:]))
+        loss = 2 * (sup_1 + sup_2) + 0.5 * (Lc_l + Lc_u) + 1.25 * w * (ps_1 + ps_2)
+
+    Both losses detach the key side, so only ``model1`` receives a contrastive gradient: on the labeled rows 0, 2, ...
+    through ``classifier_1`` and on every unlabeled row through ``projector_1``.  The four heads are in no optimizer
+    (``HipNet.frozen``): they keep their initial weights, run in train mode (BatchNorm batch statistics of the sub-batch,
+    running buffers updated) and their backward forms the input gradient only.  ``ops.contrastive_cross_tail`` adds those
+    input gradients into ``model1``'s logits gradient in the pass that writes it.  ``SCALES`` is the one place the
+    script's 2 / 0.5 / 1.25 stand.
+
+    w = consistency * ramp_up_function(iter_num // iters_per_epoch, rampup) and the script's own learning-rate rule
+    (:274-278, 1e-4 based once past half of max_iterations) advance on the device (``mis_contrastive_step_advance``), so the
+    taped step stays right across an epoch boundary and the LR switch.  With a process group the heads are broadcast from
+    rank 0 once, here, and nothing of theirs is exchanged afterwards; BatchNorm statistics stay per rank."""
+
+    TRAIN_MODE = "contrastive cross teaching runs both students and the four heads in train mode"
+    SCALES = dict(sup=2.0, contrastive=0.5, pseudo=1.25)          # reference :261
+
+    def __init__(self, model1, model2, classifier_1, classifier_2, projector_1, projector_2, *, labeled_bs, num_classes,
+                 iters_per_epoch, base_lr=0.01, max_iterations=30000, consistency=0.1, consistency_rampup=200.0,
+                 seed=1337, iter_num=0, momentum=0.9, weight_decay=1e-4, temperature=0.07, process_group=None,
+                 use_tape=None):
+        contrastive_split(int(labeled_bs) + 1, labeled_bs)        # an odd labeled_bs is refused before any launch
+        if int(iters_per_epoch) < 1:
+            raise ValueError(f"iters_per_epoch must be >= 1, got {iters_per_epoch}")
+        heads = (classifier_1, classifier_2, projector_1, projector_2)
+        if not all(getattr(h, "frozen", False) for h in heads):
+            raise RuntimeError("the contrastive heads are in no optimizer: pass HipNets with frozen = True "
+                               "(networks.projector)")
+        self.model1, self.model2 = model1, model2
+        self.classifier_1, self.classifier_2, self.projector_1, self.projector_2 = heads
+        self._setup((model1, model2), heads, (1, 2, 3, 4, 5, 6), labeled_bs=int(labeled_bs), num_classes=num_classes,
+                    base_lr=base_lr, max_iterations=max_iterations, consistency=consistency,
+                    consistency_rampup=consistency_rampup, lr_post_increment=True, seed=seed, iter_num=iter_num,
+                    momentum=momentum, weight_decay=weight_decay, process_group=process_group, use_tape=use_tape)
+        # this script's schedule instead of the Mean-Teacher family's (_setup wrote that one into the state)
+        self.sched = dict(base_lr=float(base_lr), max_iterations=float(max_iterations), consistency=float(consistency),
+                          rampup=float(consistency_rampup), iters_per_epoch=int(iters_per_epoch))
+        ops.contrastive_step_init(self.state, seed, iter_num, **self.sched)
+        self.temperature = float(temperature)
+        self.out_cl = torch.zeros(4, dtype=torch.float32, device="cuda")      # ops.patch_nce scalars: Lc_l, ...
+        self.out_cu = torch.zeros(4, dtype=torch.float32, device="cuda")      # ... and Lc_u
+        for h in heads:
+            dist.broadcast_state([h.flat_param] + list(h.buffers()), group=process_group)
+            h.weights_changed()
+        # model2 is the side-stream student (_backward_pair): its tail bucket is deferred
+        self._bucketers = (make_bucketer(model1, process_group),
+                           make_bucketer(model2, process_group, defer_tail=TWO_STREAM))
+
+    def _advance_schedule(self):
+        ops.contrastive_step_advance(self.state, **self.sched)
+
+    def step(self, volume_batch, label_batch):
+        """One iteration on device tensors [B, 1, H, W] / [B, H, W]; returns the two device scalar buffers
+        (``ops.CONTRASTIVE_OUT`` by position; no host sync)."""
+        contrastive_split(volume_batch.shape[0], self.labeled_bs)
+        return self._step(volume_batch, label_batch)
+
+    def _run(self, volume_batch, label_batch):
+        L, s = self.labeled_bs, self.SCALES
+        lab = label_batch[:L].contiguous()
+        o2, o1 = self._beside(lambda: self.model2.forward_raw(volume_batch), lambda: self.model1.forward_raw(volume_batch))
+        cls1, cls2, prj1, prj2 = self.classifier_1, self.classifier_2, self.projector_1, self.projector_2
+        # the key side is detached by both losses: forward only, beside the query side (batch-strided views, not copies)
+        z1, z2 = o1.squeeze(2), o2.squeeze(2)       # [B, C, H, W] views of the plans' logits buffers
+        (k_l, k_u), (q_l, q_u) = self._beside(
+            lambda: (cls2.forward_raw(z2[:L][1::2], no_backward=True), prj2.forward_raw(z2[L:], no_backward=True)),
+            lambda: (cls1.forward_raw(z1[:L][0::2]), prj1.forward_raw(z1[L:])))
+        ops.patch_nce(q_l, k_l, self.out_cl, dfeat=cls1.logits_grad_buffer(), temperature=self.temperature,
+                      grad_scale=s["contrastive"])
+        ops.patch_nce(q_u, k_u, self.out_cu, dfeat=prj1.logits_grad_buffer(), temperature=self.temperature,
+                      grad_scale=s["contrastive"])
+        cls1.backward_raw()
+        prj1.backward_raw()
+        ops.contrastive_cross_tail(o1, o2, lab, L, self.out1, dlogits=self.model1.logits_grad_buffer(),
+                                   extra_l=cls1.input_grad_buffer(), extra_u=prj1.input_grad_buffer(),
+                                   sup_scale=s["sup"], pseudo_scale=s["pseudo"], extra_scale=1.0, state=self.state)
+        ops.contrastive_cross_tail(o2, o1, lab, L, self.out2, dlogits=self.model2.logits_grad_buffer(),
+                                   sup_scale=s["sup"], pseudo_scale=s["pseudo"], state=self.state)
+        scales = self._backward_pair(side=1)
+        self._finish_step((self.model1, self.mom1, None, scales[0]), (self.model2, self.mom2, None, scales[1]))
+
+    def losses(self):
+        """Host copies of the last step's scalars: the quantities the reference logs (:286-294) and the terms behind them.
+        ``lr`` is the rate the next step runs with, as the script logs ``lr_`` after computing it."""
+        a, b, cl, cu = self.out1.cpu(), self.out2.cpu(), self.out_cl.cpu(), self.out_cu.cpu()
+        c_l, c_u = cl[0].item(), cu[0].item()
+        con = c_l + c_u
+        return dict(loss=a[0].item() + b[0].item() + self.SCALES["contrastive"] * con,
+                    model1_loss=a[5].item(), model2_loss=b[5].item(), con_loss=con, c_loss_l=c_l, c_loss_u=c_u,
+                    consistency_weight=a[4].item(), lr=ops.read_step_state(self.state)["lr"],
+                    loss1_ce=a[1].item(), loss1_dice=a[2].item(), pseudo_supervision1=a[3].item(),
+                    loss2_ce=b[1].item(), loss2_dice=b[2].item(), pseudo_supervision2=b[3].item())
 
 
 def linear_rampup(current, rampup_length):

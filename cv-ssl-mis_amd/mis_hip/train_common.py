@@ -64,8 +64,9 @@ def check_shards(n_labeled, n_unlabeled, labeled_bs, unlabeled_bs, world):
 
 
 def make_loader(args, label_dtype, rank, world=1, transform="random_generator"):
-    """``transform`` (2-D): "random_generator" (the reference's RandomGenerator) or "weak_strong" (its WeakStrongAugment: the
-    batches are the weakly augmented ones, FixMatchTrainer makes the strong ones).  The training batches: the dataset under ``--root_path`` resident in HBM with the reference's two-stream sampler
+    """``transform`` (2-D): "random_generator" (the reference's RandomGenerator), "weak_strong" (its WeakStrongAugment: the
+    batches are the weakly augmented ones, FixMatchTrainer makes the strong ones) or "weak" (its RandomGenerator_w: the
+    nearest-neighbour resize alone, no rotation or flip).  The training batches: the dataset under ``--root_path`` resident in HBM with the reference's two-stream sampler
     and augmentation as one gather launch per batch (dataloaders/), or -- when no dataset is there (the list file
     ``train_slices.list`` / ``train.txt`` is missing) -- synthetic resident batches of the same shapes/dtypes."""
     three_d = len(args.patch_size) == 3
@@ -91,8 +92,9 @@ def make_loader(args, label_dtype, rank, world=1, transform="random_generator"):
                                          RandomRotFlipCrop(args.patch_size), label_dtype=label_dtype)
     else:
         from dataloaders.dataset import (BaseDataSets, DeviceSlicePool, DeviceTwoStreamLoader, RandomGenerator,
-                                         TwoStreamBatchSampler, WeakStrongAugment)
-        if transform not in ("random_generator", "weak_strong"):
+                                         RandomGenerator_w, TwoStreamBatchSampler, WeakStrongAugment)
+        transforms = {"random_generator": RandomGenerator, "weak_strong": WeakStrongAugment, "weak": RandomGenerator_w}
+        if transform not in transforms:
             raise ValueError(f"unknown transform {transform!r}")
         db_train = BaseDataSets(base_dir=args.root_path, split="train", num=None)
         labeled_slice = patients_to_slices(args.root_path, args.labeled_num)   # train_mean_teacher_2D.py:172-180
@@ -102,7 +104,7 @@ def make_loader(args, label_dtype, rank, world=1, transform="random_generator"):
         unlabeled = list(range(labeled_slice, len(db_train)))[rank::world]
         sampler = TwoStreamBatchSampler(labeled, unlabeled, args.batch_size, args.batch_size - args.labeled_bs)
         loader = DeviceTwoStreamLoader(DeviceSlicePool.from_dataset(db_train), sampler,
-                                       (WeakStrongAugment if transform == "weak_strong" else RandomGenerator)(args.patch_size))
+                                       transforms[transform](args.patch_size))
     return loader, "%d cases of %s resident in HBM, %d labeled" % (len(db_train), args.root_path, len(labeled))
 
 
@@ -358,10 +360,14 @@ def open_snapshot(args, rank, fmt="../model/{}_{}_labeled/{}"):
 
 
 def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=torch.uint8, pseudo_ce=False,
-                       make_ema=None, snapshot_fmt="../model/{}_{}/{}", init_fns=None):
+                       make_ema=None, snapshot_fmt="../model/{}_{}/{}", init_fns=None, make_trainer=None,
+                       transform="random_generator", scalar_tag=None, log_line=None):
     """Hot loop of train_cross_teaching_between_cnn_transformer_2D.py:208-300 (two students, no teacher); with
     ``pseudo_ce=True`` that of train_cross_pseudo_supervision_{2D,3D}.py (CE pseudo-supervision); with ``make_ema``
-    (the EMA teacher of model2) that of train_cnn_meet_vit_2D.py:285-352."""
+    (the EMA teacher of model2) that of train_cnn_meet_vit_2D.py:285-352.  A two-student method with a trainer of its own
+    (run_contrastive_cross) passes ``make_trainer(model1, model2, rank, iters_per_epoch)``, the loader's ``transform``, the
+    tag of each logged scalar (``scalar_tag(key)``) and its log line (``log_line(iter_num, losses)``); the loader is then
+    built before the trainer, which needs its length."""
     from .step import CnnMeetVitTrainer, CrossTeachingTrainer
     rank, world, _ = setup_distributed()
     seed_everything(args)
@@ -386,12 +392,20 @@ def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=
                                     max_iterations=args.max_iterations, ema_decay=args.ema_decay,
                                     consistency=args.consistency, consistency_rampup=args.consistency_rampup,
                                     seed=args.seed + rank)
+    elif make_trainer is not None:
+        loader, source = make_loader(args, label_dtype, rank, world, transform=transform)
+        trainer = make_trainer(model1, model2, rank, len(loader))
     else:
         trainer = CrossTeachingTrainer(model1, model2, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
                                        base_lr=args.base_lr, max_iterations=args.max_iterations,
                                        consistency=args.consistency, consistency_rampup=args.consistency_rampup,
                                        seed=args.seed + rank, pseudo_ce=pseudo_ce)
-    loader, source = make_loader(args, label_dtype, rank, world)
+    if make_trainer is None:
+        loader, source = make_loader(args, label_dtype, rank, world)
+    if scalar_tag is None:
+        scalar_tag = lambda k: 'loss/' + k if k != 'consistency_weight' else 'consistency_weight/' + k
+    if log_line is None:
+        log_line = lambda it, s: 'iteration %d : model1 loss : %f model2 loss : %f' % (it, s["model1_loss"], s["model2_loss"])
     if rank == 0:
         logging.info("{} iterations per epoch ({})".format(len(loader), source))
     scalars = ScalarLog(snapshot_path, enabled=(rank == 0))
@@ -408,10 +422,8 @@ def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=
             if rank == 0 and iter_num % log_every == 0:
                 s = trainer.losses()
                 for k, v in s.items():
-                    scalars.add_scalar('loss/' + k if k != 'consistency_weight' else 'consistency_weight/' + k, v,
-                                       iter_num)
-                logging.info('iteration %d : model1 loss : %f model2 loss : %f' %
-                             (iter_num, s["model1_loss"], s["model2_loss"]))
+                    scalars.add_scalar(scalar_tag(k), v, iter_num)
+                logging.info(log_line(iter_num, s))
             validator(iter_num, val_models)      # every rank: the validation cases are sharded over the ranks
             if rank == 0 and iter_num % 3000 == 0:
                 for i, m in ((1, model1), (2, model2)):
@@ -432,6 +444,34 @@ def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=
     if world > 1:
         torch.distributed.destroy_process_group()
     return "Training Finished!"
+
+
+def run_contrastive_cross(args, make_model1, make_model2, log_every=1, label_dtype=torch.uint8,
+                          snapshot_fmt="../model/{}_{}_labeled/{}"):
+    """Hot loop of train_Contrastive_Cross_CNN_2D.py:196-408 (and its _CNN_ViT_ twin): run_cross_teaching's loop --
+    both students validated every 200 iterations, best-model and periodic checkpoints under the reference's file names --
+    around ``ContrastiveCrossTrainer``, with the four frozen heads of ``net_factory("classifier" | "projector")``, the
+    resize-only weak loader (the strong loader's batch is never read by the loss: it is not built), the script's scalars
+    (:286-292) and its log line (:294)."""
+    from networks.net_factory import net_factory
+    from .step import ContrastiveCrossTrainer
+
+    def make_trainer(model1, model2, rank, iters_per_epoch):
+        heads = [net_factory(k) for k in ("classifier", "classifier", "projector", "projector")]     # :139-142
+        for h in heads:
+            h.train()
+        return ContrastiveCrossTrainer(model1, model2, *heads, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
+                                       iters_per_epoch=iters_per_epoch, base_lr=args.base_lr,
+                                       max_iterations=args.max_iterations, consistency=args.consistency,
+                                       consistency_rampup=args.consistency_rampup, seed=args.seed + rank)
+
+    tags = {"lr": "lr", "consistency_weight": "consistency_weight/consistency_weight"}
+    line = lambda it, s: ('itr %d, loss %0.2f, m1 loss %0.2f, m2 loss %0.2f, con_loss %0.2f,c_loss_l %0.2f,c_loss_u %0.2f, lr %f'
+                          % (it, s["loss"], s["model1_loss"], s["model2_loss"], s["con_loss"], s["c_loss_l"], s["c_loss_u"],
+                             s["lr"]))
+    return run_cross_teaching(args, make_model1, make_model2, log_every=log_every, label_dtype=label_dtype,
+                              snapshot_fmt=snapshot_fmt, make_trainer=make_trainer, transform="weak",
+                              scalar_tag=lambda k: tags.get(k, "loss/" + k), log_line=line)
 
 
 def run_triple_view(args, make_models, log_every=1, label_dtype=torch.uint8, snapshot_fmt="../model/{}_{}/{}"):
