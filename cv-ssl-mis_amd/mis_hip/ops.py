@@ -280,10 +280,10 @@ def conv1x1_wgrad(a, b, dw, accumulate=False):
                                  _l.ptr(ws), nb, _l.stream_ptr()), "mis_conv1x1_wgrad")
 
 
-def conv_wino_select(N, Cin, Cout, D, H, W, ksize):
+def conv_wino_select(N, Cin, Cout, D, H, W, ksize, dilation=1):
     """Winograd variant serving this convolution (mis_conv3d_wino_select / mis_conv2d_wino_select), or -1: use the
-    direct kernel."""
-    if not WINO:
+    direct kernel.  A dilated convolution has no Winograd form here: -1."""
+    if not WINO or dilation != 1:
         return -1
     k = _ksize(ksize)
     if k == (3, 3, 3) and (WINO & 1):
@@ -473,6 +473,77 @@ def _conv_wgrad_launch(L, x, dy, dw, N, Cin, Cout, D, H, W, xbs, dbs, kd, kh, kw
     buf = _ctypes.create_string_buffer(96)
     _l.check(L.mis_conv_wgrad_kernel_name(N, Cin, Cout, D, H, W, kd, kh, kw, buf, 96), "mis_conv_wgrad_kernel_name")
     return buf.value.decode()
+
+
+# ------------------------------------------------------- dilated 3x3 convolution (conv_dilated.hip, mis_hip_dilated.h)
+def _dilated_geom(x, y):
+    N, Cx, D, H, W, S, xbs = _geom(x)
+    Ny, Cy, Dy, Hy, Wy, _, ybs = _geom(y)
+    if D != 1 or (N, D, H, W) != (Ny, Dy, Hy, Wy):
+        raise RuntimeError(f"dilated convolution: 2-D tensors of one geometry expected, got {tuple(x.shape)} {tuple(y.shape)}")
+    return N, Cx, Cy, H, W, xbs, ybs
+
+
+def _dilated_name(fn, N, Cin, Cout, H, W, dilation):
+    buf = _ctypes.create_string_buffer(128)
+    _l.check(getattr(_l.load(), fn)(N, Cin, Cout, H, W, int(dilation), buf, 128), fn)
+    return buf.value.decode()
+
+
+def conv_dilated_fwd_kernel_name(N, Cin, Cout, H, W, dilation):
+    return _dilated_name("mis_conv_dilated_fwd_kernel_name", N, Cin, Cout, H, W, dilation)
+
+
+def conv_dilated_dgrad_kernel_name(N, Cin, Cout, H, W, dilation):
+    return _dilated_name("mis_conv_dilated_dgrad_kernel_name", N, Cin, Cout, H, W, dilation)
+
+
+def conv_dilated_wgrad_kernel_name(N, Cin, Cout, H, W, dilation):
+    return _dilated_name("mis_conv_dilated_wgrad_kernel_name", N, Cin, Cout, H, W, dilation)
+
+
+def conv_dilated_fwd(x, wp, bias, y, dilation, dgrad=False):
+    """y = bias + conv3x3(x, dilation = padding = ``dilation``) with packed weights ``wp`` (mode 0, taps = 9).
+    ``dgrad``: ``x`` is the output gradient, ``wp`` the mode-1 pack and ``y`` receives the input gradient (no bias)."""
+    L = _l.load()
+    N, Cx, Cy, H, W, xbs, ybs = _dilated_geom(x, y)
+    prof = PROFILE
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    if dgrad:
+        assert bias is None
+        _l.check(L.mis_conv_dilated_dgrad(_l.ptr(x), xbs, _l.ptr(wp), _l.ptr(y), ybs, N, Cy, Cx, H, W, int(dilation),
+                                          _l.stream_ptr()), "mis_conv_dilated_dgrad")
+    else:
+        _l.check(L.mis_conv_dilated_fwd(_l.ptr(x), xbs, _l.ptr(wp), _l.ptr(bias), _l.ptr(y), ybs, N, Cx, Cy, H, W,
+                                        int(dilation), _l.stream_ptr()), "mis_conv_dilated_fwd")
+    if prof is not None:
+        e1.record()
+        prof.append((conv_dilated_fwd_kernel_name(N, Cx, Cy, H, W, dilation), 2.0 * N * Cy * Cx * 9 * H * W, e0, e1,
+                     4.0 * (N * (Cx + Cy) * H * W + Cy * Cx * 9)))
+
+
+def conv_dilated_wgrad(x, dy, dw, dilation, accumulate=False):
+    """dw[Cout,Cin,3,3] (+)= the weight gradient of the dilated convolution; deterministic."""
+    L = _l.load()
+    N, Cin, Cout, H, W, xbs, dbs = _dilated_geom(x, dy)
+    assert dw.is_contiguous() and dw.numel() == Cout * Cin * 9
+    nb = L.mis_conv_dilated_wgrad_workspace_bytes(N, Cin, Cout, H, W, int(dilation))
+    if nb < 0:
+        _l.check(nb, "mis_conv_dilated_wgrad_workspace_bytes")
+    ws = scratch(nb, "wgrad")
+    prof = PROFILE
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _tag(f"dilated_wgrad:d{dilation}@{W}")
+    _l.check(L.mis_conv_dilated_wgrad(_l.ptr(x), xbs, _l.ptr(dy), dbs, _l.ptr(dw), _l.ptr(ws), ws.numel(), N, Cin, Cout, H, W,
+                                      int(dilation), int(accumulate), _l.stream_ptr()), "mis_conv_dilated_wgrad")
+    if prof is not None:
+        e1.record()
+        prof.append((conv_dilated_wgrad_kernel_name(N, Cin, Cout, H, W, dilation), 2.0 * N * Cout * Cin * 9 * H * W, e0, e1,
+                     4.0 * (N * (Cin + Cout) * H * W + Cout * Cin * 9)))
 
 
 # ------------------------------------------------------- norm + act + dropout

@@ -152,14 +152,20 @@ class Ctx:
 
 
 class ConvOp:
-    def __init__(self, x, y, w, b, ksize, need_dx, bias_grad):
+    def __init__(self, x, y, w, b, ksize, need_dx, bias_grad, dilation=1):
         self.x, self.y, self.w, self.b = x, y, w, b
         self.ksize, self.need_dx, self.bias_grad = tuple(ksize), need_dx, bias_grad
         self.cout, self.cin = w.data.shape[0], w.data.shape[1]
+        # dilation > 1: nn.Conv2d(3x3, dilation = padding = d) on the kernels of conv_dilated.hip (forward, data gradient,
+        # weight gradient).  Such a conv takes none of the fusions keyed on the dense kernels: no Winograd variant, no
+        # epilogue statistics, no fused first layer / data-gradient sums / head (Plan.norm_act, _fuse_dgrad_norm, _fuse_head).
+        self.dilation = int(dilation)
+        if self.dilation != 1 and ops._ksize(self.ksize) != (1, 3, 3):
+            raise RuntimeError(f"dilation {dilation} needs a 3x3 convolution, got kernel {tuple(ksize)}")
         # Winograd F(2^3, 3^3) variant of the forward / of the data gradient (conv_wino.hip), or -1: direct kernel
         N, _, D, H, W = y.shape          # stride 1, 'same': the geometry of x (the plan's input has no buffer yet)
-        self.wino_f = ops.conv_wino_select(N, self.cin, self.cout, D, H, W, self.ksize)
-        self.wino_b = ops.conv_wino_select(N, self.cout, self.cin, D, H, W, self.ksize) if need_dx else -1
+        self.wino_f = ops.conv_wino_select(N, self.cin, self.cout, D, H, W, self.ksize, self.dilation)
+        self.wino_b = ops.conv_wino_select(N, self.cout, self.cin, D, H, W, self.ksize, self.dilation) if need_dx else -1
         self.wp = None
         self.wpd = None
         self.batched = False     # True: the plan repacks all conv weights in one launch (Plan._pack)
@@ -180,6 +186,9 @@ class ConvOp:
                                     out=self.wp)
         # the consumer needs batch statistics unless it is a BatchNorm in eval mode (running statistics)
         stat = self.stat if (self.stat is not None and (self.stat_norm.per_sample or ctx.training)) else None
+        if self.dilation != 1:
+            ops.conv_dilated_fwd(self.x.t, self.wp, None if self.b is None else self.b.data, self.y.t, self.dilation)
+            return
         ops.conv_fwd(self.x.t, self.wp, None if self.b is None else self.b.data, self.y.t, self.cin, self.cout,
                      self.ksize, stat=stat, wino=self.wino_f)
 
@@ -200,11 +209,11 @@ class ConvOp:
             _lib.wait_stream(side, torch.cuda.current_stream())     # dy is final
             with torch.cuda.stream(side):
                 run_deferred(ctx)
-                ops.conv_wgrad(self.x.t, dy, self.w.grad, self.ksize)
+                self._wgrad(dy)
                 if self.b is not None and self.bias_grad:
                     ops.channel_sum(dy, self.b.grad)
         else:
-            ops.conv_wgrad(self.x.t, dy, self.w.grad, self.ksize)
+            self._wgrad(dy)
             if self.b is not None and self.bias_grad:
                 ops.channel_sum(dy, self.b.grad)
         # bias_grad False: the conv feeds a normalisation, its bias gradient is exactly 0
@@ -218,7 +227,7 @@ class ConvOp:
                 # UnetResBlock feeds its input to conv1 AND to the shortcut): data gradient into a scratch, then add
                 if self._dx_tmp is None:
                     self._dx_tmp = torch.empty(self.x.shape, dtype=torch.float32, device="cuda")
-                ops.conv_fwd(dy, self.wpd, None, self._dx_tmp, self.cout, self.cin, self.ksize, wino=self.wino_b)
+                self._dgrad(dy, self._dx_tmp)
                 ops.add(self.x.grad(), self._dx_tmp, self.x.grad())
             elif self.dgrad_norm is not None:
                 n = self.dgrad_norm
@@ -226,9 +235,20 @@ class ConvOp:
                                     self.wino_b)
                 n.ext_ready = True
             else:
-                ops.conv_fwd(dy, self.wpd, None, self.x.grad(), self.cout, self.cin, self.ksize, wino=self.wino_b)
+                self._dgrad(dy, self.x.grad())
             self.x.mark_written()
 
+    def _wgrad(self, dy):
+        if self.dilation != 1:
+            ops.conv_dilated_wgrad(self.x.t, dy, self.w.grad, self.dilation)
+        else:
+            ops.conv_wgrad(self.x.t, dy, self.w.grad, self.ksize)
+
+    def _dgrad(self, dy, dx):
+        if self.dilation != 1:
+            ops.conv_dilated_fwd(dy, self.wpd, None, dx, self.dilation, dgrad=True)
+        else:
+            ops.conv_fwd(dy, self.wpd, None, dx, self.cout, self.cin, self.ksize, wino=self.wino_b)
 
     def _bwd_data_only(self):
         """The backward of a frozen network's conv: the data gradient, written (a frozen head is a chain: its activations
@@ -239,7 +259,7 @@ class ConvOp:
         if not self.batched:
             self.wpd = ops.conv_pack(self.w.data, ops.conv_wino_pack_mode(self.wino_b, True) if self.wino_b >= 0 else 1,
                                      out=self.wpd)
-        ops.conv_fwd(self.y.grad(), self.wpd, None, self.x.grad(), self.cout, self.cin, self.ksize, wino=self.wino_b)
+        self._dgrad(self.y.grad(), self.x.grad())
         self.x.mark_written()
 
 
@@ -737,8 +757,8 @@ class Plan(PlanBase):
         self.acts.append(a)
         return a
 
-    def conv(self, x, y, w, b, ksize, need_dx=True, bias_grad=True):
-        self.ops.append(ConvOp(x, y, w, b, ksize, need_dx, bias_grad))
+    def conv(self, x, y, w, b, ksize, need_dx=True, bias_grad=True, dilation=1):
+        self.ops.append(ConvOp(x, y, w, b, ksize, need_dx, bias_grad, dilation))
         self.ops[-1].frozen = bool(getattr(self.net, "frozen", False))
         return y
 
@@ -749,7 +769,7 @@ class Plan(PlanBase):
         op.frozen = bool(getattr(self.net, "frozen", False))
         # conv -> norm: let the conv epilogue produce the statistics (no separate pass over the conv output)
         prev = self.ops[-1] if self.ops else None
-        if FUSE_CONV_STATS and not no_norm and type(prev) is ConvOp and prev.y is x:
+        if FUSE_CONV_STATS and not no_norm and type(prev) is ConvOp and prev.y is x and prev.dilation == 1:
             N, C, D, H, W = x.shape
             T = ops.conv_stat_tiles(N, prev.cin, prev.cout, D, H, W, prev.ksize, wino=prev.wino_f)
             if T > 0:
@@ -757,7 +777,7 @@ class Plan(PlanBase):
                 prev.stat = (part, T, C * T) if per_sample else (part, N * T, T)
                 prev.stat_norm = op
                 op.fused = (part, T)
-        if (FUSE_FIRST and type(prev) is ConvOp and prev.y is x and not prev.need_dx and prev.cin == 1
+        if (FUSE_FIRST and type(prev) is ConvOp and prev.y is x and not prev.need_dx and prev.cin == 1 and prev.dilation == 1
                 and prev.ksize in ((3, 3, 3), (1, 3, 3)) and drop_p == 0.0 and cg == 1 and not no_norm
                 and not (per_sample and (gamma is not None or beta is not None)) and x.parent is None
                 and ops.conv_wgrad_cin1_norm_eligible(x.shape[0], prev.cout, *x.shape[2:])):
@@ -869,6 +889,8 @@ class Plan(PlanBase):
         for conv in self.ops:
             if type(conv) is not ConvOp or not conv.need_dx or conv.wino_b not in (0, 1) or conv.ksize != (3, 3, 3):
                 continue
+            if conv.dilation != 1:
+                continue
             if conv.fused_into is not None or conv.x.parent is not None:
                 continue
             norm = next((o for o in self.ops if type(o) is NormActOp and o.y is conv.x), None)
@@ -902,6 +924,8 @@ class Plan(PlanBase):
             return
         norm, conv = self.ops[-2], self.ops[-1]
         if type(norm) is not NormActOp or type(conv) is not ConvOp or conv.ksize != (1, 1, 1) or conv.x is not norm.y:
+            return
+        if conv.dilation != 1:
             return
         if norm.y.parent is not None or conv.y is not self.out or not conv.need_dx or norm.res is not None:
             return

@@ -7,17 +7,20 @@ returned already on the device, unknown keys return ``None``.  Differences, on p
   configuration from ``net_factory.swin_config`` (default: the reference's lite yaml with
   ``PRETRAIN_CKPT=None``) instead of module-level ``args``/``config`` globals;
 * ``unet`` and ``ViT_Seg`` are on the hand-written HIP hot path, and so are ``classifier`` and ``projector``, the frozen
-  heads of the contrastive cross-teaching scripts (networks/projector.py; built with their defaults, as in the reference).
-  The other keys of the reference (enet, unet_ds, unet_cct, unet_urpc, efficient_unet, pnet, nnUNet, preunet) belong to
+  heads of the contrastive cross-teaching scripts (networks/projector.py; built with their defaults, as in the reference),
+  and ``pnet`` (networks/pnet.py: ``PNet2D(in_chns, class_num, 64, [1, 2, 4, 8, 16])``, its dilated 3x3 convolutions on
+  csrc/conv_dilated.hip).
+  The other keys of the reference (enet, unet_ds, unet_cct, unet_urpc, efficient_unet, nnUNet, preunet) belong to
   other SSL methods / backbones that SURVEY.md s.8 marks out of scope; they raise ``NotImplementedError`` naming the
   scope decision instead of silently returning something else.
 """
 from config import lite_config
+from networks.pnet import PNet2D
 from networks.projector import classifier, projectors
 from networks.unet import UNet
 from networks.vision_transformer import SwinUnet as ViT_seg
 
-_OUT_OF_SCOPE = ("enet", "unet_ds", "unet_cct", "unet_urpc", "efficient_unet", "pnet", "nnUNet", "preunet")
+_OUT_OF_SCOPE = ("enet", "unet_ds", "unet_cct", "unet_urpc", "efficient_unet", "nnUNet", "preunet")
 
 swin_config = None   # set to a config.get_config(args) result to override the lite defaults
 
@@ -28,6 +31,8 @@ def net_factory(net_type="unet", in_chns=1, class_num=3):
     elif net_type == "ViT_Seg":
         cfg = swin_config if swin_config is not None else lite_config()
         net = ViT_seg(cfg, img_size=cfg.DATA.IMG_SIZE, num_classes=class_num).cuda()
+    elif net_type == "pnet":
+        net = PNet2D(in_chns, class_num, 64, [1, 2, 4, 8, 16]).cuda()
     elif net_type == "classifier":
         net = classifier().cuda()
     elif net_type == "projector":
