@@ -1269,3 +1269,102 @@ def sq_edt(seeds_u8):
     out = torch.empty(seeds_u8.shape, dtype=torch.int32, device=seeds_u8.device)
     _l.check(L.mis_sq_edt(_l.ptr(seeds_u8), ndim, D, H, W, _l.ptr(out), _l.ptr(ws), nbytes, _l.stream_ptr()), "mis_sq_edt")
     return out
+
+
+# ------------------------------------------------- grid attention gates, integer up-sampling (csrc/attention_gate.hip)
+def _gate_geom(x, att, wide):
+    """(N, G, C, D, H, W, d, h, w, x_bs, att_bs, wide_bs): ``x`` [N,C,D,H,W], ``att`` [N,G,d,h,w], ``wide`` [N,G*C,D,H,W]."""
+    N, C, D, H, W, _, xbs = _geom(x)
+    Na, G, d, h, w, _, abs_ = _geom(att)
+    Nw, GC, Dw, Hw, Ww, _, wbs = _geom(wide)
+    if Na != N or Nw != N or GC != G * C or (Dw, Hw, Ww) != (D, H, W):
+        raise RuntimeError(f"attention gate: x {tuple(x.shape)}, att {tuple(att.shape)} and the gated tensor "
+                           f"{tuple(wide.shape)} do not belong together (MIS_ERR_ARG)")
+    return N, G, C, D, H, W, d, h, w, xbs, abs_, wbs
+
+
+def attn_gate_map_fwd(theta, phi, psi_w, psi_b, att):
+    """att[N,G,d,h,w] = sigmoid(psi_b[g] + sum_i psi_w[g,i] relu(theta + phi)[N, g Ci + i]); psi_w [G,Ci], psi_b [G] contiguous."""
+    L = _l.load()
+    N, GCi, d, h, w, _, tbs = _geom(theta)
+    Np, GCp, dp, hp, wp_, _, pbs = _geom(phi)
+    Na, G, da, ha, wa, _, abs_ = _geom(att)
+    if (Np, GCp, dp, hp, wp_) != (N, GCi, d, h, w) or (Na, da, ha, wa) != (N, d, h, w) or GCi % G or psi_b.numel() != G \
+            or psi_w.numel() != GCi or not psi_w.is_contiguous() or not psi_b.is_contiguous():
+        raise RuntimeError(f"attention gate map: theta {tuple(theta.shape)}, phi {tuple(phi.shape)}, att {tuple(att.shape)}, "
+                           f"psi {tuple(psi_w.shape)} / {tuple(psi_b.shape)} do not belong together (MIS_ERR_ARG)")
+    _l.check(L.mis_attn_gate_map_fwd(_l.ptr(theta), tbs, _l.ptr(phi), pbs, _l.ptr(psi_w), _l.ptr(psi_b), _l.ptr(att), abs_, N, G,
+                                     GCi // G, d, h, w, _l.stream_ptr()), "mis_attn_gate_map_fwd")
+
+
+def attn_gate_map_bwd(datt, att, theta, phi, psi_w, df, dpsi_w, dpsi_b, dphi_b=None, accumulate=False):
+    """df[N,G*Ci,d,h,w] = psi_w dpre [theta + phi > 0] with dpre = datt att (1 - att); dpsi_w (+)= sum relu(theta + phi) dpre,
+    dpsi_b (+)= sum dpre, dphi_b[G*Ci] (+)= sum df (the phi convolution's bias gradient; None: not wanted).  Deterministic."""
+    L = _l.load()
+    N, GCi, d, h, w, _, tbs = _geom(theta)
+    pbs, fbs = _geom(phi)[6], _geom(df)[6]
+    Na, G, da, ha, wa, _, abs_ = _geom(att)
+    dbs = _geom(datt)[6]
+    if (tuple(phi.shape) != tuple(theta.shape) or tuple(df.shape) != tuple(theta.shape) or tuple(datt.shape) != tuple(att.shape)
+            or (Na, da, ha, wa) != (N, d, h, w) or GCi % G or psi_w.numel() != GCi or dpsi_w.numel() != GCi
+            or dpsi_b.numel() != G or not (psi_w.is_contiguous() and dpsi_w.is_contiguous() and dpsi_b.is_contiguous())
+            or (dphi_b is not None and (dphi_b.numel() != GCi or not dphi_b.is_contiguous()))):
+        raise RuntimeError(f"attention gate map backward: theta {tuple(theta.shape)}, att {tuple(att.shape)}, datt "
+                           f"{tuple(datt.shape)}, df {tuple(df.shape)} do not belong together (MIS_ERR_ARG)")
+    nb = L.mis_attn_gate_map_bwd_workspace_bytes(N, G, GCi // G, d, h, w)
+    if nb < 0:
+        _l.check(nb, "mis_attn_gate_map_bwd_workspace_bytes")
+    ws = scratch(nb, "attn_gate")
+    _l.check(L.mis_attn_gate_map_bwd(_l.ptr(datt), dbs, _l.ptr(att), abs_, _l.ptr(theta), tbs, _l.ptr(phi), pbs, _l.ptr(psi_w),
+                                     _l.ptr(df), fbs, _l.ptr(dpsi_w), _l.ptr(dpsi_b), _l.ptr(dphi_b), _l.ptr(ws), ws.numel(), N, G,
+                                     GCi // G, d, h, w, int(accumulate), _l.stream_ptr()), "mis_attn_gate_map_bwd")
+
+
+def attn_gate_apply_fwd(x, att, y):
+    """y[N, g C + c] = up2(att[N, g]) * x[N, c]: trilinear x2 (align_corners=False) of the attention maps, x read once."""
+    L = _l.load()
+    N, G, C, D, H, W, d, h, w, xbs, abs_, ybs = _gate_geom(x, att, y)
+    _l.check(L.mis_attn_gate_apply_fwd(_l.ptr(x), xbs, _l.ptr(att), abs_, _l.ptr(y), ybs, N, G, C, D, H, W, d, h, w,
+                                       _l.stream_ptr()), "mis_attn_gate_apply_fwd")
+
+
+def attn_gate_apply_bwd(dy, x, att, dx, datt, accumulate=False):
+    """dx (+)= sum_g up2(att_g) dy_g;  datt = up2^T(sum_c dy x).  dy and x are read once."""
+    L = _l.load()
+    N, G, C, D, H, W, d, h, w, xbs, abs_, dybs = _gate_geom(x, att, dy)
+    if tuple(dx.shape) != tuple(x.shape) or tuple(datt.shape) != tuple(att.shape):
+        raise RuntimeError(f"attention gate backward: dx {tuple(dx.shape)} / datt {tuple(datt.shape)} do not match x "
+                           f"{tuple(x.shape)} / att {tuple(att.shape)} (MIS_ERR_ARG)")
+    dxbs, dabs = _geom(dx)[6], _geom(datt)[6]
+    nb = L.mis_attn_gate_apply_bwd_workspace_bytes(N, G, D, H, W)
+    if nb < 0:
+        _l.check(nb, "mis_attn_gate_apply_bwd_workspace_bytes")
+    ws = scratch(nb, "attn_gate")
+    _l.check(L.mis_attn_gate_apply_bwd(_l.ptr(dy), dybs, _l.ptr(x), xbs, _l.ptr(att), abs_, _l.ptr(dx), dxbs, _l.ptr(datt), dabs,
+                                       _l.ptr(ws), ws.numel(), N, G, C, D, H, W, d, h, w, int(accumulate), _l.stream_ptr()),
+             "mis_attn_gate_apply_bwd")
+
+
+def _up_int_geom(coarse, fine, scale):
+    N, K, d, h, w, _, cbs = _geom(coarse)
+    Nf, Kf, D, H, W, _, fbs = _geom(fine)
+    if (Nf, Kf) != (N, K) or (D, H, W) != (scale * d, scale * h, scale * w):
+        raise RuntimeError(f"upsample x{scale}: {tuple(coarse.shape)} and {tuple(fine.shape)} do not belong together "
+                           "(MIS_ERR_ARG)")
+    return N, K, d, h, w, cbs, fbs
+
+
+def upsample_int_fwd(x, y, scale):
+    """y = trilinear up-sampling of x by ``scale`` in {2, 4, 8} per axis, align_corners=False."""
+    L = _l.load()
+    N, K, d, h, w, xbs, ybs = _up_int_geom(x, y, int(scale))
+    _l.check(L.mis_upsample_int_fwd(_l.ptr(x), xbs, _l.ptr(y), ybs, N, K, d, h, w, int(scale), _l.stream_ptr()),
+             "mis_upsample_int_fwd")
+
+
+def upsample_int_bwd(dy, dx, scale, accumulate=False):
+    """dx (+)= the adjoint of upsample_int_fwd applied to dy (gather form: deterministic)."""
+    L = _l.load()
+    N, K, d, h, w, dxbs, dybs = _up_int_geom(dx, dy, int(scale))
+    _l.check(L.mis_upsample_int_bwd(_l.ptr(dy), dybs, _l.ptr(dx), dxbs, N, K, d, h, w, int(scale), int(accumulate),
+                                    _l.stream_ptr()), "mis_upsample_int_bwd")

@@ -406,15 +406,87 @@ class MaxPoolOp:
 
 
 class UpsampleOp:
-    def __init__(self, x, y, align_corners):
-        self.x, self.y, self.align = x, y, align_corners
+    """Linear up-sampling by ``scale`` per axis: 2 on the decoder's kernels (mis_upsample2_*), 4 and 8 -- the deep-supervision
+    heads of the Attention U-Net, trilinear with align_corners=False -- on mis_upsample_int_*."""
+
+    def __init__(self, x, y, align_corners, scale=2):
+        self.x, self.y, self.align, self.scale = x, y, align_corners, int(scale)
+        if self.scale not in (2, 4, 8) or (self.scale != 2 and align_corners):
+            raise RuntimeError(f"up-sampling by {scale} (align_corners={align_corners}) of {x.shape} has no kernel")
+        # mis_upsample2_* read D == 1 as "2-D": a 3-D volume of depth 1 that doubles to depth 2 (the centre of a 16^3 input)
+        # is not theirs, they would fill a [1, 2H, 2W] volume
+        self.two = self.scale == 2 and not (x.shape[2] == 1 and y.shape[2] == 2 and not align_corners)
 
     def fwd(self, ctx):
-        ops.upsample2_fwd(self.x.t, self.y.t, self.align)
+        if self.two:
+            ops.upsample2_fwd(self.x.t, self.y.t, self.align)
+        else:
+            ops.upsample_int_fwd(self.x.t, self.y.t, self.scale)
 
     def bwd(self, ctx):
-        ops.upsample2_bwd(self.y.grad(), self.x.grad(), self.align, accumulate=self.x.written)
+        if self.two:
+            ops.upsample2_bwd(self.y.grad(), self.x.grad(), self.align, accumulate=self.x.written)
+        else:
+            ops.upsample_int_bwd(self.y.grad(), self.x.grad(), self.scale, accumulate=self.x.written)
         self.x.mark_written()
+
+
+class GateMapOp:
+    """att[N, g] = sigmoid(psi_g(relu(theta + phi)[N, g Ci : (g + 1) Ci])) for the G grid attention gates of one level,
+    stacked along channels (reference grid_attention_layer.py:97-100; mis_attn_gate_map_*).  ``psi``: [(weight, bias)] per
+    gate; ``phi_b``: the biases of the gates' phi convolutions, whose gradients -- channel sums of the buffer the backward
+    writes -- its launch forms on the way (those ConvOps are built with bias_grad=False).  The reference keeps each gate's
+    psi in a module of its own, so the parameters of two gates are not adjacent in the flat buffer: one launch per gate on
+    the gate's channel slices (the coarse grid: 1 / 8 of the voxels of the level).  The backward writes ONE buffer, the
+    gradient at theta and at phi alike: ``phi.g`` is ``theta.g``."""
+
+    def __init__(self, theta, phi, att, psi, phi_b):
+        self.theta, self.phi, self.att = theta, phi, att
+        self.G, self.Ci = len(psi), theta.shape[1] // len(psi)
+        assert tuple(theta.shape) == tuple(phi.shape) and att.shape[1] == self.G and theta.shape[1] == self.G * self.Ci
+        assert theta.parent is None and phi.parent is None
+        for g, (w, b) in enumerate(psi):         # attributes: dist.param_progress finds an op's parameters in vars(op)
+            setattr(self, f"psi_w{g}", w)
+            setattr(self, f"psi_b{g}", b)
+            setattr(self, f"phi_b{g}", phi_b[g])
+        phi.g = theta.grad()
+
+    def _gate(self, g):
+        c = slice(g * self.Ci, (g + 1) * self.Ci)
+        return c, slice(g, g + 1), getattr(self, f"psi_w{g}"), getattr(self, f"psi_b{g}")
+
+    def fwd(self, ctx):
+        for g in range(self.G):
+            c, a, w, b = self._gate(g)
+            ops.attn_gate_map_fwd(self.theta.t[:, c], self.phi.t[:, c], w.data.view(1, self.Ci), b.data, self.att.t[:, a])
+
+    def bwd(self, ctx):
+        datt, df = self.att.grad(), self.theta.grad()
+        for g in range(self.G):
+            c, a, w, b = self._gate(g)
+            ops.attn_gate_map_bwd(datt[:, a], self.att.t[:, a], self.theta.t[:, c], self.phi.t[:, c], w.data.view(1, self.Ci),
+                                  df[:, c], w.grad.view(-1), b.grad, getattr(self, f"phi_b{g}").grad)
+        self.theta.mark_written()
+        self.phi.mark_written()
+
+
+class GateApplyOp:
+    """y[N, g C + c] = up2(att[N, g]) * x[N, c] for the G gates of one level: x is read once forward and -- with dy -- once
+    backward (mis_attn_gate_apply_*; reference grid_attention_layer.py:103-104).  x has other readers (the theta
+    convolutions, the max-pool): its gradient is accumulated when one of them has written it."""
+
+    def __init__(self, x, att, y):
+        self.x, self.att, self.y = x, att, y
+        assert y.shape[1] == att.shape[1] * x.shape[1]
+
+    def fwd(self, ctx):
+        ops.attn_gate_apply_fwd(self.x.t, self.att.t, self.y.t)
+
+    def bwd(self, ctx):
+        assert not self.att.written
+        ops.attn_gate_apply_bwd(self.y.grad(), self.x.t, self.att.t, self.x.grad(), self.att.grad(), accumulate=self.x.written)
+        self.x.mark_written()
+        self.att.mark_written()
 
 
 class DownConvOp:
@@ -846,8 +918,16 @@ class Plan(PlanBase):
         self.ops.append(op)
         return y
 
-    def upsample(self, x, y, align_corners):
-        self.ops.append(UpsampleOp(x, y, align_corners))
+    def upsample(self, x, y, align_corners, scale=2):
+        self.ops.append(UpsampleOp(x, y, align_corners, scale))
+        return y
+
+    def gate_map(self, theta, phi, att, psi, phi_b):
+        self.ops.append(GateMapOp(theta, phi, att, psi, phi_b))
+        return att
+
+    def gate_apply(self, x, att, y):
+        self.ops.append(GateApplyOp(x, att, y))
         return y
 
     # ---- what this plan does in front of a walk ----
