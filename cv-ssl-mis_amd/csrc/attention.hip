@@ -104,6 +104,15 @@ extern "C" int mis_window_attention_table_partials(int B, int H, int W, int nH, 
     return MIS_ERR_UNSUPPORTED;
 }
 
+// Which kernels serve a window-attention launch of this geometry whose widest token buffer has a row stride of ldmax floats
+// (0: no buffer): 0 = fp32 MFMA, 1 = bf16x3 MFMA, 2 = the vector pipe; negative = MIS_ERR_*.  The launchers read the same
+// function (attn_path in attention_impl.inc), under the precision mask and MIS_ATTN_VALU of the moment.  Nothing is launched.
+extern "C" int mis_window_attention_path(int B, int H, int W, int nH, long long ldmax, int window) {
+    if (window == 7) return ws7::window_attention_path(B, H, W, nH, ldmax);
+    if (window == 8) return ws8::window_attention_path(B, H, W, nH, ldmax);
+    return MIS_ERR_UNSUPPORTED;
+}
+
 // the window-7 entry points of ABI version 1
 extern "C" int mis_window_attention_fwd(const float* qkv, long long ldq, float* out, long long ldo,
                                         const float* bias_table, int B, int H, int W, int nH, int shift, float scale,

@@ -971,6 +971,33 @@ bool use_valu() {
     return v;
 }
 
+// Which kernels serve a launch, decided HERE and nowhere else: the forward and backward launchers, the layout of the backward's
+// table partials (window_attention_table_partials) and the label mis_window_attention_path gives a test all read this function,
+// so they cannot diverge.  ldmax = the largest row stride (in floats) among the launch's token buffers; 0 = no buffer (the
+// table-gradient half on its own, the shape queries).
+//
+// Why < 2^31 BYTES is sufficient for the MFMA kernels' 32-bit indices: every global access there is base + e with an int element
+// offset e = (tb + srow[r]) * ld + col0 + d (load_l1 / load_l2 / store_l2 and the dQ operand loads).  tb + srow[r] is a token
+// number < B*H*W (srow holds valid tokens in all 64 entries: rows >= NTOK alias row 0, and their offset is formed although
+// never dereferenced), col0 + d < ld for any buffer that holds its columns, so 0 <= e < B*H*W*ld <= B*H*W*ldmax < 2^29 elements:
+// no intermediate of the int arithmetic leaves [0, 2^31), and the scaling to bytes happens in the 64-bit pointer addition.  The
+// bound is four times tighter than the arithmetic needs; it is the documented condition and stays.  The partial-table and dS
+// offsets are 64-bit in both generations.
+enum { ATTN_PATH_MFMA_F32 = 0, ATTN_PATH_MFMA_BF3 = 1, ATTN_PATH_VALU = 2 };
+
+int attn_path(int B, int H, int W, long long ldmax) {
+    const bool small = (long long)B * H * W * ldmax * 4 < (1LL << 31);
+    if (use_valu() || !small) return ATTN_PATH_VALU;
+    return (mis_split_precision_mask() & 4) ? ATTN_PATH_MFMA_BF3 : ATTN_PATH_MFMA_F32;
+}
+
+// the label: ATTN_PATH_* for this geometry and stride, or a negative MIS_ERR_*
+int window_attention_path(int B, int H, int W, int nH, long long ldmax) {
+    if (B <= 0 || H <= 0 || W <= 0 || nH <= 0 || ldmax < 0) return MIS_ERR_ARG;
+    if (H % WS || W % WS) return MIS_ERR_UNSUPPORTED;
+    return attn_path(B, H, W, ldmax);
+}
+
 
 int window_attention_fwd(const float* qkv, long long ldq, float* out, long long ldo,
                                         const float* bias_table, int B, int H, int W, int nH, int shift, float scale,
@@ -981,15 +1008,13 @@ int window_attention_fwd(const float* qkv, long long ldq, float* out, long long 
     if (ldq % 4 || ldo % 4 || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return MIS_ERR_UNSUPPORTED;
     AttnArgs a{qkv, ldq, out, ldo, bias_table, B, H, W, nH, shift, scale};
     const long long units = (long long)B * (H / WS) * (W / WS) * nH;
-    // the MFMA kernels index with 32-bit element offsets
-    const bool small = (long long)B * H * W * (ldq > ldo ? ldq : ldo) * 4 < (1LL << 31);
-    if (use_valu() || !small)
+    const int path = attn_path(B, H, W, ldq > ldo ? ldq : ldo);
+    if (path == ATTN_PATH_VALU)
         hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)mis_cdiv(units, 4)), dim3(256), 0, stream, a, units);
+    else if (path == ATTN_PATH_MFMA_BF3)
+        hipLaunchKernelGGL(attn_fwd_mfma_kernel<1>, dim3((unsigned)mis_cdiv(units, 4)), dim3(256), 0, stream, a, units);
     else
-        if (mis_split_precision_mask() & 4)
-            hipLaunchKernelGGL(attn_fwd_mfma_kernel<1>, dim3((unsigned)mis_cdiv(units, 4)), dim3(256), 0, stream, a, units);
-        else
-            hipLaunchKernelGGL(attn_fwd_mfma_kernel<0>, dim3((unsigned)mis_cdiv(units, 4)), dim3(256), 0, stream, a, units);
+        hipLaunchKernelGGL(attn_fwd_mfma_kernel<0>, dim3((unsigned)mis_cdiv(units, 4)), dim3(256), 0, stream, a, units);
     return mis_launch_status();
 }
 
@@ -1017,19 +1042,23 @@ int window_attention_bwd(const float* qkv, long long ldq, const float* dout, lon
     const int nW = (H / WS) * (W / WS);
     long long ldmax = ldq > ldo ? ldq : ldo;
     if (lddq > ldmax) ldmax = lddq;
-    const bool small = (long long)B * H * W * ldmax * 4 < (1LL << 31);
-    if (phases != 3 && !small && !use_valu()) return MIS_ERR_UNSUPPORTED;      // see phase 2 below: use the one-call form
+    // (the table-gradient half on its own has no token buffer: ldmax = 0)
+    const int path = attn_path(B, H, W, ldmax);
+    // the split form is refused where the buffers, not MIS_ATTN_VALU, put the launch on the vector pipe: the half that forms the
+    // table gradient does not see the strides and would read MFMA-layout partials (use the one-call form)
+    if (phases != 3 && path == ATTN_PATH_VALU && !use_valu()) return MIS_ERR_UNSUPPORTED;
     if (phases & 1) {
-        if (use_valu() || !small)
+        if (path == ATTN_PATH_VALU)
             hipLaunchKernelGGL(attn_bwd_kernel, dim3(chunks * nW * nH), dim3(64), 0, stream, a);
+        else if (path == ATTN_PATH_MFMA_BF3)
+            hipLaunchKernelGGL(attn_bwd_mfma_kernel<1>, dim3(chunks * nW * nH), dim3(64), 0, stream, a);
         else
-            if (mis_split_precision_mask() & 4) hipLaunchKernelGGL(attn_bwd_mfma_kernel<1>, dim3(chunks * nW * nH), dim3(64), 0, stream, a);
-            else hipLaunchKernelGGL(attn_bwd_mfma_kernel<0>, dim3(chunks * nW * nH), dim3(64), 0, stream, a);
+            hipLaunchKernelGGL(attn_bwd_mfma_kernel<0>, dim3(chunks * nW * nH), dim3(64), 0, stream, a);
     }
     if (phases & 2) {
-        // the layout of the partials follows the kernel of phase 1.  The split form (phases 1 and 2 in separate calls) is refused
-        // above for buffers the MFMA kernel cannot index, so `small` is known here
-        if (use_valu() || !small) {
+        // the layout of the partials follows the kernel of phase 1: the same `path` in the one-call form, and in the split form
+        // the refusal above leaves only MIS_ATTN_VALU to select the vector pipe, which both halves see
+        if (path == ATTN_PATH_VALU) {
             float* dsum = a.dS_part + (long long)chunks * nW * nH * (NTOK * NTOK);
             hipLaunchKernelGGL(attn_ds_reduce_kernel, dim3((NTOK * NTOK + 63) / 64, nH), dim3(1024), 0, stream, a.dS_part,
                                chunks * nW, nH, dsum);
@@ -1048,7 +1077,7 @@ int window_attention_bwd(const float* qkv, long long ldq, const float* dout, lon
 // are selected (MIS_ATTN_VALU), whose workspace holds dS blocks.
 int window_attention_table_partials(int B, int H, int W, int nH, long long* rows, int* cols) {
     if (B <= 0 || H <= 0 || W <= 0 || nH <= 0 || H % WS || W % WS || !rows || !cols) return MIS_ERR_ARG;
-    if (use_valu()) return MIS_ERR_UNSUPPORTED;
+    if (attn_path(B, H, W, 0) == ATTN_PATH_VALU) return MIS_ERR_UNSUPPORTED;
     *rows = mis_cdiv(B, bwd_chunk(B, H, W, nH)) * (H / WS) * (W / WS);
     *cols = NBIAS * nH;
     return MIS_OK;

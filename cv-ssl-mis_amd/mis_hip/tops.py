@@ -657,6 +657,19 @@ def window_attention_bwd(qkv, dout, dqkv, table, dtable, B, H, W, nH, shift, sca
                                            _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_window_attention_bwd_ws")
 
 
+ATTN_PATHS = ("mfma_f32", "mfma_bf16x3", "valu")
+
+
+def window_attention_path(B, H, W, nH, *buffers, window=7):
+    """Which kernels serve a window-attention launch over these token buffers (none: the table-gradient half / the shape
+    queries): one of ATTN_PATHS, as the launchers themselves decide it (mis_window_attention_path)."""
+    ldmax = max((_mat(t)[2] for t in buffers), default=0)
+    p = int(_l.load().mis_window_attention_path(B, H, W, nH, ldmax, window))
+    if p < 0:
+        _l.check(p, "mis_window_attention_path")
+    return ATTN_PATHS[p]
+
+
 def window_attention_workspace(B, H, W, nH, window=7):
     L = _l.load()
     nb = L.mis_window_attention_workspace_bytes_ws(B, H, W, nH, window)

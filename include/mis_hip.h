@@ -787,6 +787,12 @@ int mis_window_attention_bwd_parts_ws(const float* qkv, long long ldq, const flo
 int mis_window_attention_dtable_ws(void* workspace, long long workspace_bytes, float* dbias_table, int accumulate_table,
                                    int B, int H, int W, int nH, int window, mis_stream_t stream);
 int mis_window_attention_table_partials(int B, int H, int W, int nH, int window, long long* rows, int* cols);
+/* Which kernels serve a window-attention launch (host-side query, nothing is launched): 0 = fp32 MFMA, 1 = bf16x3 MFMA (bit 2 of
+ * mis_gemm_set_split_precision), 2 = the first-generation vector-pipe kernels (MIS_ATTN_VALU in the environment, or token
+ * buffers of B*H*W*ldmax*4 >= 2^31 bytes, which the MFMA kernels' 32-bit element offsets do not cover); negative = MIS_ERR_*.
+ * ldmax = the largest row stride in floats among qkv / out / dout / dqkv of the launch, 0 for none.  The forward, the backward
+ * and mis_window_attention_table_partials decide through the same function. */
+int mis_window_attention_path(int B, int H, int W, int nH, long long ldmax, int window);
 
 /* ---- UNETR (reference code/networks/unetr.py, built from MONAI blocks that are NOT vendored in the reference:
  * parity of these entry points is pinned to a torch restatement of the published algorithm only) --------------------

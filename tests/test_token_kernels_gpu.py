@@ -363,8 +363,10 @@ def _ref_window_attention(qkv, table, B, H, W, nH, shift, scale, ws=7):
 
 @pytest.mark.parametrize("B,H,W,nH,shift,ws", [(2, 14, 14, 3, 0, 7), (3, 14, 21, 2, 3, 7), (2, 7, 7, 6, 0, 7),
                                                 (9, 28, 28, 3, 3, 7),
-                                                # enough (sample, window, head) units that the backward sums dS over 4
-                                                # samples per wave, with a ragged last chunk (18 = 4*4 + 2)
+                                                # 3456 (sample, window, head) units: several rounds of resident waves, one
+                                                # table partial per unit (the MFMA backward runs with bwd_chunk = 1; summing dS
+                                                # over several samples per wave, with a ragged last chunk, is the vector-pipe
+                                                # backward under MIS_ATTN_VALU: tests/test_attention_edges_gpu.py runs it)
                                                 (18, 56, 56, 3, 3, 7),
                                                 # window 8 (64 tokens: IMG_SIZE 256 / WINDOW_SIZE 8), shift 4
                                                 (2, 16, 16, 3, 0, 8), (3, 16, 24, 2, 4, 8), (2, 8, 8, 6, 0, 8),
