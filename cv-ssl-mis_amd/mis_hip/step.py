@@ -337,9 +337,9 @@ class UAMTTrainer(_TeacherStudentStep):
     _rep_in = None
     _mean_probs = None
 
-    def __init__(self, model, ema_model, *, use_graph=False, use_tape=None, **kw):
-        # eager only, whatever the caller asks for (run_training passes both switches to every trainer class): the MC passes
-        # cycle the teacher through RNG sub-streams set from Python, which a recorded step would not repeat
+    def __init__(self, model, ema_model, *, use_tape=None, **kw):
+        # eager only, whatever the caller asks for: the MC passes cycle the teacher through RNG sub-streams set from
+        # Python, which a recorded step would not repeat
         super().__init__(model, ema_model, use_tape=False, **kw)
 
     def _run(self, volume, label, noise, mc_noise):
@@ -412,10 +412,10 @@ class ICTTrainer(_TeacherStudentStep):
     TRAIN_MODE = "ICT runs both networks in train mode (the reference never calls ema_model.eval())"
     _mix_in = None
 
-    def __init__(self, model, ema_model, *, ict_alpha=0.2, use_graph=False, **kw):
+    def __init__(self, model, ema_model, *, ict_alpha=0.2, **kw):
         if not float(ict_alpha) > 0.0:
             raise ValueError(f"ict_alpha must be > 0, got {ict_alpha}")
-        super().__init__(model, ema_model, **kw)      # (use_graph: accepted from run_training; replays go through the tape)
+        super().__init__(model, ema_model, **kw)
         self.ict_alpha = float(ict_alpha)
         self.mix_factors = None     # [M] device tensor: the factors of the last step
 
@@ -486,9 +486,8 @@ class FixMatchTrainer(_TeacherStudentStep):
     TRAIN_MODE = "FixMatch runs both passes in train mode (the reference never calls .eval() inside the loop)"
     _strong_in = None
 
-    def __init__(self, model, ema_model, *, conf_thresh=0.8, use_graph=False, **kw):
-        kw.pop("cons_start_iter", None)           # (run_training-style callers pass it; FixMatch has no gate)
-        super().__init__(model, ema_model, **kw)  # (use_graph: accepted, replays go through the tape)
+    def __init__(self, model, ema_model, *, conf_thresh=0.8, **kw):
+        super().__init__(model, ema_model, **kw)
         self._bucketer = None                     # two backwards fill the flat gradient: one exchange after the second
         self.conf_thresh = float(conf_thresh)
         self.jitter_factors = None                # [B, 3] device tensor: (beta, gamma, order) of the last step

@@ -1,16 +1,22 @@
-"""Shared driver of the ``train_mean_teacher_{2D,3D}.py`` command lines.
+"""Shared driver of all ``train_*.py`` command lines: Mean Teacher, UA-MT, ICT and deep co-training (``run_training``),
+cross teaching, cross pseudo supervision and CNN-meets-ViT (``run_cross_teaching``), contrastive cross teaching
+(``run_contrastive_cross``), triple view (``run_triple_view``) and FixMatch (``run_fixmatch``).
 
-Keeps what the reference scripts do around the hot loop (seeding, snapshot directory, ``log.txt``,
-periodic checkpoints with the reference's file names, the two-stream "labeled first" batch contract)
-and replaces the loop body by ``MeanTeacherTrainer.step``.  Batches come from the dataset under ``--root_path``
-held resident in HBM (dataloaders/: two-stream sampler + one augmentation gather launch per batch) or, when no
-dataset is there, from a synthetic two-stream source with the reference's shapes/dtypes.
+Keeps what the reference scripts do around the hot loop (seeding, snapshot directory, ``log.txt``, the scalars, the
+in-training validation, periodic checkpoints with the reference's file names, the two-stream "labeled first" batch
+contract) and replaces the loop body by the ``step`` of a trainer of ``mis_hip.step``.  There is ONE loop (``run`` and its
+core ``train_loop``); each ``run_*`` only describes its method as a ``Method`` and calls it.  Batches come from the dataset
+under ``--root_path`` held resident in HBM (dataloaders/: two-stream sampler + one augmentation gather launch per batch) or,
+when no dataset is there, from a synthetic two-stream source with the reference's shapes/dtypes.
 """
+import dataclasses
 import logging
 import os
 import random
 import sys
 import time
+import types
+import typing
 
 import numpy as np
 import torch
@@ -220,8 +226,10 @@ class Validator:
     ``resume`` broadcasts (train_common.broadcast_model_state).  Scalars, logs and checkpoints are rank 0's.  When the validation list file is missing (the synthetic runs) nothing is scored and ``finish`` writes
     the final weights under the best-model name, so that the inference CLIs always find their checkpoint."""
 
-    def __init__(self, args, snapshot_path, scalars=None, rank=0, world=1, process_group=None):
+    def __init__(self, args, snapshot_path, scalars=None, rank=0, world=1, process_group=None, save=None):
+        """``save(model, path)`` writes a new best model; the default is the bare ``state_dict`` of the reference."""
         self.args, self.snapshot_path, self.scalars = args, snapshot_path, scalars
+        self.save = save or (lambda model, path: torch.save(model.state_dict(), path))
         self.rank, self.world = rank, world
         self.pg = process_group          # the trainer's group: validation collectives must run where the gradients do
         self.three_d = len(args.patch_size) == 3
@@ -324,10 +332,9 @@ class Validator:
                 self.scalars.add_scalar('info/%sval_mean_hd95' % tag, hd95, iter_num)
             if perf > self.best.get(best_name, 0.0):
                 self.best[best_name] = perf
-                torch.save(model.state_dict(), os.path.join(
+                self.save(model, os.path.join(
                     self.snapshot_path, '%siter_%d_dice_%s.pth' % (prefix, iter_num, round(perf, 4))))
-                torch.save(model.state_dict(), os.path.join(
-                    self.snapshot_path, '%s_%s.pth' % (self.args.model, best_name)))
+                self.save(model, os.path.join(self.snapshot_path, '%s_%s.pth' % (self.args.model, best_name)))
             if self.three_d:      # train_mean_teacher_3D.py:221-222
                 logging.info('iteration %d : %sdice_score : %f %shd95 : %f' % (iter_num, tag, perf, tag, hd95))
             else:                 # train_mean_teacher_2D.py:292-293
@@ -357,182 +364,6 @@ def open_snapshot(args, rank, fmt="../model/{}_{}_labeled/{}"):
         logging.getLogger().addHandler(logging.StreamHandler(sys.stdout))
         logging.info(str(args))
     return snapshot_path
-
-
-def run_cross_teaching(args, make_model1, make_model2, log_every=1, label_dtype=torch.uint8, pseudo_ce=False,
-                       make_ema=None, snapshot_fmt="../model/{}_{}/{}", init_fns=None, make_trainer=None,
-                       transform="random_generator", scalar_tag=None, log_line=None):
-    """Hot loop of train_cross_teaching_between_cnn_transformer_2D.py:208-300 (two students, no teacher); with
-    ``pseudo_ce=True`` that of train_cross_pseudo_supervision_{2D,3D}.py (CE pseudo-supervision); with ``make_ema``
-    (the EMA teacher of model2) that of train_cnn_meet_vit_2D.py:285-352.  A two-student method with a trainer of its own
-    (run_contrastive_cross) passes ``make_trainer(model1, model2, rank, iters_per_epoch)``, the loader's ``transform``, the
-    tag of each logged scalar (``scalar_tag(key)``) and its log line (``log_line(iter_num, losses)``); the loader is then
-    built before the trainer, which needs its length."""
-    from .step import CnnMeetVitTrainer, CrossTeachingTrainer
-    rank, world, _ = setup_distributed()
-    seed_everything(args)
-    snapshot_path = open_snapshot(args, rank, snapshot_fmt)
-    model1, model2 = make_model1(), make_model2()
-    if init_fns is not None:          # e.g. kaiming_normal / xavier_normal of the CPS scripts
-        init_fns[0](model1)
-        init_fns[1](model2)
-    ema_model = make_ema() if make_ema is not None else None
-    if world > 1:
-        broadcast_model_state(model1, model2)
-    model1.train()
-    model2.train()
-    if ema_model is not None:
-        for p in ema_model.parameters():
-            p.detach_()
-        if world > 1:
-            broadcast_model_state(ema_model)
-        ema_model.train()
-        trainer = CnnMeetVitTrainer(model1, model2, ema_model, labeled_bs=args.labeled_bs,
-                                    num_classes=args.num_classes, base_lr=args.base_lr,
-                                    max_iterations=args.max_iterations, ema_decay=args.ema_decay,
-                                    consistency=args.consistency, consistency_rampup=args.consistency_rampup,
-                                    seed=args.seed + rank)
-    elif make_trainer is not None:
-        loader, source = make_loader(args, label_dtype, rank, world, transform=transform)
-        trainer = make_trainer(model1, model2, rank, len(loader))
-    else:
-        trainer = CrossTeachingTrainer(model1, model2, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
-                                       base_lr=args.base_lr, max_iterations=args.max_iterations,
-                                       consistency=args.consistency, consistency_rampup=args.consistency_rampup,
-                                       seed=args.seed + rank, pseudo_ce=pseudo_ce)
-    if make_trainer is None:
-        loader, source = make_loader(args, label_dtype, rank, world)
-    if scalar_tag is None:
-        scalar_tag = lambda k: 'loss/' + k if k != 'consistency_weight' else 'consistency_weight/' + k
-    if log_line is None:
-        log_line = lambda it, s: 'iteration %d : model1 loss : %f model2 loss : %f' % (it, s["model1_loss"], s["model2_loss"])
-    if rank == 0:
-        logging.info("{} iterations per epoch ({})".format(len(loader), source))
-    scalars = ScalarLog(snapshot_path, enabled=(rank == 0))
-    validator = Validator(args, snapshot_path, scalars, rank, world, process_group=trainer.pg)
-    val_models = [('model1_', 'model1_', 'best_model1', model1), ('model2_', 'model2_', 'best_model2', model2)]
-    if ema_model is not None:     # train_cnn_meet_vit_2D.py:441-468
-        val_models.append(('ema_model_', 'ema_model_', 'best_ema_model', ema_model))
-    iter_num, t0 = 0, time.time()
-    max_epoch = args.max_iterations // len(loader) + 1
-    for _epoch in range(max_epoch):
-        for sampled_batch in loader:
-            trainer.step(sampled_batch["image"], sampled_batch["label"])
-            iter_num += 1
-            if rank == 0 and iter_num % log_every == 0:
-                s = trainer.losses()
-                for k, v in s.items():
-                    scalars.add_scalar(scalar_tag(k), v, iter_num)
-                logging.info(log_line(iter_num, s))
-            validator(iter_num, val_models)      # every rank: the validation cases are sharded over the ranks
-            if rank == 0 and iter_num % 3000 == 0:
-                for i, m in ((1, model1), (2, model2)):
-                    path = os.path.join(snapshot_path, 'model%d_iter_%d.pth' % (i, iter_num))
-                    torch.save(m.state_dict(), path)
-                    logging.info("save model%d to %s" % (i, path))
-            if iter_num >= args.max_iterations:
-                break
-        if iter_num >= args.max_iterations:
-            break
-    torch.cuda.synchronize()
-    if rank == 0:
-        dt = time.time() - t0
-        logging.info("%d iterations in %.2f s (%.1f samples/s over %d GPU(s))" %
-                     (iter_num, dt, iter_num * args.batch_size * world / dt, world))
-        validator.finish(val_models)
-        scalars.close()
-    if world > 1:
-        torch.distributed.destroy_process_group()
-    return "Training Finished!"
-
-
-def run_contrastive_cross(args, make_model1, make_model2, log_every=1, label_dtype=torch.uint8,
-                          snapshot_fmt="../model/{}_{}_labeled/{}"):
-    """Hot loop of train_Contrastive_Cross_CNN_2D.py:196-408 (and its _CNN_ViT_ twin): run_cross_teaching's loop --
-    both students validated every 200 iterations, best-model and periodic checkpoints under the reference's file names --
-    around ``ContrastiveCrossTrainer``, with the four frozen heads of ``net_factory("classifier" | "projector")``, the
-    resize-only weak loader (the strong loader's batch is never read by the loss: it is not built), the script's scalars
-    (:286-292) and its log line (:294)."""
-    from networks.net_factory import net_factory
-    from .step import ContrastiveCrossTrainer
-
-    def make_trainer(model1, model2, rank, iters_per_epoch):
-        heads = [net_factory(k) for k in ("classifier", "classifier", "projector", "projector")]     # :139-142
-        for h in heads:
-            h.train()
-        return ContrastiveCrossTrainer(model1, model2, *heads, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
-                                       iters_per_epoch=iters_per_epoch, base_lr=args.base_lr,
-                                       max_iterations=args.max_iterations, consistency=args.consistency,
-                                       consistency_rampup=args.consistency_rampup, seed=args.seed + rank)
-
-    tags = {"lr": "lr", "consistency_weight": "consistency_weight/consistency_weight"}
-    line = lambda it, s: ('itr %d, loss %0.2f, m1 loss %0.2f, m2 loss %0.2f, con_loss %0.2f,c_loss_l %0.2f,c_loss_u %0.2f, lr %f'
-                          % (it, s["loss"], s["model1_loss"], s["model2_loss"], s["con_loss"], s["c_loss_l"], s["c_loss_u"],
-                             s["lr"]))
-    return run_cross_teaching(args, make_model1, make_model2, log_every=log_every, label_dtype=label_dtype,
-                              snapshot_fmt=snapshot_fmt, make_trainer=make_trainer, transform="weak",
-                              scalar_tag=lambda k: tags.get(k, "loss/" + k), log_line=line)
-
-
-def run_triple_view(args, make_models, log_every=1, label_dtype=torch.uint8, snapshot_fmt="../model/{}_{}/{}"):
-    """Hot loop of train_tripleview_2D(demo).py:283-491: three students (``make_models``: three factories), no teacher.  The
-    same scalars and log line as the reference (:356-362), all three models validated every 200 iterations (:379-471), the
-    periodic checkpoints every 3000 (:473-484)."""
-    from .step import TripleViewTrainer, triple_split
-    triple_split(args.batch_size, args.labeled_bs)
-    rank, world, _ = setup_distributed()
-    seed_everything(args)
-    snapshot_path = open_snapshot(args, rank, snapshot_fmt)
-    models = [make() for make in make_models]
-    if world > 1:
-        broadcast_model_state(*models)
-    for m in models:
-        m.train()
-    trainer = TripleViewTrainer(*models, labeled_bs=args.labeled_bs, num_classes=args.num_classes, base_lr=args.base_lr,
-                                max_iterations=args.max_iterations, consistency=args.consistency,
-                                consistency_rampup=args.consistency_rampup, seed=args.seed + rank)
-    loader, source = make_loader(args, label_dtype, rank, world)
-    if rank == 0:
-        logging.info("{} iterations per epoch ({})".format(len(loader), source))
-    scalars = ScalarLog(snapshot_path, enabled=(rank == 0))
-    validator = Validator(args, snapshot_path, scalars, rank, world, process_group=trainer.pg)
-    val_models = [('model%d_' % i, 'model%d_' % i, 'best_model%d' % i, m) for i, m in enumerate(models, start=1)]
-    iter_num, t0 = 0, time.time()
-    max_epoch = args.max_iterations // len(loader) + 1
-    for _epoch in range(max_epoch):
-        for sampled_batch in loader:
-            # lr_ as the reference logs it: computed before iter_num is incremented (:346-347)
-            lr_ = args.base_lr * (1.0 - iter_num / args.max_iterations) ** 0.9
-            trainer.step(sampled_batch["image"], sampled_batch["label"])
-            iter_num += 1
-            if rank == 0 and iter_num % log_every == 0:
-                s = trainer.losses()
-                scalars.add_scalar('lr', lr_, iter_num)
-                scalars.add_scalar('consistency_weight/consistency_weight', s["consistency_weight"], iter_num)
-                for i in (1, 2, 3):
-                    scalars.add_scalar('loss/model%d_loss' % i, s["model%d_loss" % i], iter_num)
-                logging.info('iteration %d : model1 loss : %f model2 loss : %f : model3 loss: %f' %
-                             (iter_num, s["model1_loss"], s["model2_loss"], s["model3_loss"]))
-            validator(iter_num, val_models)      # every rank: the validation cases are sharded over the ranks
-            if rank == 0 and iter_num % 3000 == 0:
-                for i, m in enumerate(models, start=1):
-                    path = os.path.join(snapshot_path, 'model%d_iter_%d.pth' % (i, iter_num))
-                    torch.save(m.state_dict(), path)
-                    logging.info("save model%d to %s" % (i, path))
-            if iter_num >= args.max_iterations:
-                break
-        if iter_num >= args.max_iterations:
-            break
-    torch.cuda.synchronize()
-    if rank == 0:
-        dt = time.time() - t0
-        logging.info("%d iterations in %.2f s (%.1f samples/s over %d GPU(s))" %
-                     (iter_num, dt, iter_num * args.batch_size * world / dt, world))
-        validator.finish(val_models)
-        scalars.close()
-    if world > 1:
-        torch.distributed.destroy_process_group()
-    return "Training Finished!"
 
 
 def save_checkpoint(epoch, model, trainer, loss, path):
@@ -570,204 +401,267 @@ def newest_checkpoint(snapshot_path):
     return best[1] if best else None
 
 
-def run_fixmatch(args, make_model, log_every=1, label_dtype=torch.uint8, snapshot_fmt="../model/{}_{}/{}"):
-    """Hot loop of train_Fixmatch_CNN_2D.py:243-372: one network and the EMA copy the reference keeps updated,
-    ``FixMatchTrainer.step`` on the weakly augmented batches (the strong ones are made inside the step), the reference's
-    scalar tags (:303-305, :328-344) and log line, validation every 200 iterations with ``model_iter_{n}_dice_{d}.pth`` /
-    ``{model}_best_model.pth`` and the periodic ``model_iter_{n}.pth`` every 3000, all in the ``util.save_checkpoint`` shape.
-    ``--load`` resumes from the newest ``model_iter_*.pth``: weights, momentum buffer, iteration and epoch."""
-    from .step import FixMatchTrainer, fixmatch_split
-    fixmatch_split(args.batch_size, args.labeled_bs)
+@dataclasses.dataclass
+class Method:
+    """What one training method changes in ``run``; everything not named here is the same for all of them.
+
+    ``nets`` lists the networks as ``(stem, factory)``, the students first and the ``ema`` EMA copies (parameters detached)
+    last; they are built in this order.  The stem names everything a network leaves behind: ``''`` | ``'model_'`` |
+    ``'model1_'`` | ``'ema_model_'`` gives the validation tags ``info/<stem>val_*``, the files ``<stem>iter_<n>.pth``,
+    ``<stem>iter_<n>_dice_<d>.pth`` and ``{model}_best_<name>.pth`` and the log line ``save <name> to``, where the name is
+    the stem without its underscore (``model`` for the empty stem).  ``make_trainer(models, ctx)`` gets all networks and
+    ``ctx.rank``, ``ctx.world``, ``ctx.iter_num`` (non-zero on resume) and, with ``loader_first``, ``ctx.iters_per_epoch``.
+    ``scalars(s, lr_)`` returns the ``(tag, value)`` rows of an iteration and ``log_line(iter_num, s)`` its log line: ``s`` is
+    ``trainer.losses()`` and ``lr_`` the poly rate the step ran with, which is the one the reference scripts log."""
+    nets: list
+    make_trainer: typing.Callable
+    scalars: typing.Callable
+    log_line: typing.Callable
+    snapshot_fmt: str                       # the snapshot directory pattern of the script being mirrored (open_snapshot)
+    label_dtype: torch.dtype = torch.uint8
+    ema: int = 0
+    init_fns: tuple = ()                    # on the first students, once ALL students are built and before an EMA copy is
+    transform: str = "random_generator"     # make_loader's 2-D batch transform
+    loader_first: bool = False              # the trainer needs len(loader): the loader is built before it, not after it
+    validated: tuple = (0,)                 # indices into nets: scored every 200 iterations
+    saved: tuple = (0,)                     # indices into nets: written every 3000 iterations
+    last_model: bool = False                # ``{model}_last_model.pth`` at the end of the run
+    checkpoints: bool = False               # train_Fixmatch_CNN_2D.py: files are ``save_checkpoint`` dictionaries; ``--load``
+
+
+def _name(stem):
+    return stem[:-1] or "model"
+
+
+def _val_models(method, models):
+    """The Validator's (tag, file prefix, best-file suffix, module) of every validated network."""
+    return [(method.nets[i][0], method.nets[i][0], "best_" + _name(method.nets[i][0]), models[i]) for i in method.validated]
+
+
+def train_loop(args, method, rank, models, trainer, loader, validator, scalars, progress):
+    """The one epoch / batch loop: ``trainer.step``, the scalars and the log line on rank 0, validation on every rank, the
+    periodic files every 3000 iterations, until ``args.max_iterations``.  Starts at ``progress.iter_num`` / ``.epoch`` and
+    keeps ``progress`` (with ``.losses``, those of the last logged iteration) current.  Touches no device itself: the only
+    host read is ``trainer.losses()``, once per logged iteration and once more per periodic file of a ``checkpoints``
+    method.  Returns the number of iterations done."""
+    val_models = _val_models(method, models)
+    done = 0
+    for epoch in range(progress.epoch, args.max_iterations // len(loader) + 1):
+        progress.epoch = epoch
+        for sampled_batch in loader:
+            # lr_ as the reference logs it: computed BEFORE iter_num += 1 and logged under the incremented iter_num
+            # (train_mean_teacher_2D.py:234, train_tripleview_2D(demo).py:346-347, train_Fixmatch_CNN_2D.py:297); a run
+            # that starts below max_iterations leaves the loop before this count can pass it, so the base stays >= 0
+            lr_ = args.base_lr * (1.0 - progress.iter_num / args.max_iterations) ** 0.9
+            trainer.step(sampled_batch["image"], sampled_batch["label"])
+            done += 1
+            progress.iter_num += 1
+            iter_num = progress.iter_num
+            if rank == 0:
+                s = progress.losses = trainer.losses()      # the only device->host read of the step
+                for tag, value in method.scalars(s, lr_):
+                    scalars.add_scalar(tag, value, iter_num)
+                logging.info(method.log_line(iter_num, s))
+            validator(iter_num, val_models)      # every rank: the validation cases are sharded over the ranks
+            if rank == 0 and iter_num % 3000 == 0:
+                for i in method.saved:
+                    stem = method.nets[i][0]
+                    path = os.path.join(validator.snapshot_path, '%siter_%d.pth' % (stem, iter_num))
+                    if method.checkpoints:
+                        save_checkpoint(epoch, models[i], trainer, trainer.losses()["loss"], path)
+                    else:
+                        torch.save(models[i].state_dict(), path)
+                    logging.info("save %s to %s" % (_name(stem), path))
+            if iter_num >= args.max_iterations:
+                return done
+    return done
+
+
+def run(args, method):
+    """A whole training run of ``method`` (a ``Method``) for the parsed command line ``args``: ranks, seed and snapshot
+    directory; the networks, every rank starting from rank 0's; trainer and loader; ``train_loop``; the final files."""
     rank, world, _ = setup_distributed()
     seed_everything(args)
-    snapshot_path = open_snapshot(args, rank, snapshot_fmt)
-    model, ema_model = make_model(), make_model()
-    for p in ema_model.parameters():
-        p.detach_()
-    iter_num, start_epoch, momentum = 0, 0, None
-    if args.load:
+    snapshot_path = open_snapshot(args, rank, method.snapshot_fmt)
+    students = len(method.nets) - method.ema
+    models = [make() for _, make in method.nets[:students]]
+    for init, m in zip(method.init_fns, models):     # e.g. kaiming_normal / xavier_normal of the CPS scripts
+        init(m)
+    models += [make() for _, make in method.nets[students:]]
+    for m in models[students:]:
+        for p in m.parameters():           # create_model(ema=True): teacher params are detached
+            p.detach_()
+    progress = types.SimpleNamespace(iter_num=0, epoch=0, losses={})
+    momentum = None
+    if method.checkpoints and args.load:   # resume from the newest model_iter_*.pth: weights, momentum, iteration, epoch
         path = newest_checkpoint(snapshot_path)
         if path is None:
             logging.warning("no model_iter_*.pth under %s: using a new model" % snapshot_path)
         else:
-            start_epoch, iter_num, momentum, _ = load_checkpoint(path, model)
-            logging.info("Models restored from iteration %d (%s)" % (iter_num, path))
-    if world > 1:
-        broadcast_model_state(model, ema_model)
-    model.train()
-    ema_model.train()
-    trainer = FixMatchTrainer(model, ema_model, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
-                              base_lr=args.base_lr, max_iterations=args.max_iterations, ema_decay=args.ema_decay,
-                              consistency=args.consistency, consistency_rampup=args.consistency_rampup,
-                              conf_thresh=args.conf_thresh, seed=args.seed + rank, iter_num=iter_num)
+            progress.epoch, progress.iter_num, momentum, _ = load_checkpoint(path, models[0])
+            logging.info("Models restored from iteration %d (%s)" % (progress.iter_num, path))
+    start_epoch = progress.epoch
+    if world > 1:                          # every rank starts from rank 0's weights and running statistics
+        broadcast_model_state(*models)
+    for m in models:
+        m.train()
+    ctx = types.SimpleNamespace(rank=rank, world=world, iter_num=progress.iter_num, iters_per_epoch=None)
+    if method.loader_first:
+        loader, source = make_loader(args, method.label_dtype, rank, world, transform=method.transform)
+        ctx.iters_per_epoch = len(loader)
+    trainer = method.make_trainer(models, ctx)
     if momentum is not None:
         trainer.momentum_buf.copy_(momentum)
-    loader, source = make_loader(args, label_dtype, rank, world, transform="weak_strong")
+    if not method.loader_first:
+        loader, source = make_loader(args, method.label_dtype, rank, world, transform=method.transform)
     if rank == 0:
         logging.info("{} iterations per epoch ({})".format(len(loader), source))
     scalars = ScalarLog(snapshot_path, enabled=(rank == 0))
-    validator = FixMatchValidator(args, snapshot_path, scalars, rank, world, process_group=trainer.pg)
-    validator.trainer = trainer
-    val_models = [('model_', 'model_', 'best_model', model)]
-    max_epoch = args.max_iterations // len(loader) + 1
-    t0, done = time.time(), 0
-    for epoch_num in range(start_epoch, max_epoch):
-        validator.epoch = epoch_num
-        for sampled_batch in loader:
-            lr_ = args.base_lr * (1.0 - iter_num / args.max_iterations) ** 0.9      # :297, before iter_num += 1
-            trainer.step(sampled_batch["image"], sampled_batch["label"])
-            iter_num += 1
-            done += 1
-            if rank == 0 and iter_num % log_every == 0:
-                s = trainer.losses()
-                validator.loss = s["loss"]
-                scalars.add_scalar('lr', lr_, iter_num)
-                scalars.add_scalar('consistency_weight/consistency_weight', s["consistency_weight"], iter_num)
-                scalars.add_scalar('loss/model_loss', s["loss"], iter_num)
-                logging.info('iteration %d : model loss : %f' % (iter_num, s["loss"]))
-            validator(iter_num, val_models)
-            if rank == 0 and iter_num % 3000 == 0:
-                path = os.path.join(snapshot_path, 'model_iter_' + str(iter_num) + '.pth')
-                save_checkpoint(epoch_num, model, trainer, trainer.losses()["loss"], path)
-                logging.info("save model to {}".format(path))
-            if iter_num >= args.max_iterations:
-                break
-        if iter_num >= args.max_iterations:
-            break
+    save = None
+    if method.checkpoints:                 # train_Fixmatch_CNN_2D.py:346-354: a new best model is a checkpoint too
+        save = lambda model, path: save_checkpoint(progress.epoch, model, trainer, progress.losses.get("loss", 0.0), path)
+    validator = Validator(args, snapshot_path, scalars, rank, world, process_group=trainer.pg, save=save)
+    t0 = time.time()
+    done = train_loop(args, method, rank, models, trainer, loader, validator, scalars, progress)
     torch.cuda.synchronize()
     if rank == 0:
         dt = time.time() - t0
         logging.info("%d iterations in %.2f s (%.1f samples/s over %d GPU(s))" %
                      (done, dt, done * args.batch_size * world / max(dt, 1e-9), world))
-        path = os.path.join(snapshot_path, '{}_best_model.pth'.format(args.model))
-        if not os.path.exists(path):          # no validation score was recorded: the inference CLI still finds its file
-            save_checkpoint(max(start_epoch, 0), model, trainer, trainer.losses()["loss"], path)
-            logging.info("no validation score was recorded: final weights saved as %s" % path)
+        if method.last_model:
+            torch.save(models[0].state_dict(), os.path.join(snapshot_path, '{}_last_model.pth'.format(args.model)))
+        if not method.checkpoints:
+            validator.finish(_val_models(method, models))
+        else:                              # no validation score was recorded: the inference CLI still finds its file
+            path = os.path.join(snapshot_path, '{}_best_model.pth'.format(args.model))
+            if not os.path.exists(path):
+                save_checkpoint(start_epoch, models[0], trainer, trainer.losses()["loss"], path)
+                logging.info("no validation score was recorded: final weights saved as %s" % path)
         scalars.close()
     if world > 1:
         torch.distributed.destroy_process_group()
     return "Training Finished!"
 
 
-class FixMatchValidator(Validator):
-    """The Validator with the FixMatch script's files: a new best mean Dice writes ``model_iter_{n}_dice_{d}.pth`` and
-    ``{model}_best_model.pth`` as ``save_checkpoint`` dictionaries (train_Fixmatch_CNN_2D.py:346-354)."""
-
-    trainer, epoch, loss = None, 0, 0.0
-
-    def __call__(self, iter_num, models):
-        if not self.available or iter_num <= 0 or iter_num % 200:
-            return
-        (tag, _, best_name, model), = models
-        was_training = model.training
-        model.eval()
-        perf, hd95, m = self.score(model)
-        model.train(was_training)
-        if self.rank != 0:
-            return
-        if self.scalars is not None:
-            for c in range(m.shape[0]):
-                self.scalars.add_scalar('info/%sval_%d_dice' % (tag, c + 1), m[c, 0], iter_num)
-                self.scalars.add_scalar('info/%sval_%d_hd95' % (tag, c + 1), m[c, 1], iter_num)
-            self.scalars.add_scalar('info/%sval_mean_dice' % tag, perf, iter_num)
-            self.scalars.add_scalar('info/%sval_mean_hd95' % tag, hd95, iter_num)
-        if perf > self.best.get(best_name, 0.0):
-            self.best[best_name] = perf
-            for path in (os.path.join(self.snapshot_path, 'model_iter_%d_dice_%s.pth' % (iter_num, round(perf, 4))),
-                         os.path.join(self.snapshot_path, '%s_best_model.pth' % self.args.model)):
-                save_checkpoint(self.epoch, model, self.trainer, self.loss, path)
-        logging.info('iteration %d : model_mean_dice : %f model_mean_hd95 : %f' % (iter_num, perf, hd95))
+def _common_kw(args, rank):
+    """The keyword arguments every trainer class takes."""
+    return dict(labeled_bs=args.labeled_bs, num_classes=args.num_classes, base_lr=args.base_lr,
+                max_iterations=args.max_iterations, consistency=args.consistency,
+                consistency_rampup=args.consistency_rampup, seed=args.seed + rank)
 
 
-def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, log_every=1, trainer_cls=None,
+def _tagged_losses(s, lr_):
+    """Every entry of ``losses()`` under ``loss/<key>``, but the consistency weight and (ContrastiveCrossTrainer has it)
+    the learning rate under the reference's own tags (train_cross_teaching_between_cnn_transformer_2D.py:263-270,
+    train_Contrastive_Cross_CNN_2D.py:286-292)."""
+    own = {"lr": "lr", "consistency_weight": "consistency_weight/consistency_weight"}
+    return [(own.get(k, "loss/" + k), v) for k, v in s.items()]
+
+
+def run_training(args, make_model, *, label_dtype, cons_start_iter, save_ema, trainer_cls=None,
                  snapshot_fmt="../model/{}_{}_labeled/{}", trainer_kw=None, single_model=False):
-    """Hot loop of train_mean_teacher_2D.py:196-312 / train_mean_teacher_3D.py:128-230 (and, with
-    ``trainer_cls=UAMTTrainer``, of train_uncertainty_aware_mean_teacher_{2D,3D}.py; with ``trainer_cls=ICTTrainer``
-    and ``trainer_kw=dict(ict_alpha=...)``, of train_interpolation_consistency_training_{2D,3D,2D_ViT}.py).
-    ``trainer_kw``: extra keyword arguments of the trainer class.  ``single_model=True``: no EMA teacher is built and
-    the trainer class takes the one network alone (``trainer_cls=DeepCoTrainingTrainer``:
-    train_deep_co_training_2D{,_ViT}.py:116-237)."""
+    """train_mean_teacher_2D.py:196-312 / train_mean_teacher_3D.py:128-230 (and, with ``trainer_cls=UAMTTrainer``,
+    train_uncertainty_aware_mean_teacher_{2D,3D}.py; with ``trainer_cls=ICTTrainer`` and ``trainer_kw=dict(ict_alpha=...)``,
+    train_interpolation_consistency_training_{2D,3D,2D_ViT}.py).  ``trainer_kw``: extra keyword arguments of the trainer
+    class.  ``single_model=True``: no EMA teacher is built and the trainer class takes the one network alone
+    (``trainer_cls=DeepCoTrainingTrainer``: train_deep_co_training_2D{,_ViT}.py:116-237)."""
     from .step import MeanTeacherTrainer
-    if trainer_cls is not None:
-        MeanTeacherTrainer = trainer_cls
-    rank, world, _ = setup_distributed()
-    seed_everything(args)
-    snapshot_path = open_snapshot(args, rank, snapshot_fmt)
 
-    model = make_model()
-    ema_model = None if single_model else make_model()
-    if ema_model is not None:
-        for p in ema_model.parameters():   # create_model(ema=True): teacher params are detached
-            p.detach_()
-    if world > 1:                          # every rank starts from rank 0's weights and running statistics
-        broadcast_model_state(model, ema_model)
-    model.train()
-    if ema_model is not None:
-        ema_model.train()
+    def make_trainer(models, ctx):
+        kw = dict(_common_kw(args, ctx.rank), **(trainer_kw or {}))
+        if not single_model:
+            kw.update(ema_decay=args.ema_decay, cons_start_iter=cons_start_iter)
+        if trainer_cls is None:
+            # captured replay of a step that contains an RCCL collective is not verified on hardware: --hip_graph is
+            # honoured for single-GPU runs only
+            kw.update(use_graph=bool(getattr(args, "hip_graph", 0)) and ctx.world == 1)
+        if ctx.rank == 0 and getattr(args, "hip_graph", 0) and ctx.world > 1:
+            logging.info("--hip_graph ignored for world_size %d (single-GPU only)" % ctx.world)
+        return (trainer_cls or MeanTeacherTrainer)(*models, **kw)
 
-    if single_model:
-        trainer = MeanTeacherTrainer(model, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
-                                     base_lr=args.base_lr, max_iterations=args.max_iterations,
-                                     consistency=args.consistency, consistency_rampup=args.consistency_rampup,
-                                     seed=args.seed + rank, **(trainer_kw or {}))
+    # all scalars of train_mean_teacher_2D.py:239-245
+    return run(args, Method(
+        nets=[('', make_model)] if single_model else [('', make_model), ('ema_model_', make_model)],
+        ema=0 if single_model else 1, make_trainer=make_trainer, saved=(0, 1) if save_ema else (0,), last_model=True,
+        scalars=lambda s, lr_: [('info/lr', lr_), ('info/total_loss', s["loss"]), ('info/loss_ce', s["loss_ce"]),
+                                ('info/loss_dice', s["loss_dice"]), ('info/consistency_loss', s["consistency_loss"]),
+                                ('info/consistency_weight', s["consistency_weight"])],
+        log_line=lambda it, s: 'iteration %d : loss : %f, loss_ce: %f, loss_dice: %f' % (it, s["loss"], s["loss_ce"],
+                                                                                        s["loss_dice"]),
+        snapshot_fmt=snapshot_fmt, label_dtype=label_dtype))
+
+
+def run_cross_teaching(args, make_model1, make_model2, label_dtype=torch.uint8, pseudo_ce=False, make_ema=None,
+                       snapshot_fmt="../model/{}_{}/{}", init_fns=()):
+    """train_cross_teaching_between_cnn_transformer_2D.py:208-300 (two students, no teacher); with ``pseudo_ce=True``
+    train_cross_pseudo_supervision_{2D,3D}.py (CE pseudo-supervision); with ``make_ema`` (the EMA teacher of model2, which
+    is validated too: :441-468) train_cnn_meet_vit_2D.py:285-352."""
+    from .step import CnnMeetVitTrainer, CrossTeachingTrainer
+    nets = [('model1_', make_model1), ('model2_', make_model2)]
+    if make_ema is not None:
+        nets.append(('ema_model_', make_ema))
+        make_trainer = lambda models, ctx: CnnMeetVitTrainer(*models, ema_decay=args.ema_decay, **_common_kw(args, ctx.rank))
     else:
-        trainer = MeanTeacherTrainer(model, ema_model, labeled_bs=args.labeled_bs, num_classes=args.num_classes,
-                                     base_lr=args.base_lr, max_iterations=args.max_iterations, ema_decay=args.ema_decay,
-                                     consistency=args.consistency, consistency_rampup=args.consistency_rampup,
-                                     cons_start_iter=cons_start_iter, seed=args.seed + rank,
-                                     # captured replay of a step that contains an RCCL collective is not verified on
-                                     # hardware: --hip_graph is honoured for single-GPU runs only
-                                     use_graph=bool(getattr(args, "hip_graph", 0)) and world == 1,
-                                     **(trainer_kw or {}))
-    if rank == 0 and getattr(args, "hip_graph", 0) and world > 1:
-        logging.info("--hip_graph ignored for world_size %d (single-GPU only)" % world)
-    loader, source = make_loader(args, label_dtype, rank, world)
-    if rank == 0:
-        logging.info("{} iterations per epoch ({})".format(len(loader), source))
-    scalars = ScalarLog(snapshot_path, enabled=(rank == 0))
-    validator = Validator(args, snapshot_path, scalars, rank, world, process_group=trainer.pg)
-    val_models = [('', '', 'best_model', model)]
-    iter_num = 0
-    max_epoch = args.max_iterations // len(loader) + 1
-    t0 = time.time()
-    for _epoch in range(max_epoch):
-        for sampled_batch in loader:
-            trainer.step(sampled_batch["image"], sampled_batch["label"])
-            iter_num += 1
-            if rank == 0 and iter_num % log_every == 0:
-                s = trainer.losses()          # the only device->host read of the step: ONE copy of trainer.out
-                # all scalars of train_mean_teacher_2D.py:239-245.  lr_ is computed there (:234) BEFORE iter_num += 1
-                # and logged under the incremented iter_num: base_lr * (1 - (n - 1) / max) ** 0.9 at tag n
-                lr_ = args.base_lr * (1.0 - min(iter_num - 1, args.max_iterations) / args.max_iterations) ** 0.9
-                scalars.add_scalar('info/lr', lr_, iter_num)
-                scalars.add_scalar('info/total_loss', s["loss"], iter_num)
-                scalars.add_scalar('info/loss_ce', s["loss_ce"], iter_num)
-                scalars.add_scalar('info/loss_dice', s["loss_dice"], iter_num)
-                scalars.add_scalar('info/consistency_loss', s["consistency_loss"], iter_num)
-                scalars.add_scalar('info/consistency_weight', s["consistency_weight"], iter_num)
-                logging.info('iteration %d : loss : %f, loss_ce: %f, loss_dice: %f' %
-                             (iter_num, s["loss"], s["loss_ce"], s["loss_dice"]))
-            validator(iter_num, val_models)      # every rank: the validation cases are sharded over the ranks
-            if rank == 0 and iter_num % 3000 == 0:
-                path = os.path.join(snapshot_path, 'iter_' + str(iter_num) + '.pth')
-                torch.save(model.state_dict(), path)
-                logging.info("save model to {}".format(path))
-                if save_ema:
-                    path = os.path.join(snapshot_path, 'ema_model_iter_' + str(iter_num) + '.pth')
-                    torch.save(ema_model.state_dict(), path)
-                    logging.info("save ema_model to {}".format(path))
-            if iter_num >= args.max_iterations:
-                break
-        if iter_num >= args.max_iterations:
-            break
-    torch.cuda.synchronize()
-    if rank == 0:
-        dt = time.time() - t0
-        logging.info("%d iterations in %.2f s (%.1f samples/s over %d GPU(s))" %
-                     (iter_num, dt, iter_num * args.batch_size * world / dt, world))
-        torch.save(model.state_dict(), os.path.join(snapshot_path, '{}_last_model.pth'.format(args.model)))
-        validator.finish(val_models)
-        scalars.close()
-    if world > 1:
-        torch.distributed.destroy_process_group()
-    return "Training Finished!"
+        make_trainer = lambda models, ctx: CrossTeachingTrainer(*models, pseudo_ce=pseudo_ce, **_common_kw(args, ctx.rank))
+    return run(args, Method(
+        nets=nets, ema=len(nets) - 2, init_fns=init_fns, make_trainer=make_trainer, validated=tuple(range(len(nets))),
+        saved=(0, 1), scalars=_tagged_losses,
+        log_line=lambda it, s: 'iteration %d : model1 loss : %f model2 loss : %f' % (it, s["model1_loss"], s["model2_loss"]),
+        snapshot_fmt=snapshot_fmt, label_dtype=label_dtype))
+
+
+def run_contrastive_cross(args, make_model1, make_model2, label_dtype=torch.uint8,
+                          snapshot_fmt="../model/{}_{}_labeled/{}"):
+    """train_Contrastive_Cross_CNN_2D.py:196-408 (and its _CNN_ViT_ twin): two students around ``ContrastiveCrossTrainer``
+    with the four frozen heads of ``net_factory("classifier" | "projector")``, the resize-only weak loader (the strong
+    loader's batch is never read by the loss: it is not built), the script's scalars (:286-292) and its log line (:294).
+    The trainer needs the loader's length (the script's consistency ramp counts epochs), so the loader comes first."""
+    from networks.net_factory import net_factory
+    from .step import ContrastiveCrossTrainer
+
+    def make_trainer(models, ctx):
+        heads = [net_factory(k).train() for k in ("classifier", "classifier", "projector", "projector")]     # :139-142
+        return ContrastiveCrossTrainer(*models, *heads, iters_per_epoch=ctx.iters_per_epoch, **_common_kw(args, ctx.rank))
+
+    return run(args, Method(
+        nets=[('model1_', make_model1), ('model2_', make_model2)], make_trainer=make_trainer, loader_first=True,
+        transform="weak", validated=(0, 1), saved=(0, 1), scalars=_tagged_losses,
+        log_line=lambda it, s: ('itr %d, loss %0.2f, m1 loss %0.2f, m2 loss %0.2f, con_loss %0.2f,c_loss_l %0.2f,'
+                                'c_loss_u %0.2f, lr %f' % (it, s["loss"], s["model1_loss"], s["model2_loss"], s["con_loss"],
+                                                          s["c_loss_l"], s["c_loss_u"], s["lr"])),
+        snapshot_fmt=snapshot_fmt, label_dtype=label_dtype))
+
+
+def run_triple_view(args, make_models, label_dtype=torch.uint8, snapshot_fmt="../model/{}_{}/{}"):
+    """train_tripleview_2D(demo).py:283-491: three students (``make_models``: three factories), no teacher.  The same
+    scalars and log line as the reference (:356-362), all three models validated every 200 iterations (:379-471), the
+    periodic checkpoints every 3000 (:473-484)."""
+    from .step import TripleViewTrainer, triple_split
+    triple_split(args.batch_size, args.labeled_bs)
+    return run(args, Method(
+        nets=list(zip(('model1_', 'model2_', 'model3_'), make_models)), validated=(0, 1, 2), saved=(0, 1, 2),
+        make_trainer=lambda models, ctx: TripleViewTrainer(*models, **_common_kw(args, ctx.rank)),
+        scalars=lambda s, lr_: [('lr', lr_), ('consistency_weight/consistency_weight', s["consistency_weight"]),
+                                ('loss/model1_loss', s["model1_loss"]), ('loss/model2_loss', s["model2_loss"]),
+                                ('loss/model3_loss', s["model3_loss"])],
+        log_line=lambda it, s: 'iteration %d : model1 loss : %f model2 loss : %f : model3 loss: %f' % (
+            it, s["model1_loss"], s["model2_loss"], s["model3_loss"]),
+        snapshot_fmt=snapshot_fmt, label_dtype=label_dtype))
+
+
+def run_fixmatch(args, make_model, label_dtype=torch.uint8, snapshot_fmt="../model/{}_{}/{}"):
+    """train_Fixmatch_CNN_2D.py:243-372: one network and the EMA copy the reference keeps updated, ``FixMatchTrainer.step``
+    on the weakly augmented batches (the strong ones are made inside the step), the reference's scalar tags (:303-305,
+    :328-344) and log line, ``model_iter_{n}_dice_{d}.pth`` / ``{model}_best_model.pth`` and the periodic
+    ``model_iter_{n}.pth``, all in the ``util.save_checkpoint`` shape.  ``--load`` resumes from the newest
+    ``model_iter_*.pth``: weights, momentum buffer, iteration and epoch."""
+    from .step import FixMatchTrainer, fixmatch_split
+    fixmatch_split(args.batch_size, args.labeled_bs)
+    return run(args, Method(
+        nets=[('model_', make_model), ('ema_model_', make_model)], ema=1, transform="weak_strong", checkpoints=True,
+        make_trainer=lambda models, ctx: FixMatchTrainer(*models, ema_decay=args.ema_decay, conf_thresh=args.conf_thresh,
+                                                         iter_num=ctx.iter_num, **_common_kw(args, ctx.rank)),
+        scalars=lambda s, lr_: [('lr', lr_), ('consistency_weight/consistency_weight', s["consistency_weight"]),
+                                ('loss/model_loss', s["loss"])],
+        log_line=lambda it, s: 'iteration %d : model loss : %f' % (it, s["loss"]),
+        snapshot_fmt=snapshot_fmt, label_dtype=label_dtype))
