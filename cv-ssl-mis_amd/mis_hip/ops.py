@@ -1368,3 +1368,166 @@ def upsample_int_bwd(dy, dx, scale, accumulate=False):
     N, K, d, h, w, dxbs, dybs = _up_int_geom(dx, dy, int(scale))
     _l.check(L.mis_upsample_int_bwd(_l.ptr(dy), dybs, _l.ptr(dx), dxbs, N, K, d, h, w, int(scale), int(accumulate),
                                     _l.stream_ptr()), "mis_upsample_int_bwd")
+
+
+# ------------------------------------------------------- adversarial training (csrc/adversarial.hip)
+ADAM_STATE_BYTES = 16      # int64 step, float 1 - beta1^step, float 1 - beta2^step
+
+
+def channel_dropout_scale(scale, p, salt, state):
+    """scale[N, C] = nn.Dropout3d(p)'s factor per (sample, channel): 0 or 1 / (1 - p), drawn from ``state``."""
+    L = _l.load()
+    _l.require_gpu(scale)
+    assert scale.dim() == 2 and scale.is_contiguous() and scale.dtype == torch.float32
+    _l.check(L.mis_channel_dropout_scale(_l.ptr(scale), scale.shape[0], scale.shape[1], float(p), int(salt), _l.ptr(state),
+                                         _l.stream_ptr()), "mis_channel_dropout_scale")
+
+
+def _k4s2_in(x, logits):
+    """Geometry of the two-part input of a kernel-4 / stride-2 convolution: (N, D, H, W, x_bs, Cx, l_bs, Cl)."""
+    N = D = H = W = None
+    xbs = lbs = Cx = Cl = 0
+    if logits is not None:
+        N, Cl, D, H, W, _, lbs = _geom(logits)
+    if x is not None:
+        Nx, Cx, Dx, Hx, Wx, _, xbs = _geom(x)
+        if N is not None and (Nx, Dx, Hx, Wx) != (N, D, H, W):
+            raise RuntimeError(f"conv_k4s2: {tuple(x.shape)} and {tuple(logits.shape)} do not belong together (MIS_ERR_ARG)")
+        N, D, H, W = Nx, Dx, Hx, Wx
+    if N is None:
+        raise RuntimeError("conv_k4s2: no input (MIS_ERR_ARG)")
+    return N, D, H, W, xbs, Cx, lbs, Cl
+
+
+def _k4s2_out(t, N, D, H, W, what):
+    No, Co, Do, Ho, Wo, _, bs = _geom(t)
+    if (No, 2 * Do, 2 * Ho, 2 * Wo) != (N, D, H, W):
+        raise RuntimeError(f"conv_k4s2: {what} {tuple(t.shape)} does not belong to an input of {(N, D, H, W)} (MIS_ERR_ARG)")
+    return Co, bs
+
+
+def conv_k4s2_fwd(x, logits, w_x, w_l, bias, bias2, y, slope=0.2, drop_scale=None):
+    """y = drop(leaky_relu(bias + bias2 + Conv3d(k=4, s=2, p=1)(cat(softmax(logits), x)), slope)).  ``logits`` / ``w_l``: the
+    channels read through a softmax and their filter (None: none); ``x`` / ``w_x``: the plain ones (None: none)."""
+    L = _l.load()
+    N, D, H, W, xbs, Cx, lbs, Cl = _k4s2_in(x, logits)
+    Cout, ybs = _k4s2_out(y, N, D, H, W, "y")
+    assert (w_x is None or (w_x.is_contiguous() and w_x.numel() == Cout * Cx * 64))
+    assert (w_l is None or (w_l.is_contiguous() and w_l.numel() == Cout * Cl * 64))
+    nb = L.mis_conv_k4s2_fwd_workspace_bytes(N, Cx + Cl, Cout, D, H, W)
+    if nb < 0:
+        _l.check(nb, "mis_conv_k4s2_fwd_workspace_bytes")
+    ws = scratch(nb, "k4s2")
+    _l.check(L.mis_conv_k4s2_fwd(_l.ptr(x), xbs, Cx, _l.ptr(logits), lbs, Cl, _l.ptr(w_x), _l.ptr(w_l), _l.ptr(bias),
+                                 _l.ptr(bias2), _l.ptr(y), ybs, N, Cout, D, H, W, float(slope), _l.ptr(drop_scale),
+                                 _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_conv_k4s2_fwd")
+
+
+def conv_k4s2_dgrad(dy, y, w, dx, slope=0.2, drop_scale=None):
+    """dx = the gradient at the input of the convolution with filter ``w`` [Cout, Cin, 4, 4, 4] for the gradient ``dy`` at its
+    activated output ``y`` (None: the plain convolution's gradient)."""
+    L = _l.load()
+    N, Cin, D, H, W, _, dxbs = _geom(dx)
+    Cout, dybs = _k4s2_out(dy, N, D, H, W, "dy")
+    ybs = _k4s2_out(y, N, D, H, W, "y")[1] if y is not None else 0
+    assert w.is_contiguous() and w.numel() == Cout * Cin * 64
+    _l.check(L.mis_conv_k4s2_dgrad(_l.ptr(dy), dybs, _l.ptr(y), ybs, float(slope), _l.ptr(drop_scale), _l.ptr(w), _l.ptr(dx),
+                                   dxbs, N, Cin, Cout, D, H, W, _l.stream_ptr()), "mis_conv_k4s2_dgrad")
+
+
+def conv_k4s2_wgrad(x, logits, dy, y, dw_x, dw_l, dbias=None, dbias2=None, slope=0.2, drop_scale=None, accumulate=False):
+    """dw_l / dw_x (+)= the filter gradient in the two parts of conv_k4s2_fwd's input, dbias / dbias2 (+)= the bias gradient;
+    deterministic."""
+    L = _l.load()
+    N, D, H, W, xbs, Cx, lbs, Cl = _k4s2_in(x, logits)
+    Cout, dybs = _k4s2_out(dy, N, D, H, W, "dy")
+    ybs = _k4s2_out(y, N, D, H, W, "y")[1] if y is not None else 0
+    assert (dw_x is None or (dw_x.is_contiguous() and dw_x.numel() == Cout * Cx * 64))
+    assert (dw_l is None or (dw_l.is_contiguous() and dw_l.numel() == Cout * Cl * 64))
+    nb = L.mis_conv_k4s2_wgrad_workspace_bytes(N, Cx + Cl, Cout, D, H, W)
+    if nb < 0:
+        _l.check(nb, "mis_conv_k4s2_wgrad_workspace_bytes")
+    ws = scratch(nb, "k4s2")
+    _l.check(L.mis_conv_k4s2_wgrad(_l.ptr(x), xbs, Cx, _l.ptr(logits), lbs, Cl, _l.ptr(dy), dybs, _l.ptr(y), ybs, float(slope),
+                                   _l.ptr(drop_scale), _l.ptr(dw_x), _l.ptr(dw_l), _l.ptr(dbias), _l.ptr(dbias2), N, Cout,
+                                   D, H, W, int(accumulate), _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_conv_k4s2_wgrad")
+
+
+def adv_head_workspace(N, C, K):
+    """The buffer adv_head_fwd leaves the pooled features and d loss / d logits in for adv_head_bwd."""
+    L = _l.load()
+    nb = L.mis_adv_head_workspace_bytes(N, C, K)
+    if nb < 0:
+        _l.check(nb, "mis_adv_head_workspace_bytes")
+    return torch.empty(nb // 4, dtype=torch.float32, device="cuda")
+
+
+def adv_head_fwd(a, w, b, target, loss, logits, ws, pool=None):
+    """loss[0] = cross_entropy(Linear(avg_pool(a)), target), logits [N, K]; ``pool`` defaults to the feature's extent."""
+    L = _l.load()
+    N, C, D, H, W, _, abs_ = _geom(a)
+    K = w.shape[0]
+    pool = (D, H, W) if pool is None else tuple(int(p) for p in pool)
+    assert w.is_contiguous() and w.numel() == K * C and target.dtype == torch.int32 and target.numel() == N
+    assert logits.is_contiguous() and logits.numel() == N * K
+    _l.require_gpu(w, target, loss, logits, ws)
+    _l.check(L.mis_adv_head_fwd(_l.ptr(a), abs_, _l.ptr(w), _l.ptr(b), _l.ptr(target), _l.ptr(loss), _l.ptr(logits), N, C, K,
+                                D, H, W, pool[0], pool[1], pool[2], _l.ptr(ws), ws.numel() * 4, _l.stream_ptr()),
+             "mis_adv_head_fwd")
+
+
+def adv_head_bwd(w, da, dw, db, ws, shape=None, accumulate=False):
+    """da (None: not wanted; then ``shape`` = the feature's (N, C, D, H, W)), dw [K, C], db [K] (+)= the head's gradients."""
+    L = _l.load()
+    if da is not None:
+        N, C, D, H, W, _, dabs = _geom(da)
+    else:
+        N, C, D, H, W = shape
+        dabs = 0
+    K = w.shape[0]
+    _l.check(L.mis_adv_head_bwd(_l.ptr(w), _l.ptr(da), dabs, _l.ptr(dw), _l.ptr(db), int(accumulate), N, C, K, D, H, W,
+                                _l.ptr(ws), ws.numel() * 4, _l.stream_ptr()), "mis_adv_head_bwd")
+
+
+def adversarial_tail(logits, label, labeled_bs, dmap, cons_loss, out, dlogits=None, cons_weight=0.0, state=None,
+                     loss_scale=1.0):
+    """0.5 * (CE + Dice) on the labeled samples + w * cons_loss; dlogits: the supervised gradient on the labeled samples,
+    w * (softmax Jacobian)^T dmap on the unlabeled ones.  ``out`` (>= 5 + C floats): [loss, loss_ce, loss_dice,
+    consistency_loss, consistency_weight, class-wise dice...]."""
+    L = _l.load()
+    B, C, D, H, W, S, sbs = _geom(logits)
+    mbs = 0
+    if dmap is not None:
+        Bm, Cm, _, _, _, Sm, mbs = _geom(dmap)
+        assert Bm == B - labeled_bs and Cm == C and Sm == S
+    if label is not None:
+        _l.require_gpu(label)
+        assert label.is_contiguous() and label.dtype in (torch.uint8, torch.int64)
+        assert label.numel() >= labeled_bs * S
+    lb = 1 if (label is None or label.dtype == torch.uint8) else 8
+    dbs = _geom(dlogits)[6] if dlogits is not None else 0
+    nb = L.mis_adversarial_tail_workspace_bytes(B, C, S)
+    if nb < 0:
+        _l.check(nb, "mis_adversarial_tail_workspace_bytes")
+    ws = scratch(nb, "tail")
+    _l.check(L.mis_adversarial_tail(_l.ptr(logits), sbs, _l.ptr(label), lb, _l.ptr(dmap), mbs, _l.ptr(cons_loss), B,
+                                    labeled_bs, C, S, cons_weight, _l.ptr(state), loss_scale, _l.ptr(out), _l.ptr(dlogits),
+                                    dbs, _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_adversarial_tail")
+
+
+def adam_init(adam_state, step=0):
+    """Set the device-resident step count of an Adam state (a 16-byte buffer)."""
+    L = _l.load()
+    _l.require_gpu(adam_state)
+    assert adam_state.numel() * adam_state.element_size() >= ADAM_STATE_BYTES
+    _l.check(L.mis_adam_init(_l.ptr(adam_state), int(step), _l.stream_ptr()), "mis_adam_init")
+
+
+def adam_step(param, grad, m, v, adam_state, lr, betas=(0.9, 0.999), eps=1e-8):
+    """One torch.optim.Adam step (no weight decay) on flat fp32 buffers; the step count advances on the device."""
+    L = _l.load()
+    _l.require_gpu(param, grad, m, v, adam_state)
+    n = param.numel()
+    assert grad.numel() == n and m.numel() == n and v.numel() == n
+    _l.check(L.mis_adam_step(_l.ptr(param), _l.ptr(grad), _l.ptr(m), _l.ptr(v), n, float(lr), float(betas[0]),
+                             float(betas[1]), float(eps), _l.ptr(adam_state), _l.stream_ptr()), "mis_adam_step")

@@ -1,6 +1,6 @@
 """The training steps, each one fused device-side sequence replacing a loop body of the reference.
 
-Nine methods share one skeleton (``_Step``); DESIGN.md has a section per method:
+Ten methods share one skeleton (``_Step``); DESIGN.md has a section per method:
 
     MeanTeacherTrainer      student + EMA teacher on the noised unlabeled half (code/train_mean_teacher_{2D,3D}.py)
     UAMTTrainer             + T = 8 MC-dropout teacher passes, the entropy of their mean masks the consistency term
@@ -11,6 +11,7 @@ Nine methods share one skeleton (``_Step``); DESIGN.md has a section per method:
     ContrastiveCrossTrainer cross teaching + two pixel-wise contrastive terms through frozen projector / classifier heads
     CnnMeetVitTrainer       cross teaching + an EMA teacher of the second student
     TripleViewTrainer       three students, each taught by the arg-max pseudo labels of both others; one joint loss tail
+    AdversarialTrainer      a 3-D student and a discriminator (SGD / Adam), two phases per step (code/train_adversarial_network_3D.py)
 
 The skeleton of a step:
 
@@ -942,3 +943,103 @@ class TripleViewTrainer(_Step):
                       "consistency_weight": o[4].item()})
         d["loss"] = d["model1_loss"] + d["model2_loss"] + d["model3_loss"]
         return d
+
+
+class AdversarialTrainer(_Step):
+    """Adversarial network training of the 3-D nets (reference code/train_adversarial_network_3D.py:129-175), two phases
+    per step, both recorded on the launch tape:
+
+    A (segmenter)      student forward in train mode; the discriminator, frozen and in eval mode (no dropout), judges
+                       softmax(outputs[L:]) against the target 1 and hands back its cross-entropy and the gradient at
+                       its ``map`` input -- no parameter gradient is formed, the reference discards it; one fused tail
+                       (``mis_adversarial_tail``) writes 0.5 * (CE + Dice) + w * consistency_loss and the logits gradient;
+                       student backward, SGD (momentum 0.9, wd 1e-4).
+    B (discriminator)  student forward in eval mode with the weights phase A just updated (no backward, on a plan of
+                       its own); the discriminator in train mode (Dropout3d from the step's Philox state) on all B
+                       samples against the target ``1 if i < labeled_bs else 0``; its backward; Adam (``dan_lr``,
+                       betas (0.9, 0.99)) with the step count on the device.
+
+    Then the schedule: poly LR and w = consistency * sigmoid_rampup(iter_num // 150, rampup) in the Mean-Teacher order.
+    The student's softmax is never written: the discriminator's first layer reads the logits through it.  Single process:
+    the discriminator's gradient has no exchange."""
+
+    TRAIN_MODE = "the adversarial step switches train / eval mode itself: hand it both networks in train mode"
+
+    def __init__(self, model, dan, *, labeled_bs, num_classes, base_lr=0.01, dan_lr=1e-4, max_iterations=30000,
+                 consistency=0.1, consistency_rampup=200.0, seed=1337, iter_num=0, momentum=0.9, weight_decay=1e-4,
+                 betas=(0.9, 0.99), eps=1e-8, process_group=None, use_tape=None):
+        if dist.world_size(process_group) > 1:
+            raise NotImplementedError("AdversarialTrainer is single-process: the discriminator's gradient is not exchanged")
+        if not 0 < int(labeled_bs):
+            raise ValueError(f"adversarial training needs labeled samples, got labeled_bs={labeled_bs}")
+        self.model, self.dan = model, dan
+        self._setup((model,), (dan,), (1, 2), labeled_bs=int(labeled_bs), num_classes=num_classes, base_lr=base_lr,
+                    max_iterations=max_iterations, consistency=consistency, consistency_rampup=consistency_rampup,
+                    seed=seed, iter_num=iter_num, momentum=momentum, weight_decay=weight_decay,
+                    process_group=process_group, use_tape=use_tape)
+        self.dan_lr, self.betas, self.eps = float(dan_lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.adam_m, self.adam_v = torch.zeros_like(dan.flat_param), torch.zeros_like(dan.flat_param)
+        self.adam_state = torch.zeros(2, dtype=torch.int64, device="cuda")
+        ops.adam_init(self.adam_state, 0)
+        self.dan_out = torch.zeros(1, dtype=torch.float32, device="cuda")
+        self._targets = {}
+
+    def _target(self, B, ones):
+        """int32 [B]: phase B's ``1 if i < labeled_bs else 0``; ``ones``: phase A's all-ones target of the unlabeled samples."""
+        t = self._targets.get((B, ones))
+        if t is None:
+            t = (torch.ones(B) if ones else (torch.arange(B) < self.labeled_bs)).to(torch.int32).cuda()
+            self._targets[(B, ones)] = t
+        return t
+
+    def _run(self, volume, label):
+        L, m, dan = self.labeled_bs, self.model, self.dan
+        B = volume.shape[0]
+        # ---- phase A
+        dan.eval()
+        s_logits = m.forward_raw(volume)
+        self.pass_a = m.last_pass()              # phase B's forward runs on a plan of its own: this pass stays readable
+        dan.loss_forward(s_logits[L:], volume[L:], self._target(B - L, True))
+        dan.loss_backward(params=False, dmap=True)
+        ops.adversarial_tail(s_logits, label[:L].contiguous(), L, dan.dmap_buffer(), dan.loss_buffer(), self.out,
+                             dlogits=m.logits_grad_buffer(), state=self.state)
+        grad_scale = backward_and_sync(m, self.pg)
+        ops.sgd_ema_step(m.flat_param, m.flat_grad, self.momentum_buf, None, momentum=self.momentum,
+                         weight_decay=self.weight_decay, grad_scale=grad_scale, state=self.state)
+        # ---- phase B
+        m.eval()
+        b_logits = m.forward_raw(volume, no_backward=True, slot=1)
+        m.train()
+        dan.train()
+        dan.loss_forward(b_logits, volume, self._target(B, False))
+        dan.loss_backward(params=True, dmap=False)
+        self.dan_out = dan.loss_buffer()             # static per batch shape: the recorded launches write it again
+        ops.adam_step(dan.flat_param, dan.flat_grad, self.adam_m, self.adam_v, self.adam_state, self.dan_lr, self.betas,
+                      self.eps)
+        self._advance_schedule()
+
+    def step(self, volume_batch, label_batch):
+        """One iteration on device tensors [B, 1, D, H, W] / [B, D, H, W]; returns the device scalar buffer ``[loss, loss_ce,
+        loss_dice, consistency_loss, consistency_weight, ...]`` (no host sync); ``dan_out[0]`` is the discriminator's loss."""
+        if volume_batch.dim() != 5:
+            raise ValueError(f"adversarial training runs the 3-D networks on [B, C, D, H, W]; got {tuple(volume_batch.shape)}")
+        if not self.labeled_bs < volume_batch.shape[0]:
+            raise ValueError(f"adversarial training needs unlabeled samples: batch {volume_batch.shape[0]}, "
+                             f"labeled_bs {self.labeled_bs}")
+        return self._step(volume_batch, label_batch)
+
+    def losses(self):
+        o = self.out.cpu()
+        return dict(loss=o[0].item(), loss_ce=o[1].item(), loss_dice=o[2].item(), consistency_loss=o[3].item(),
+                    consistency_weight=o[4].item(), DAN_loss=self.dan_out.item())
+
+    # ---- checkpoint: the discriminator and its optimizer
+    def dan_checkpoint(self):
+        return dict(state_dict={k: v.detach().cpu().clone() for k, v in self.dan.state_dict().items()},
+                    adam_m=self.adam_m.cpu(), adam_v=self.adam_v.cpu(), adam_step=int(self.adam_state[0].item()))
+
+    def load_dan_checkpoint(self, ck):
+        self.dan.load_state_dict(ck["state_dict"])
+        self.adam_m.copy_(ck["adam_m"])
+        self.adam_v.copy_(ck["adam_v"])
+        ops.adam_init(self.adam_state, int(ck["adam_step"]))

@@ -1,6 +1,7 @@
 """Shared driver of all ``train_*.py`` command lines: Mean Teacher, UA-MT, ICT and deep co-training (``run_training``),
 cross teaching, cross pseudo supervision and CNN-meets-ViT (``run_cross_teaching``), contrastive cross teaching
-(``run_contrastive_cross``), triple view (``run_triple_view``) and FixMatch (``run_fixmatch``).
+(``run_contrastive_cross``), triple view (``run_triple_view``), FixMatch (``run_fixmatch``) and adversarial network
+training (``run_adversarial``).
 
 Keeps what the reference scripts do around the hot loop (seeding, snapshot directory, ``log.txt``, the scalars, the
 in-training validation, periodic checkpoints with the reference's file names, the two-stream "labeled first" batch
@@ -427,6 +428,7 @@ class Method:
     saved: tuple = (0,)                     # indices into nets: written every 3000 iterations
     last_model: bool = False                # ``{model}_last_model.pth`` at the end of the run
     checkpoints: bool = False               # train_Fixmatch_CNN_2D.py: files are ``save_checkpoint`` dictionaries; ``--load``
+    extra_files: typing.Callable = None     # (trainer, snapshot_path, iter_num): more periodic files, beside those of ``saved``
 
 
 def _name(stem):
@@ -472,6 +474,8 @@ def train_loop(args, method, rank, models, trainer, loader, validator, scalars, 
                     else:
                         torch.save(models[i].state_dict(), path)
                     logging.info("save %s to %s" % (_name(stem), path))
+                if method.extra_files is not None:
+                    method.extra_files(trainer, validator.snapshot_path, iter_num)
             if iter_num >= args.max_iterations:
                 return done
     return done
@@ -664,4 +668,28 @@ def run_fixmatch(args, make_model, label_dtype=torch.uint8, snapshot_fmt="../mod
         scalars=lambda s, lr_: [('lr', lr_), ('consistency_weight/consistency_weight', s["consistency_weight"]),
                                 ('loss/model_loss', s["loss"])],
         log_line=lambda it, s: 'iteration %d : model loss : %f' % (it, s["loss"]),
+        snapshot_fmt=snapshot_fmt, label_dtype=label_dtype))
+
+
+def run_adversarial(args, make_model, make_dan, label_dtype=torch.int64, snapshot_fmt="../model/{}_{}/{}"):
+    """train_adversarial_network_3D.py:84-238: the segmenter and the discriminator around ``AdversarialTrainer``, the
+    script's scalars (:177-184) and log line (:186-188), the segmenter validated every 200 iterations and written every
+    3000 as the reference does (``iter_<n>.pth``, ``{model}_best_model.pth``).  Beside every ``iter_<n>.pth`` goes
+    ``DAN_iter_<n>.pth``: the discriminator's state_dict, Adam's two moment buffers and its step count
+    (``AdversarialTrainer.dan_checkpoint``)."""
+    from .step import AdversarialTrainer
+
+    def extra_files(trainer, snapshot_path, iter_num):
+        path = os.path.join(snapshot_path, 'DAN_iter_%d.pth' % iter_num)
+        torch.save(trainer.dan_checkpoint(), path)
+        logging.info("save DAN to %s" % path)
+
+    return run(args, Method(
+        nets=[('', make_model), ('DAN_', make_dan)], extra_files=extra_files,
+        make_trainer=lambda models, ctx: AdversarialTrainer(*models, dan_lr=args.DAN_lr, **_common_kw(args, ctx.rank)),
+        scalars=lambda s, lr_: [('info/lr', lr_), ('info/total_loss', s["loss"]), ('info/loss_ce', s["loss_ce"]),
+                                ('info/loss_dice', s["loss_dice"]), ('info/consistency_loss', s["consistency_loss"]),
+                                ('info/consistency_weight', s["consistency_weight"]), ('info/DAN_loss', s["DAN_loss"])],
+        log_line=lambda it, s: 'iteration %d : loss : %f, loss_ce: %f, loss_dice: %f' % (it, s["loss"], s["loss_ce"],
+                                                                                        s["loss_dice"]),
         snapshot_fmt=snapshot_fmt, label_dtype=label_dtype))

@@ -1,0 +1,154 @@
+"""The adversarial discriminator of the 3-D nets on hand-written gfx950 kernels (csrc/adversarial.hip).
+
+``FC3DDiscriminator(num_classes, ndf=64, n_channel=1)`` is the reference's (code/networks/discriminator.py:6-55): same
+constructor, same twelve state_dict entries (``conv0`` .. ``conv4`` and ``classifier``, weight and bias each), torch's default
+initialisation.  Five Conv3d(kernel 4, stride 2, padding 1), LeakyReLU(0.2) after each, Dropout3d(0.5) after the first three,
+AvgPool3d over the 6^3 feature, Linear(8 ndf, 2).  ``pool`` (keyword only, for tests) is another pool window; it has to equal
+conv4's output extent.
+
+It is no segmenter: two inputs and a scalar out.  It keeps HipNet's flat parameter and gradient buffers and the nn.Module
+surface, and runs its own static launch sequence instead of a Plan:
+
+  ``loss_forward(logits, image, target)``   cross_entropy(D(softmax(logits), image), target).  The ``map`` input is the
+      student's LOGITS: the first layer reads them through a softmax (conv0 and conv1 are one convolution over
+      num_classes + n_channel channels), the probabilities are never stored.  ``self.training`` decides the dropout; the
+      keep decisions come from ``step_state`` (Philox) or from ``drop_masks`` = three [N, C] scale arrays.
+  ``loss_backward(params=..., dmap=...)``   the parameter gradients into ``flat_grad`` and / or the gradient at the
+      softmax output into ``dmap_buffer()`` (a frozen discriminator forms no parameter gradient).
+
+All buffers are static per batch shape, so both calls can be recorded on a launch tape.  ``FCDiscriminator`` (2-D) is not built.
+"""
+import math
+
+import torch
+
+from mis_hip import ops
+from mis_hip.plan import HipNet
+from networks.unet import _conv_init
+
+SLOPE = 0.2
+DROP_P = 0.5
+DROP_SALT = 0x80000000 | 0x0AD50000      # channel mode (bit 31, as mis_norm_act_fwd's Dropout3d sites) + the layer's index
+
+
+class FC3DDiscriminator(HipNet):
+    ndim_spatial = 3
+
+    @staticmethod
+    def spec(num_classes, ndf=64, n_channel=1):
+        """[(state_dict key, shape)] in the reference's order."""
+        k = (4, 4, 4)
+        chans = [("conv0", num_classes, ndf), ("conv1", n_channel, ndf), ("conv2", ndf, 2 * ndf), ("conv3", 2 * ndf, 4 * ndf),
+                 ("conv4", 4 * ndf, 8 * ndf)]
+        keys = []
+        for name, cin, cout in chans:
+            keys += [(f"{name}.weight", (cout, cin) + k), (f"{name}.bias", (cout,))]
+        return keys + [("classifier.weight", (2, 8 * ndf)), ("classifier.bias", (2,))]
+
+    def __init__(self, num_classes, ndf=64, n_channel=1, *, pool=(6, 6, 6)):
+        super().__init__()
+        self.num_classes, self.ndf, self.n_channel = int(num_classes), int(ndf), int(n_channel)
+        self.pool = tuple(int(p) for p in pool)
+        for name, shape in self.spec(self.num_classes, self.ndf, self.n_channel):
+            if name.endswith("weight"):
+                if len(shape) == 5:
+                    w, b = _conv_init(shape[0], shape[1], shape[2:])
+                else:                                   # nn.Linear's default: the same two uniform laws
+                    w = torch.empty(shape)
+                    torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+                    b = torch.empty(shape[0]).uniform_(-1.0 / math.sqrt(shape[1]), 1.0 / math.sqrt(shape[1]))
+                self._declare(name, w)
+                self._declare(name[:-len("weight")] + "bias", b)
+        self._materialize()
+        self._bufs = {}
+        self._cur = None
+
+    def _build(self, plan):
+        raise RuntimeError("FC3DDiscriminator has no Plan: use loss_forward / loss_backward")
+
+    def forward(self, map, image):
+        raise RuntimeError("FC3DDiscriminator runs through loss_forward(logits, image, target): it reads the student's logits "
+                           "(the softmax is on its load path) and ends in the cross-entropy")
+
+    # ---- static buffers per batch shape
+    def _static(self, N, D, H, W):
+        key = (N, D, H, W)
+        b = self._bufs.get(key)
+        if b is None:
+            if D % 16 or H % 16 or W % 16:
+                raise RuntimeError(f"FC3DDiscriminator: input extent {(D, H, W)} is no multiple of 16 (MIS_ERR_UNSUPPORTED)")
+            new = lambda *s: torch.zeros(s, dtype=torch.float32, device="cuda")
+            widths = [self.ndf, 2 * self.ndf, 4 * self.ndf, 8 * self.ndf]
+            ext = [(D >> (i + 1), H >> (i + 1), W >> (i + 1)) for i in range(4)]
+            b = dict(act=[new(N, c, *e) for c, e in zip(widths, ext)], grad=[new(N, c, *e) for c, e in zip(widths, ext)],
+                     scale=[new(N, c) for c in widths[:3]], dmap=new(N, self.num_classes, D, H, W),
+                     head=ops.adv_head_workspace(N, widths[3], 2), loss=new(1), logits=new(N, 2))
+            self._bufs[key] = b
+        return b
+
+    def loss_forward(self, logits, image, target):
+        """Writes ``loss_buffer()`` [1] and ``logits_buffer()`` [N, 2].  logits [N, num_classes, D, H, W] (the student's),
+        image [N, n_channel, D, H, W], target [N] int32; batch-strided views are fine."""
+        N, _, D, H, W = logits.shape
+        b = self._static(N, D, H, W)
+        P = self.P
+        scales = [None, None, None]
+        if self.training and self.dropout_enabled:
+            for i in range(3):
+                if self.drop_masks is not None:
+                    b["scale"][i].copy_(self.drop_masks[i])
+                else:
+                    if self.step_state is None:
+                        raise RuntimeError("FC3DDiscriminator in train mode needs step_state (Philox) or drop_masks")
+                    ops.channel_dropout_scale(b["scale"][i], DROP_P, DROP_SALT + 16 * self.rng_stream + i, self.step_state)
+                scales[i] = b["scale"][i]
+        a = b["act"]
+        ops.conv_k4s2_fwd(image, logits, P("conv1.weight").data, P("conv0.weight").data, P("conv1.bias").data,
+                          P("conv0.bias").data, a[0], SLOPE, scales[0])
+        for i, name in ((1, "conv2"), (2, "conv3"), (3, "conv4")):
+            ops.conv_k4s2_fwd(a[i - 1], None, P(name + ".weight").data, None, P(name + ".bias").data, None, a[i], SLOPE,
+                              scales[i] if i < 3 else None)
+        ops.adv_head_fwd(a[3], P("classifier.weight").data, P("classifier.bias").data, target, b["loss"], b["logits"],
+                         b["head"], self.pool)
+        self._cur = (b, logits, image, scales)
+        return b["loss"]
+
+    def loss_backward(self, params=True, dmap=False):
+        """Backward of the last loss_forward: ``params`` writes every parameter gradient into ``flat_grad`` (overwriting),
+        ``dmap`` the gradient at softmax(logits) into ``dmap_buffer()``."""
+        b, logits, image, scales = self._cur
+        P = self.P
+        a, g = b["act"], b["grad"]
+        cw = P("classifier.weight")
+        ops.adv_head_bwd(cw.data, g[3], cw.grad if params else None, P("classifier.bias").grad if params else None, b["head"])
+        for i, name in ((3, "conv4"), (2, "conv3"), (1, "conv2")):
+            w = P(name + ".weight")
+            sc = scales[i] if i < 3 else None
+            if params:
+                ops.conv_k4s2_wgrad(a[i - 1], None, g[i], a[i], w.grad, None, P(name + ".bias").grad, None, SLOPE, sc)
+            ops.conv_k4s2_dgrad(g[i], a[i], w.data, g[i - 1], SLOPE, sc)
+        if params:
+            ops.conv_k4s2_wgrad(image, logits, g[0], a[0], P("conv1.weight").grad, P("conv0.weight").grad,
+                                P("conv1.bias").grad, P("conv0.bias").grad, SLOPE, scales[0])
+        if dmap:
+            ops.conv_k4s2_dgrad(g[0], a[0], P("conv0.weight").data, b["dmap"], SLOPE, scales[0])
+
+    def loss_buffer(self):
+        return self._cur[0]["loss"]
+
+    def logits_buffer(self):
+        return self._cur[0]["logits"]
+
+    def dmap_buffer(self):
+        return self._cur[0]["dmap"]
+
+    def activations(self):
+        """The stored activated outputs of conv0+conv1, conv2, conv3, conv4 of the last loss_forward."""
+        return self._cur[0]["act"]
+
+
+class FCDiscriminator:
+    """The 2-D discriminator (reference code/networks/discriminator.py:58-100) is not built."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("FCDiscriminator (2-D) is not built on the HIP path; only FC3DDiscriminator is")

@@ -1,0 +1,239 @@
+"""The adversarial step (mis_hip.step.AdversarialTrainer, networks/discriminator.py) on the GPU: unet_3D at 96^3, B = 2 + 2,
+ndf = 8.  The kernels themselves are held to the float64 oracle in tests/test_adversarial_kernels_gpu.py; here the step is
+held to those ops bit for bit (what the student receives, what Adam and SGD do, eager against taped, run against run), and
+the discriminator's side of the golden's reference iteration (tests/golden/adversarial_3d.npz) to the kernel tests' gate."""
+import numpy as np
+import pytest
+import torch
+
+import adversarial_oracle as ao
+from test_adversarial_kernels_gpu import _Check, _one_thread
+
+pytestmark = pytest.mark.gpu
+
+B, L, C, NDF, SIZE = 4, 2, 2, 8, 96
+KW = dict(labeled_bs=L, num_classes=C, base_lr=0.01, dan_lr=1e-4, max_iterations=100, consistency=0.1,
+          consistency_rampup=1.0, seed=11)       # rampup 1: the consistency weight is 0.1 * exp(-5) > 0 from iteration 0
+
+
+def _ops():
+    from mis_hip import ops
+    return ops
+
+
+def _nets(seed=5):
+    from networks.discriminator import FC3DDiscriminator
+    from networks.net_factory_3d import net_factory_3d
+    torch.manual_seed(seed)
+    model = net_factory_3d("unet_3D", 1, C)
+    dan = FC3DDiscriminator(C, ndf=NDF)
+    return model.train(), dan.train()
+
+
+@pytest.fixture(scope="module")
+def batch():
+    vol, _, lab = ao.golden_inputs(B, C, SIZE)
+    return vol.cuda(), lab.long().cuda()
+
+
+def _run(batch, steps, use_tape):
+    """``steps`` steps from the seeded start; returns what the comparisons need (host copies)."""
+    from mis_hip.step import AdversarialTrainer
+    model, dan = _nets()
+    tr = AdversarialTrainer(model, dan, use_tape=use_tape, **KW)
+    outs = []
+    for _ in range(steps):
+        tr.step(*batch)
+        outs.append((tr.out.clone(), tr.dan_out.clone()))
+    torch.cuda.synchronize()
+    res = dict(model=model.flat_param.cpu(), dan=dan.flat_param.cpu(), m=tr.adam_m.cpu(), v=tr.adam_v.cpu(),
+               step=int(tr.adam_state[0].item()), outs=[(a.cpu(), b.cpu()) for a, b in outs], taped=tr._tape is not None)
+    del tr, model, dan
+    torch.cuda.empty_cache()
+    return res
+
+
+def _same(a, b):
+    return (torch.equal(a["model"], b["model"]) and torch.equal(a["dan"], b["dan"]) and torch.equal(a["m"], b["m"])
+            and torch.equal(a["v"], b["v"]) and a["step"] == b["step"]
+            and all(torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) for x, y in zip(a["outs"], b["outs"])))
+
+
+def test_one_step_is_its_separately_tested_pieces_bit_for_bit(batch):
+    from mis_hip.step import AdversarialTrainer
+    from networks.discriminator import FC3DDiscriminator
+    ops = _ops()
+    volume, label = batch
+    model, dan = _nets()
+    tr = AdversarialTrainer(model, dan, use_tape=False, **KW)
+    sd0 = {k: v.detach().clone() for k, v in dan.state_dict().items()}
+    p0, state0 = model.flat_param.clone(), tr.state.clone()
+    SENT = 123.0
+    for _, gv in dan.named_flat(dan.flat_grad):      # not the padding words between the parameters: Adam reads those too
+        gv.fill_(SENT)
+    seen = []
+    inner = dan.loss_forward
+
+    def spy(logits, image, target):
+        if logits.shape[0] == B:       # phase B begins: what phase A left of the discriminator
+            seen.append((dan.flat_param.clone(), dan.flat_grad.clone(), tr.adam_m.clone(), tr.adam_v.clone(),
+                         tr.adam_state.clone(), model.training, dan.training))
+        return inner(logits, image, target)
+    dan.loss_forward = spy
+    tr.step(volume, label)
+    torch.cuda.synchronize()
+    # phase A leaves the discriminator's parameters, gradients and Adam state untouched
+    fp, fg, am, av, ast, m_train, d_train = seen[0]
+    ref = FC3DDiscriminator(C, ndf=NDF)
+    ref.load_state_dict(sd0)
+    assert torch.equal(fp, ref.flat_param) and all((gv == SENT).all() for _, gv in dan.named_flat(fg))
+    assert (am == 0).all() and (av == 0).all() and ast[0].item() == 0
+    assert m_train and d_train
+    # ---- the student's logits gradient: the tail on the trainer's own logits and the discriminator branch of the ops
+    plan = tr.pass_a[0]
+    a_logits = plan.out.t
+    ref.eval()
+    ref.loss_forward(a_logits[L:], volume[L:], torch.ones(B - L, dtype=torch.int32, device="cuda"))
+    ref.loss_backward(params=False, dmap=True)
+    out = torch.full((16,), float("nan"), device="cuda")
+    want = torch.full_like(a_logits, float("nan"))
+    ops.adversarial_tail(a_logits, label[:L].contiguous(), L, ref.dmap_buffer(), ref.loss_buffer(), out, dlogits=want,
+                         state=state0)
+    got = model.logits_grad_buffer(tr.pass_a)
+    assert torch.equal(got, want) and torch.isfinite(got).all() and got[L:].abs().max() > 0
+    assert torch.equal(out[:5 + C], tr.out[:5 + C])
+    sup = torch.full_like(a_logits, float("nan"))
+    ops.adversarial_tail(a_logits, label[:L].contiguous(), L, ref.dmap_buffer(), ref.loss_buffer(), out, dlogits=sup,
+                         cons_weight=0.0)
+    assert torch.equal(sup[:L], got[:L]) and (sup[L:] == 0).all()      # the labeled samples: the supervised gradient alone
+    # ---- the student's parameters: the existing SGD path on its gradient
+    p, mom = p0.clone(), torch.zeros_like(p0)
+    ops.sgd_ema_step(p, model.flat_grad, mom, None, momentum=0.9, weight_decay=1e-4, grad_scale=1.0, state=state0)
+    assert torch.equal(p, model.flat_param) and torch.equal(mom, tr.momentum_buf)
+    # ---- the discriminator's parameters: mis_adam_step on the ops' gradients (phase B read the updated student's logits)
+    b_logits = model._last[0].out.t
+    assert model._last[0] is not plan
+    ref.train()
+    ref.drop_masks = [s.clone() for s in dan._cur[0]["scale"]]
+    assert all(((s == 0) | (s == 2)).all() for s in ref.drop_masks)
+    ref.loss_forward(b_logits, volume, (torch.arange(B) < L).int().cuda())
+    ref.loss_backward(params=True, dmap=False)
+    assert torch.equal(ref.loss_buffer(), tr.dan_out) and torch.equal(ref.flat_grad, dan.flat_grad)
+    m, v, st = torch.zeros_like(ref.flat_param), torch.zeros_like(ref.flat_param), torch.zeros(2, dtype=torch.int64, device="cuda")
+    ops.adam_init(st, 0)
+    ops.adam_step(ref.flat_param, ref.flat_grad, m, v, st, 1e-4, (0.9, 0.99), 1e-8)
+    assert torch.equal(ref.flat_param, dan.flat_param) and torch.equal(m, tr.adam_m) and torch.equal(v, tr.adam_v)
+    assert not torch.equal(dan.flat_param, fp) and tr.adam_state[0].item() == 1
+    s = tr.losses()
+    assert abs(s["consistency_weight"] - 0.1 * np.exp(-5.0)) < 1e-7 and s["DAN_loss"] > 0 and s["consistency_loss"] > 0
+
+
+def test_taped_replay_and_a_second_seeded_run_equal_the_eager_run_bit_for_bit(batch):
+    eager = _run(batch, 4, use_tape=False)
+    taped = _run(batch, 4, use_tape=True)           # two eager steps, the recorded one, one replay
+    again = _run(batch, 3, use_tape=False)
+    assert taped["taped"] and not eager["taped"]
+    assert _same(eager, taped), "the taped step differs from the eager one"
+    first3 = _run(batch, 3, use_tape=True)
+    assert _same(again, first3), "two seeded runs of three steps differ"
+    assert eager["step"] == 4 and all(torch.isfinite(o[0][:5]).all() for o in eager["outs"])
+
+
+def test_checkpoint_round_trip_restores_the_discriminator_and_adam(batch, tmp_path):
+    from mis_hip.step import AdversarialTrainer
+    model, dan = _nets()
+    tr = AdversarialTrainer(model, dan, use_tape=False, **KW)
+    tr.step(*batch)
+    tr.step(*batch)
+    path = str(tmp_path / "DAN_iter_2.pth")
+    torch.save(tr.dan_checkpoint(), path)
+    ck = torch.load(path)
+    assert sorted(ck) == ["adam_m", "adam_step", "adam_v", "state_dict"] and list(ck["state_dict"]) == list(ao.DISC_KEYS)
+    assert ck["adam_step"] == 2
+    model2, dan2 = _nets(seed=6)
+    tr2 = AdversarialTrainer(model2, dan2, use_tape=False, **KW)
+    assert not torch.equal(dan2.flat_param, dan.flat_param)
+    tr2.load_dan_checkpoint(ck)
+    torch.cuda.synchronize()
+    assert torch.equal(dan2.flat_param, dan.flat_param) and torch.equal(tr2.adam_m, tr.adam_m)
+    assert torch.equal(tr2.adam_v, tr.adam_v) and tr2.adam_state[0].item() == 2
+
+
+def test_the_goldens_reference_iteration_is_reproduced_within_the_gate():
+    """The discriminator's side of one iteration of the real reference (FC3DDiscriminator(2, ndf=4), 96^3, 2 + 2): phase A's
+    loss, logits and ``map`` gradient, phase B's loss, logits and all twelve parameter gradients, the parameters after one
+    and two Adam steps.  e32 = the oracle in fp32 (one thread) against the golden."""
+    from networks.discriminator import FC3DDiscriminator
+    ops = _ops()
+    g = np.load(ao.__file__.replace("adversarial_oracle.py", "golden/adversarial_3d.npz"))
+    gold = lambda k: torch.from_numpy(np.asarray(g[k])).double()
+    chk = _Check("golden")
+    vol, logits, _ = ao.golden_inputs(B, C, SIZE)
+    sd0 = ao.golden_state_dict(C, 4, 1)
+    masks = ao.golden_masks(4, B)
+    target = torch.tensor([1, 1, 0, 0])
+    probs32 = _one_thread(lambda: torch.softmax(logits, 1))
+    a32 = _one_thread(lambda: ao.disc_step(sd0, probs32[L:], vol[L:], target[:L], None, dtype=torch.float32))
+    b32 = _one_thread(lambda: ao.disc_step(sd0, probs32, vol, target, masks, dtype=torch.float32))
+    dan = FC3DDiscriminator(C, ndf=4)
+    dan.load_state_dict(sd0)
+    lg, vd = logits.cuda(), vol.cuda()
+    dan.eval()
+    dan.loss_forward(lg[L:], vd[L:], torch.ones(B - L, dtype=torch.int32, device="cuda"))
+    dan.loss_backward(params=False, dmap=True)
+    chk("A loss", "y", dan.loss_buffer(), gold("a_loss"), a32["loss"])
+    chk("A logits", "y", dan.logits_buffer(), gold("a_logits"), a32["logits"], 0)
+    dmap = dan.dmap_buffer().cpu().double()
+    chk("A dmap lattice", "dx", ao.lattice(dmap), gold("dmap_lattice"), ao.lattice(a32["dmap"]))
+    chk("A dmap sums", "dx", dmap.sum((2, 3, 4)), gold("dmap_sums"), a32["dmap"].double().sum((2, 3, 4)))
+    dan.train()
+    dan.drop_masks = [m.float().cuda() for m in masks]
+    m, v = torch.zeros_like(dan.flat_param), torch.zeros_like(dan.flat_param)
+    st = torch.zeros(2, dtype=torch.int64, device="cuda")
+    ops.adam_init(st, 0)
+    p0 = dan.flat_param.clone()
+    td = target.int().cuda()
+    for step in (1, 2):
+        dan.loss_forward(lg, vd, td)
+        dan.loss_backward(params=True)
+        if step == 1:
+            chk("B loss", "y", dan.loss_buffer(), gold("b_loss"), b32["loss"])
+            chk("B logits", "y", dan.logits_buffer(), gold("b_logits"), b32["logits"], 0)
+            for key, gv in dan.named_flat(dan.flat_grad.clone()):
+                chk("B d" + key, "dw", gv, gold("grad/" + key), b32["grads"][key], 0)
+            sd1_32 = {k: _one_thread(lambda k=k: ao.adam(sd0[k], [b32["grads"][k]], 1e-4, dtype=torch.float32))[0] for k in sd0}
+            b32_2 = _one_thread(lambda: ao.disc_step(sd1_32, probs32, vol, target, masks, dtype=torch.float32))
+        ops.adam_step(dan.flat_param, dan.flat_grad, m, v, st, 1e-4, (0.9, 0.99), 1e-8)
+        for key, pv in dan.named_flat((dan.flat_param - p0).clone()):
+            if step == 1:
+                r32 = sd1_32[key].double() - sd0[key].double()
+            else:
+                two = _one_thread(lambda key=key: ao.adam(sd0[key], [b32["grads"][key], b32_2["grads"][key]], 1e-4,
+                                                          dtype=torch.float32))[1]
+                r32 = two.double() - sd0[key].double()
+            chk(f"delta{step} {key}", "dw", pv, gold(f"delta{step}/{key}"), r32, 0)
+    chk.done()
+
+
+def test_command_line_trains_on_synthetic_batches(tmp_path):
+    """``train_adversarial_network_3D.py`` through ``train_common.run``: no dataset under --root_path, so the batches are the
+    synthetic two-stream ones; 32^3 patches (conv4 leaves 2^3, which the pool then covers), 2 + 2 volumes, five iterations."""
+    import os
+    import subprocess
+    import sys
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cv-ssl-mis_amd")
+    work = tmp_path / "code"
+    work.mkdir()
+    r = subprocess.run([sys.executable, os.path.join(pkg, "train_adversarial_network_3D.py"), "--root_path",
+                        str(tmp_path / "none"), "--exp", "t/ADV", "--max_iterations", "5", "--patch_size", "32", "32", "32",
+                        "--labeled_num", "2"], cwd=str(work), env=dict(os.environ, PYTHONPATH=pkg), capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert "Training Finished!" in r.stdout
+    snap = tmp_path / "model" / "t" / "ADV_2" / "unet_3D"
+    sc = (snap / "scalars.csv").read_text()
+    for tag in ("info/lr", "info/total_loss", "info/loss_ce", "info/loss_dice", "info/consistency_loss",
+                "info/consistency_weight", "info/DAN_loss"):
+        assert "," + tag + "," in sc, tag
+    log = (snap / "log.txt").read_text()
+    assert "iteration 5 : loss :" in log and "nan" not in log.lower()
