@@ -95,8 +95,11 @@ constexpr int GDBG = MIS_GEMM_DBG_CT;
 // PREC = 1 ("bf16x3", MIS_GEMM_BF3=1): an fp32 value is cut EXACTLY into three bf16 pieces by truncation, x = h + m + l (8 + 8 + 8
 // significant bits; the two subtractions are exact), and a product of two such values is the sum of the six piece products
 // hh + hm + mh + hl + lh + mm on v_mfma_f32_16x16x32_bf16 with fp32 accumulation -- what is dropped (ml + lm + ll) is below
-// 2^-24 of |a||b|, i.e. below the rounding of the fp32 fmaf chain it replaces (tests: error against float64 no larger than the
-// fp32 kernel's).  One K = 32 block costs 6 instructions of 18 cycles instead of 8 of 32 (scripts/ubench/pipe_share.hip:
+// 2^-24 of |a||b|, i.e. below the rounding of the fp32 fmaf chain it replaces.  Measured against float64 per output channel
+// (tests/test_token_edges_gpu.py): the same size of error as the fp32-MFMA kernel's -- case by case 0.6 .. 1.6 x its worst-column
+// error and 0.8 .. 1.3 x its rms, median 1.0 in both -- and every kernel of either form within 2.3 x the fp32 noise of torch's CPU
+// matmul and of a plain fp32 chain; a lost third-order product is 10 .. 100 x that and fails those tests.
+// One K = 32 block costs 6 instructions of 18 cycles instead of 8 of 32 (scripts/ubench/pipe_share.hip:
 // 7.5 ns against 13.8 ns per instruction), and the 32-bit integer / fp32 ops of the split overlap a co-resident wave's bf16
 // MFMAs (v_add beside mfma_bf16: 2175 us together against 2967 serial), which packed fp32 ops and the fp32 MFMA do not.
 typedef mis_u32x4 u32x4;

@@ -1,4 +1,7 @@
-"""Op-level parity of the token-major (SwinUnet) HIP kernels against stock torch CPU fp32/fp64 ops."""
+"""Op-level parity of the token-major (SwinUnet) HIP kernels against stock torch CPU fp32/fp64 ops: geometry, dispatch, refusals
+and bit-identities, at 2e-4 of the tensor's largest value on zero-mean uniform inputs.  The PRECISION of the same kernels -- per
+output channel, in units of fp32 noise, against a float64 oracle, every row of every kernel family in both arithmetic forms --
+lives in tests/test_token_edges_gpu.py (oracle: tests/token_oracle.py, checked on the CPU by tests/test_token_oracle_cpu.py)."""
 import ctypes
 
 import pytest
