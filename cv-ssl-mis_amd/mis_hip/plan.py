@@ -1158,11 +1158,20 @@ class _PRef:
         self.data, self.grad = data, grad
 
 
+def trunc_normal(*shape, std=0.02):
+    """The transformers' weight law (timm / MONAI ``trunc_normal_(std=.02)``), also for their position tables."""
+    return torch.nn.init.trunc_normal_(torch.empty(*shape), std=std)
+
+
+_WEIGHT_LAWS = {"uniform": lambda w: torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5)),
+                "normal": lambda w: torch.nn.init.kaiming_normal_(w, a=0, mode="fan_in")}
+
+
 class HipNet(nn.Module):
     """Base of the HIP-backed networks: flat parameter storage + plans + the nn.Module surface.
 
-    Sub-classes call ``_declare`` for every parameter/buffer in the reference's state_dict order,
-    then ``_materialize``; they implement ``_build(plan)`` describing the layer graph.
+    Sub-classes declare every parameter/buffer in the reference's state_dict order (``_conv`` / ``_norm`` / ``_linear``,
+    ``_declare`` for the odd tensor), then ``_materialize``; they implement ``_build(plan)`` describing the layer graph.
     """
 
     ndim_spatial = 2
@@ -1179,6 +1188,7 @@ class HipNet(nn.Module):
         self.weights_version = 0
         self.net_id = next(_net_ids)
         self._specs = []       # (dotted name, shape, kind, init tensor)
+        self.transposed_convs = set()   # keys of the nn.ConvTranspose weights: train_common._init_conv_weights skips them
         self._refs = {}
         self._plans = {}
         self.flat_param = None
@@ -1191,8 +1201,65 @@ class HipNet(nn.Module):
         self._last = None
 
     # ---- declaration ----
+    # A network states its layers through _conv / _norm / _linear (and _declare for the odd tensor: position embeddings,
+    # index and mask buffers).  Each call registers its entries in torch's order and draws them from the global CPU
+    # generator as the reference's module would: weight first, then bias.
+    _shapes_only = False    # True inside _declared(): entries are recorded, nothing is drawn or allocated
+
     def _declare(self, name, init, kind="param"):
         self._specs.append((name, tuple(init.shape), kind, init))
+
+    def _entry(self, name, shape, make, kind="param"):
+        shape = tuple(int(s) for s in shape)
+        self._specs.append((name, shape, kind, None if self._shapes_only else make(shape)))
+
+    def _conv(self, name, cout, cin, k, bias=True, law="uniform", transposed=False, listed=True):
+        """Conv{2,3}d ``name``: weight [cout][cin][k...] -- a transposed one [cin][cout][k...], listed in
+        ``transposed_convs`` (what _init_conv_weights skips) unless ``listed=False`` -- and bias [cout].
+        ``law``: "uniform" = torch's default kaiming_uniform(a=sqrt(5)), "normal" = kaiming_normal(fan_in); the bias is
+        torch's default U(+-1/sqrt(fan_in)) under both, fan_in = shape[1] * prod(k).  ``bias="discard"`` draws it and
+        registers none."""
+        shape = ((cin, cout) if transposed else (cout, cin)) + tuple(k)
+        bound = 1.0 / math.sqrt(shape[1] * math.prod(k))
+        self._entry(name + ".weight", shape, lambda s: _WEIGHT_LAWS[law](torch.empty(s)))
+        if bias == "discard":
+            if not self._shapes_only:
+                torch.empty(cout).uniform_(-bound, bound)
+        elif bias:
+            self._entry(name + ".bias", (cout,), lambda s: torch.empty(s).uniform_(-bound, bound))
+        if transposed and listed:
+            self.transposed_convs.add(name + ".weight")
+
+    def _norm(self, name, C, affine=True, running=False, weight_std=None):
+        """A normalisation over C channels: weight := 1 (N(1, weight_std) when given) and bias := 0 if ``affine``, then
+        BatchNorm's running_mean / running_var / num_batches_tracked buffers if ``running``."""
+        if affine:
+            self._entry(name + ".weight", (C,), torch.ones if weight_std is None else
+                        lambda s: torch.empty(s).normal_(1.0, weight_std))
+            self._entry(name + ".bias", (C,), torch.zeros)
+        if running:
+            self._entry(name + ".running_mean", (C,), torch.zeros, "buffer")
+            self._entry(name + ".running_var", (C,), torch.ones, "buffer")
+            self._entry(name + ".num_batches_tracked", (), lambda s: torch.zeros(s, dtype=torch.long), "buffer")
+
+    def _linear(self, name, out_f, in_f, bias=True, law="trunc_normal"):
+        """nn.Linear ``name``.  ``law``: "trunc_normal" = the transformers' trunc_normal(std 0.02) weight and zero bias,
+        "uniform" = torch's nn.Linear default, the same two uniform laws as a convolution without a kernel."""
+        if law == "uniform":
+            return self._conv(name, out_f, in_f, (), bias)
+        self._entry(name + ".weight", (out_f, in_f), lambda s: trunc_normal(*s))
+        if bias:
+            self._entry(name + ".bias", (out_f,), torch.zeros)
+
+    @classmethod
+    def _declared(cls, *args):
+        """[(state_dict key, shape)] that ``_layers(*args)`` declares -- what the constructor registers -- without a
+        device, a draw or an allocation: the ``spec()`` of the networks whose CPU tests read one."""
+        net = cls.__new__(cls)
+        nn.Module.__init__(net)
+        net._specs, net.transposed_convs, net._shapes_only = [], set(), True
+        net._layers(*args)
+        return [(n, s) for n, s, _, _ in net._specs]
 
     def _materialize(self):
         if not torch.cuda.is_available():

@@ -25,29 +25,27 @@ trilinear up-sampling by 8 / 4 / 2 (mis_upsample_int_* / mis_upsample2_*) into c
 
 The layer graph is executed by ``mis_hip.plan``; nothing here computes on the CPU.
 """
-import torch
-
 from mis_hip.plan import HipNet
-from networks.unet_3D import _conv_init
 
 
 class Attention_UNet(HipNet):
     ndim_spatial = 3
 
-    @staticmethod
-    def spec(feature_scale=4, n_classes=21, in_channels=3):
+    @classmethod
+    def spec(cls, feature_scale=4, n_classes=21, in_channels=3):
         """[(state_dict key, shape)] in the reference's order."""
+        return cls._declared(feature_scale, n_classes, in_channels)
+
+    def _layers(self, feature_scale, n_classes, in_channels):
+        """``init_weights(..., 'kaiming')``: kaiming_normal_ for every convolution (its bias keeps torch's default), N(1, 0.02)
+        for the BatchNorm weights."""
         f = [int(x / feature_scale) for x in (64, 128, 256, 512, 1024)]
-        keys = []
 
         def conv(prefix, cout, cin, k, bias=True):
-            keys.append((f"{prefix}.weight", (cout, cin) + k))
-            if bias:
-                keys.append((f"{prefix}.bias", (cout,)))
+            self._conv(prefix, cout, cin, k, bias, law="normal")
 
         def bn(prefix, C):
-            keys.extend([(f"{prefix}.weight", (C,)), (f"{prefix}.bias", (C,)), (f"{prefix}.running_mean", (C,)),
-                         (f"{prefix}.running_var", (C,)), (f"{prefix}.num_batches_tracked", ())])
+            self._norm(prefix, C, running=True, weight_std=0.02)
 
         def unetconv(prefix, cin, cout):
             conv(f"{prefix}.conv1.0", cout, cin, (3, 3, 3))
@@ -64,7 +62,7 @@ class Attention_UNet(HipNet):
                 p = f"attentionblock{lvl}.gate_block_{k}"
                 conv(f"{p}.W.0", C, C, (1, 1, 1))
                 bn(f"{p}.W.1", C)
-                conv(f"{p}.theta", C, C, (2, 2, 2), bias=False)
+                conv(f"{p}.theta", C, C, (2, 2, 2), bias="discard")     # bias-free, its bias draw is made and dropped
                 conv(f"{p}.phi", C, Cg, (1, 1, 1))
                 conv(f"{p}.psi", 1, C, (1, 1, 1))
             conv(f"attentionblock{lvl}.combine_gates.0", C, 2 * C, (1, 1, 1))
@@ -75,7 +73,6 @@ class Attention_UNet(HipNet):
             conv(f"dsv{lvl}.dsv.0", n_classes, f[lvl - 1], (1, 1, 1))
         conv("dsv1", n_classes, f[0], (1, 1, 1))
         conv("final", n_classes, 4 * n_classes, (1, 1, 1))
-        return keys
 
     def __init__(self, feature_scale=4, n_classes=21, is_deconv=True, in_channels=3, nonlocal_mode='concatenation',
                  attention_dsample=(2, 2, 2), is_batchnorm=True):
@@ -85,26 +82,7 @@ class Attention_UNet(HipNet):
                                       "(the variant net_factory_3d builds) are on the HIP hot path")
         self.in_channels, self.n_classes = in_channels, n_classes
         self.filters = [int(x / feature_scale) for x in (64, 128, 256, 512, 1024)]
-        spec = self.spec(feature_scale, n_classes, in_channels)
-        shapes = dict(spec)
-        for name, shape in spec:
-            is_bn = ".W.1." in name or ".combine_gates.1." in name
-            if len(shape) == 5:                 # a convolution: init_weights' kaiming_normal_, the bias keeps torch's default
-                w, b = _conv_init(shape[0], shape[1], shape[2:])
-                self._declare(name, w)
-                if name[:-len("weight")] + "bias" in shapes:
-                    self._declare(name[:-len("weight")] + "bias", b)
-            elif is_bn and name.endswith(".weight"):
-                self._declare(name, torch.empty(shape).normal_(1.0, 0.02))
-            elif is_bn and name.endswith(".bias"):
-                self._declare(name, torch.zeros(shape))
-            elif name.endswith("running_mean"):
-                self._declare(name, torch.zeros(shape), "buffer")
-            elif name.endswith("running_var"):
-                self._declare(name, torch.ones(shape), "buffer")
-            elif name.endswith("num_batches_tracked"):
-                self._declare(name, torch.zeros((), dtype=torch.long), "buffer")
-        assert [n for n, _, _, _ in self._specs] == [n for n, _ in spec]
+        self._layers(feature_scale, n_classes, in_channels)
         self._materialize()
 
     # UnetConv3 (networks/utils.py:99-123): (conv3x3x3 - InstanceNorm - ReLU) x 2

@@ -18,13 +18,10 @@ surface, and runs its own static launch sequence instead of a Plan:
 
 All buffers are static per batch shape, so both calls can be recorded on a launch tape.  ``FCDiscriminator`` (2-D) is not built.
 """
-import math
-
 import torch
 
 from mis_hip import ops
 from mis_hip.plan import HipNet
-from networks.unet import _conv_init
 
 SLOPE = 0.2
 DROP_P = 0.5
@@ -34,34 +31,25 @@ DROP_SALT = 0x80000000 | 0x0AD50000      # channel mode (bit 31, as mis_norm_act
 class FC3DDiscriminator(HipNet):
     ndim_spatial = 3
 
-    @staticmethod
-    def spec(num_classes, ndf=64, n_channel=1):
+    @classmethod
+    def spec(cls, num_classes, ndf=64, n_channel=1):
         """[(state_dict key, shape)] in the reference's order."""
-        k = (4, 4, 4)
-        chans = [("conv0", num_classes, ndf), ("conv1", n_channel, ndf), ("conv2", ndf, 2 * ndf), ("conv3", 2 * ndf, 4 * ndf),
-                 ("conv4", 4 * ndf, 8 * ndf)]
-        keys = []
-        for name, cin, cout in chans:
-            keys += [(f"{name}.weight", (cout, cin) + k), (f"{name}.bias", (cout,))]
-        return keys + [("classifier.weight", (2, 8 * ndf)), ("classifier.bias", (2,))]
+        return cls._declared(num_classes, ndf, n_channel)
 
     def __init__(self, num_classes, ndf=64, n_channel=1, *, pool=(6, 6, 6)):
         super().__init__()
         self.num_classes, self.ndf, self.n_channel = int(num_classes), int(ndf), int(n_channel)
         self.pool = tuple(int(p) for p in pool)
-        for name, shape in self.spec(self.num_classes, self.ndf, self.n_channel):
-            if name.endswith("weight"):
-                if len(shape) == 5:
-                    w, b = _conv_init(shape[0], shape[1], shape[2:])
-                else:                                   # nn.Linear's default: the same two uniform laws
-                    w = torch.empty(shape)
-                    torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-                    b = torch.empty(shape[0]).uniform_(-1.0 / math.sqrt(shape[1]), 1.0 / math.sqrt(shape[1]))
-                self._declare(name, w)
-                self._declare(name[:-len("weight")] + "bias", b)
+        self._layers(self.num_classes, self.ndf, self.n_channel)
         self._materialize()
         self._bufs = {}
         self._cur = None
+
+    def _layers(self, num_classes, ndf, n_channel):
+        for name, cin, cout in (("conv0", num_classes, ndf), ("conv1", n_channel, ndf), ("conv2", ndf, 2 * ndf),
+                                ("conv3", 2 * ndf, 4 * ndf), ("conv4", 4 * ndf, 8 * ndf)):
+            self._conv(name, cout, cin, (4, 4, 4))
+        self._linear("classifier", 2, 8 * ndf, law="uniform")
 
     def _build(self, plan):
         raise RuntimeError("FC3DDiscriminator has no Plan: use loss_forward / loss_backward")

@@ -14,10 +14,7 @@ The convolutions with r_k > 1 run on csrc/conv_dilated.hip, those with r_k = 1 a
 
 The layer graph is executed by ``mis_hip.plan``; nothing here computes on the CPU.
 """
-import torch
-
 from mis_hip.plan import HipNet
-from networks.unet import _conv_init
 
 _SLOPE = 0.01       # nn.LeakyReLU() default
 _DROP = 0.3         # OutPutBlock's two nn.Dropout2d
@@ -26,24 +23,10 @@ _DROP = 0.3         # OutPutBlock's two nn.Dropout2d
 class PNet2D(HipNet):
     ndim_spatial = 2
 
-    @staticmethod
-    def spec(in_chns, out_chns, num_filters, ratios=(1, 2, 4, 8, 16)):
+    @classmethod
+    def spec(cls, in_chns, out_chns, num_filters, ratios=(1, 2, 4, 8, 16)):
         """[(state_dict key, shape)] in the reference's order."""
-        F = int(num_filters)
-        keys = []
-        for k in range(1, 6):
-            cin = int(in_chns) if k == 1 else F
-            keys += [(f"block{k}.conv1.weight", (F, cin, 3, 3)), (f"block{k}.conv1.bias", (F,)),
-                     (f"block{k}.conv2.weight", (F, F, 3, 3)), (f"block{k}.conv2.bias", (F,))]
-            for bn in ("in1", "in2"):
-                keys += [(f"block{k}.{bn}.weight", (F,)), (f"block{k}.{bn}.bias", (F,)),
-                         (f"block{k}.{bn}.running_mean", (F,)), (f"block{k}.{bn}.running_var", (F,)),
-                         (f"block{k}.{bn}.num_batches_tracked", ())]
-        keys += [("catblock.conv1.weight", (5 * F, 5 * F, 1, 1)), ("catblock.conv1.bias", (5 * F,)),
-                 ("catblock.conv2.weight", (2 * F, 5 * F, 1, 1)), ("catblock.conv2.bias", (2 * F,)),
-                 ("out.conv1.weight", (F, 2 * F, 1, 1)), ("out.conv1.bias", (F,)),
-                 ("out.conv2.weight", (int(out_chns), F, 1, 1)), ("out.conv2.bias", (int(out_chns),))]
-        return keys
+        return cls._declared(in_chns, out_chns, num_filters)
 
     def __init__(self, in_chns, out_chns, num_filters, ratios):
         super().__init__()
@@ -51,24 +34,19 @@ class PNet2D(HipNet):
         self.ratios = [int(r) for r in ratios]
         if len(self.ratios) != 5:
             raise ValueError(f"PNet2D has five blocks: five dilation ratios expected, got {ratios}")
-        spec = self.spec(in_chns, out_chns, num_filters)
-        for name, shape in spec:
-            if name.endswith("weight") and len(shape) == 4:
-                w, b = _conv_init(shape[0], shape[1], shape[2:])            # torch's default Conv2d init, weight then bias
-                self._declare(name, w)
-                self._declare(name[:-len("weight")] + "bias", b)
-            elif name.endswith("weight"):
-                self._declare(name, torch.ones(shape))
-            elif name.endswith("running_mean"):
-                self._declare(name, torch.zeros(shape), "buffer")
-            elif name.endswith("running_var"):
-                self._declare(name, torch.ones(shape), "buffer")
-            elif name.endswith("num_batches_tracked"):
-                self._declare(name, torch.zeros((), dtype=torch.long), "buffer")
-            elif ".in" in name and name.endswith("bias"):
-                self._declare(name, torch.zeros(shape))
-        assert [n for n, _, _, _ in self._specs] == [n for n, _ in spec]
+        self._layers(in_chns, out_chns, num_filters)
         self._materialize()
+
+    def _layers(self, in_chns, out_chns, F):
+        for k in range(1, 6):
+            self._conv(f"block{k}.conv1", F, in_chns if k == 1 else F, (3, 3))
+            self._conv(f"block{k}.conv2", F, F, (3, 3))
+            self._norm(f"block{k}.in1", F, running=True)
+            self._norm(f"block{k}.in2", F, running=True)
+        self._conv("catblock.conv1", 5 * F, 5 * F, (1, 1))
+        self._conv("catblock.conv2", 2 * F, 5 * F, (1, 1))
+        self._conv("out.conv1", F, 2 * F, (1, 1))
+        self._conv("out.conv2", out_chns, F, (1, 1))
 
     def _bn(self, prefix):
         P, B = self.P, self.B

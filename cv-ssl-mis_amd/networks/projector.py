@@ -15,10 +15,7 @@ no weight, bias or affine gradient launch, filters packed once), a first convolu
 ``input_grad_buffer()`` to read the result.  ``strided_input``: the classifier's input ``logits[:L][0::2]`` is bound as
 the batch-strided view it is.
 """
-import torch
-
 from mis_hip.plan import HipNet
-from networks.unet import _conv_init
 
 
 class _Head(HipNet):
@@ -31,38 +28,20 @@ class _Head(HipNet):
     @classmethod
     def spec(cls, in_chns=4, ndf=8):
         """[(state_dict key, shape)] in the reference's order."""
-        widths = [int(in_chns)] + [int(ndf) << i for i in range(cls.BLOCKS)]
-        keys = []
-        for i in range(1, cls.BLOCKS + 1):
-            cin, cout = widths[i - 1], widths[i]
-            keys += [(f"conv_{i}.conv.weight", (cout, cin, 3, 3)), (f"conv_{i}.conv.bias", (cout,)),
-                     (f"conv_{i}.bn.weight", (cout,)), (f"conv_{i}.bn.bias", (cout,)),
-                     (f"conv_{i}.bn.running_mean", (cout,)), (f"conv_{i}.bn.running_var", (cout,)),
-                     (f"conv_{i}.bn.num_batches_tracked", ())]
-        return keys + [("final.weight", (widths[-1], widths[-1], 1, 1)), ("final.bias", (widths[-1],))]
+        return cls._declared([int(in_chns)] + [int(ndf) << i for i in range(cls.BLOCKS)])
 
     def __init__(self, in_chns, ndf):
         super().__init__()
         self.in_chns, self.ndf = int(in_chns), int(ndf)
         self.widths = [self.in_chns] + [self.ndf << i for i in range(self.BLOCKS)]
-        spec = self.spec(in_chns, ndf)
-        for name, shape in spec:
-            if name.endswith("conv.weight") or name == "final.weight":
-                w, b = _conv_init(shape[0], shape[1], shape[2:])            # torch's default Conv2d init, weight then bias
-                self._declare(name, w)
-                self._declare(name[:-len("weight")] + "bias", b)
-            elif name.endswith("bn.weight"):
-                self._declare(name, torch.ones(shape))
-            elif name.endswith("bn.bias"):
-                self._declare(name, torch.zeros(shape))
-            elif name.endswith("running_mean"):
-                self._declare(name, torch.zeros(shape), "buffer")
-            elif name.endswith("running_var"):
-                self._declare(name, torch.ones(shape), "buffer")
-            elif name.endswith("num_batches_tracked"):
-                self._declare(name, torch.zeros((), dtype=torch.long), "buffer")
-        assert [n for n, _, _, _ in self._specs] == [n for n, _ in spec]
+        self._layers(self.widths)
         self._materialize()
+
+    def _layers(self, widths):
+        for i in range(1, len(widths)):
+            self._conv(f"conv_{i}.conv", widths[i], widths[i - 1], (3, 3))
+            self._norm(f"conv_{i}.bn", widths[i], running=True)
+        self._conv("final", widths[-1], widths[-1], (1, 1))
 
     @property
     def out_channels(self):

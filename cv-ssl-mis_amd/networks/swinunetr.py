@@ -20,13 +20,11 @@ blocks: 3x3x3 Winograd / MFMA convs, InstanceNorm + LeakyReLU, k2s2 transposed c
 concat buffers).  The five hidden states reach the conv side through an affine-free channel LayerNorm (``proj_out``) and a
 per-sample transpose.
 """
-import math
-
 import torch
 
 from mis_hip import swin_plan as sp
-from mis_hip.plan import DownConvOp, HipNet
-from networks.unetr import UNETR, _conv_default, _trunc_normal
+from mis_hip.plan import DownConvOp, HipNet, trunc_normal
+from networks.unetr import UNETR
 
 WS = 7
 
@@ -71,25 +69,22 @@ class SwinUNETR(HipNet):
                                       "depths (2,2,2,2), heads of 16 channels, instance norm, all dropout 0, 'merging'")
         self.in_channels, self.n_classes, self.fs = in_channels, out_channels, feature_size
         self.depths, self.heads = tuple(depths), tuple(num_heads)
-        self.transposed_convs = set()
-        f, D = feature_size, self._declare
-        D("swinViT.patch_embed.proj.weight", _conv_default(f, in_channels, 2, 2, 2))
-        b = 1.0 / math.sqrt(in_channels * 8)
-        D("swinViT.patch_embed.proj.bias", torch.empty(f).uniform_(-b, b))
+        f = feature_size
+        self._conv("swinViT.patch_embed.proj", f, in_channels, (2, 2, 2))
         for i, (depth, nh) in enumerate(zip(self.depths, self.heads)):
             dim = f * 2 ** i
             for blk in range(depth):
                 p = f"swinViT.layers{i + 1}.0.blocks.{blk}"
-                D(p + ".norm1.weight", torch.ones(dim)); D(p + ".norm1.bias", torch.zeros(dim))
-                D(p + ".attn.relative_position_bias_table", _trunc_normal((2 * WS - 1) ** 3, nh))
-                D(p + ".attn.qkv.weight", _trunc_normal(3 * dim, dim)); D(p + ".attn.qkv.bias", torch.zeros(3 * dim))
-                D(p + ".attn.proj.weight", _trunc_normal(dim, dim)); D(p + ".attn.proj.bias", torch.zeros(dim))
-                D(p + ".norm2.weight", torch.ones(dim)); D(p + ".norm2.bias", torch.zeros(dim))
-                D(p + ".mlp.linear1.weight", _trunc_normal(4 * dim, dim)); D(p + ".mlp.linear1.bias", torch.zeros(4 * dim))
-                D(p + ".mlp.linear2.weight", _trunc_normal(dim, 4 * dim)); D(p + ".mlp.linear2.bias", torch.zeros(dim))
+                self._norm(p + ".norm1", dim)
+                self._declare(p + ".attn.relative_position_bias_table", trunc_normal((2 * WS - 1) ** 3, nh))
+                self._linear(p + ".attn.qkv", 3 * dim, dim)
+                self._linear(p + ".attn.proj", dim, dim)
+                self._norm(p + ".norm2", dim)
+                self._linear(p + ".mlp.linear1", 4 * dim, dim)
+                self._linear(p + ".mlp.linear2", dim, 4 * dim)
             p = f"swinViT.layers{i + 1}.0.downsample"
-            D(p + ".reduction.weight", _trunc_normal(2 * dim, 8 * dim))
-            D(p + ".norm.weight", torch.ones(8 * dim)); D(p + ".norm.bias", torch.zeros(8 * dim))
+            self._linear(p + ".reduction", 2 * dim, 8 * dim, bias=False)
+            self._norm(p + ".norm", 8 * dim)
         self._declare_res("encoder1.layer", in_channels, f)
         self._declare_res("encoder2.layer", f, f)
         self._declare_res("encoder3.layer", 2 * f, 2 * f)
@@ -98,11 +93,9 @@ class SwinUNETR(HipNet):
         self.dec_cfg = (("decoder5", 16 * f, 8 * f), ("decoder4", 8 * f, 4 * f), ("decoder3", 4 * f, 2 * f),
                         ("decoder2", 2 * f, f), ("decoder1", f, f))
         for name, cin, cout in self.dec_cfg:
-            self._declare_up(name + ".transp_conv.conv.weight", cin, cout)
+            self._declare_up(name + ".transp_conv.conv", cin, cout)
             self._declare_res(name + ".conv_block", 2 * cout, cout)
-        D("out.conv.conv.weight", _conv_default(out_channels, f, 1, 1, 1))
-        bound = 1.0 / math.sqrt(f)
-        D("out.conv.conv.bias", torch.empty(out_channels).uniform_(-bound, bound))
+        self._conv("out.conv.conv", out_channels, f, (1, 1, 1))
         self._materialize()
 
     _declare_up = UNETR._declare_up

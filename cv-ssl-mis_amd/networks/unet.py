@@ -15,23 +15,10 @@ p = [.05,.1,.2,.3,.5] after the first activation of each encoder block; decoder 
 
 The layer graph is executed by ``mis_hip.plan``; nothing here computes on the CPU.
 """
-import math
-
-import torch
-
 from mis_hip.plan import HipNet
 
 _FT = [16, 32, 64, 128, 256]
 _DROPOUT = [0.05, 0.1, 0.2, 0.3, 0.5]
-
-
-def _conv_init(cout, cin, k):
-    """torch's default Conv init: kaiming_uniform(a=sqrt(5)) weight, U(+-1/sqrt(fan_in)) bias."""
-    w = torch.empty(cout, cin, *k)
-    torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-    bound = 1.0 / math.sqrt(cin * math.prod(k))
-    b = torch.empty(cout).uniform_(-bound, bound)
-    return w, b
 
 
 class UNet(HipNet):
@@ -41,39 +28,23 @@ class UNet(HipNet):
         super().__init__()
         self.in_chns, self.class_num, self.bilinear = in_chns, class_num, bool(bilinear)
         ft = _FT
-        self._blocks = []   # (prefix, cin, cout, dropout)
         self._declare_block("encoder.in_conv.conv_conv", in_chns, ft[0])
         for i in range(1, 5):
             self._declare_block(f"encoder.down{i}.maxpool_conv.1.conv_conv", ft[i - 1], ft[i])
         for i in range(1, 5):
             c1, c2 = ft[5 - i], ft[4 - i]
             if self.bilinear:
-                w, b = _conv_init(c2, c1, (1, 1))
-                self._declare(f"decoder.up{i}.conv1x1.weight", w)
-                self._declare(f"decoder.up{i}.conv1x1.bias", b)
-            else:       # nn.ConvTranspose2d(c1, c2, 2, stride=2): weight [c1][c2][2][2]; torch's fan_in = size(1) * 4
-                w = torch.empty(c1, c2, 2, 2)
-                torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-                bound = 1.0 / math.sqrt(c2 * 4)
-                self._declare(f"decoder.up{i}.up.weight", w)
-                self._declare(f"decoder.up{i}.up.bias", torch.empty(c2).uniform_(-bound, bound))
+                self._conv(f"decoder.up{i}.conv1x1", c2, c1, (1, 1))
+            else:       # nn.ConvTranspose2d(c1, c2, 2, stride=2); not listed in transposed_convs ("Declarations")
+                self._conv(f"decoder.up{i}.up", c2, c1, (2, 2), transposed=True, listed=False)
             self._declare_block(f"decoder.up{i}.conv.conv_conv", 2 * c2, c2)
-        w, b = _conv_init(class_num, ft[0], (3, 3))
-        self._declare("decoder.out_conv.weight", w)
-        self._declare("decoder.out_conv.bias", b)
+        self._conv("decoder.out_conv", class_num, ft[0], (3, 3))
         self._materialize()
 
     def _declare_block(self, prefix, cin, cout):
-        for idx, (ci, co) in ((0, (cin, cout)), (4, (cout, cout))):
-            w, b = _conv_init(co, ci, (3, 3))
-            self._declare(f"{prefix}.{idx}.weight", w)
-            self._declare(f"{prefix}.{idx}.bias", b)
-            bn = idx + 1
-            self._declare(f"{prefix}.{bn}.weight", torch.ones(co))
-            self._declare(f"{prefix}.{bn}.bias", torch.zeros(co))
-            self._declare(f"{prefix}.{bn}.running_mean", torch.zeros(co), "buffer")
-            self._declare(f"{prefix}.{bn}.running_var", torch.ones(co), "buffer")
-            self._declare(f"{prefix}.{bn}.num_batches_tracked", torch.zeros((), dtype=torch.long), "buffer")
+        for idx, ci in ((0, cin), (4, cout)):
+            self._conv(f"{prefix}.{idx}", cout, ci, (3, 3))
+            self._norm(f"{prefix}.{idx + 1}", cout, running=True)
 
     # ConvBlock (unet.py:31-47): conv-BN-LeakyReLU-Dropout-conv-BN-LeakyReLU
     def _conv_block(self, plan, prefix, x, cout, sp, drop_p, out, need_dx=True):

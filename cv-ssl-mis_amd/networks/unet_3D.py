@@ -11,19 +11,7 @@ and ReLU; MaxPool3d(2) between encoder levels; decoder = trilinear x2 (align_cor
 cat([skip, up]) -> UnetConv3; Dropout(0.3) after ``center`` and after ``up_concat1``; final 1x1x1
 conv.  Weights: kaiming_normal(fan_in) like ``init_weights(..., 'kaiming')`` (networks_other.py:40-49).
 """
-import math
-
-import torch
-
 from mis_hip.plan import HipNet
-
-
-def _conv_init(cout, cin, k):
-    w = torch.empty(cout, cin, *k)
-    torch.nn.init.kaiming_normal_(w, a=0, mode="fan_in")
-    bound = 1.0 / math.sqrt(cin * math.prod(k))
-    b = torch.empty(cout).uniform_(-bound, bound)
-    return w, b
 
 
 class unet_3D(HipNet):
@@ -43,16 +31,12 @@ class unet_3D(HipNet):
             cin = co
         for lvl in (4, 3, 2, 1):
             self._declare_unetconv(f"up_concat{lvl}.conv", f[lvl] + f[lvl - 1], f[lvl - 1])
-        w, b = _conv_init(n_classes, f[0], (1, 1, 1))
-        self._declare("final.weight", w)
-        self._declare("final.bias", b)
+        self._conv("final", n_classes, f[0], (1, 1, 1), law="normal")
         self._materialize()
 
     def _declare_unetconv(self, prefix, cin, cout):
-        for sub, ci in (("conv1", cin), ("conv2", cout)):
-            w, b = _conv_init(cout, ci, (3, 3, 3))
-            self._declare(f"{prefix}.{sub}.0.weight", w)
-            self._declare(f"{prefix}.{sub}.0.bias", b)
+        self._conv(f"{prefix}.conv1.0", cout, cin, (3, 3, 3), law="normal")
+        self._conv(f"{prefix}.conv2.0", cout, cout, (3, 3, 3), law="normal")
 
     # UnetConv3 (networks/utils.py:99-123): (conv3x3x3 - InstanceNorm - ReLU) x 2
     def _unetconv(self, plan, prefix, x, cout, sp, out, drop_p=0.0, need_dx=True):

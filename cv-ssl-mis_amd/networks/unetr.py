@@ -14,25 +14,10 @@ LayerNorm / GELU / residual on the SwinUnet kernels, full 216-token attention in
 NCDHW conv ops of the decoder (3x3x3 / 1x1x1 MFMA convs, InstanceNorm + LeakyReLU, k2s2 transposed convs as 1x1x1 conv
 + depth-to-space, skips written straight into the concat buffers); ``proj_feat`` is a per-sample transpose.
 """
-import math
-
 import torch
 
 from mis_hip import swin_plan as sp
-from mis_hip.plan import HipNet
-
-
-def _trunc_normal(*shape, std=0.02):
-    t = torch.empty(*shape)
-    torch.nn.init.trunc_normal_(t, std=std)
-    return t
-
-
-def _conv_default(*shape):
-    """torch's default (transposed) conv init: kaiming_uniform(a=sqrt(5))"""
-    w = torch.empty(*shape)
-    torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-    return w
+from mis_hip.plan import HipNet, trunc_normal
 
 
 class UNETR(HipNet):
@@ -59,48 +44,44 @@ class UNETR(HipNet):
         self.L = self.feat_size[0] * self.feat_size[1] * self.feat_size[2]
         if self.L > 256:
             raise NotImplementedError("attention_full.hip holds one sample's tokens per workgroup: at most 256 patches")
-        self.transposed_convs = set()
         H, f = hidden_size, feature_size
-        D = self._declare
-        D("vit.patch_embedding.position_embeddings", _trunc_normal(1, self.L, H))
-        D("vit.patch_embedding.cls_token", torch.zeros(1, 1, H))
-        D("vit.patch_embedding.patch_embeddings.1.weight", _trunc_normal(H, 4096))
-        D("vit.patch_embedding.patch_embeddings.1.bias", torch.zeros(H))
+        self._declare("vit.patch_embedding.position_embeddings", trunc_normal(1, self.L, H))
+        self._declare("vit.patch_embedding.cls_token", torch.zeros(1, 1, H))
+        self._linear("vit.patch_embedding.patch_embeddings.1", H, 4096)
         for i in range(self.num_layers):
             p = f"vit.blocks.{i}"
-            D(p + ".mlp.linear1.weight", _trunc_normal(mlp_dim, H)); D(p + ".mlp.linear1.bias", torch.zeros(mlp_dim))
-            D(p + ".mlp.linear2.weight", _trunc_normal(H, mlp_dim)); D(p + ".mlp.linear2.bias", torch.zeros(H))
-            D(p + ".norm1.weight", torch.ones(H)); D(p + ".norm1.bias", torch.zeros(H))
-            D(p + ".attn.out_proj.weight", _trunc_normal(H, H)); D(p + ".attn.out_proj.bias", torch.zeros(H))
-            D(p + ".attn.qkv.weight", _trunc_normal(3 * H, H))
-            D(p + ".norm2.weight", torch.ones(H)); D(p + ".norm2.bias", torch.zeros(H))
-        D("vit.norm.weight", torch.ones(H)); D("vit.norm.bias", torch.zeros(H))
+            self._linear(p + ".mlp.linear1", mlp_dim, H)
+            self._linear(p + ".mlp.linear2", H, mlp_dim)
+            self._norm(p + ".norm1", H)
+            self._linear(p + ".attn.out_proj", H, H)
+            self._linear(p + ".attn.qkv", 3 * H, H, bias=False)
+            self._norm(p + ".norm2", H)
+        self._norm("vit.norm", H)
         self._declare_res("encoder1.layer", 1, f)
         self.enc_cfg = (("encoder2", 2 * f, 2), ("encoder3", 4 * f, 1), ("encoder4", 8 * f, 0))
         for name, cout, nl in self.enc_cfg:
-            self._declare_up(name + ".transp_conv_init.conv.weight", H, cout)
+            self._declare_up(name + ".transp_conv_init.conv", H, cout)
             for b in range(nl):
-                self._declare_up(f"{name}.blocks.{b}.0.conv.weight", cout, cout)
+                self._declare_up(f"{name}.blocks.{b}.0.conv", cout, cout)
                 self._declare_res(f"{name}.blocks.{b}.1", cout, cout)
         self.dec_cfg = (("decoder5", H, 8 * f), ("decoder4", 8 * f, 4 * f), ("decoder3", 4 * f, 2 * f),
                         ("decoder2", 2 * f, f))
         for name, cin, cout in self.dec_cfg:
-            self._declare_up(name + ".transp_conv.conv.weight", cin, cout)
+            self._declare_up(name + ".transp_conv.conv", cin, cout)
             self._declare_res(name + ".conv_block", 2 * cout, cout)
-        D("out.conv.conv.weight", _conv_default(out_channels, f, 1, 1, 1))
-        bound = 1.0 / math.sqrt(f)
-        D("out.conv.conv.bias", torch.empty(out_channels).uniform_(-bound, bound))
+        self._conv("out.conv.conv", out_channels, f, (1, 1, 1))
         self._materialize()
 
+    # MONAI's bias-free blocks: a convolution without a bias draws none
+
     def _declare_up(self, name, cin, cout):
-        self._declare(name, _conv_default(cin, cout, 2, 2, 2))        # ConvTranspose3d weight layout [Cin][Cout][2][2][2]
-        self.transposed_convs.add(name)
+        self._conv(name, cout, cin, (2, 2, 2), bias=False, transposed=True)
 
     def _declare_res(self, p, cin, cout):
-        self._declare(p + ".conv1.conv.weight", _conv_default(cout, cin, 3, 3, 3))
-        self._declare(p + ".conv2.conv.weight", _conv_default(cout, cout, 3, 3, 3))
+        self._conv(p + ".conv1.conv", cout, cin, (3, 3, 3), bias=False)
+        self._conv(p + ".conv2.conv", cout, cout, (3, 3, 3), bias=False)
         if cin != cout:
-            self._declare(p + ".conv3.conv.weight", _conv_default(cout, cin, 1, 1, 1))
+            self._conv(p + ".conv3.conv", cout, cin, (1, 1, 1), bias=False)
 
     # ---- layer graph ----
     def _resblock(self, plan, p, x, cin, cout, spatial, out, need_dx=True):

@@ -14,18 +14,12 @@ inputs are taken as they are (the other branch of :48-50).  ``MODEL.SWIN.WINDOW_
 multiple of 224) or 8 (a multiple of 256: ``--opts DATA.IMG_SIZE 256 MODEL.SWIN.WINDOW_SIZE 8``, config.py:194-195 --
 the way the reference runs SwinUnet on the 256 x 256 inputs of the cross-teaching configuration).
 """
-import math
 import re
 
 import torch
 
-from mis_hip.plan import HipNet
+from mis_hip.plan import HipNet, trunc_normal
 from mis_hip import swin_plan as sp
-
-def _trunc_normal(*shape, std=0.02):
-    t = torch.empty(*shape)
-    torch.nn.init.trunc_normal_(t, std=std)
-    return t
 
 
 def _rel_pos_index(WS):
@@ -75,27 +69,18 @@ class SwinUnet(HipNet):
         self._materialize()
 
     # ---- parameters / buffers in the reference's state_dict order ----
-    def _declare_linear(self, name, out_f, in_f, bias=True):
-        self._declare(name + ".weight", _trunc_normal(out_f, in_f))
-        if bias:
-            self._declare(name + ".bias", torch.zeros(out_f))
-
-    def _declare_ln(self, name, C):
-        self._declare(name + ".weight", torch.ones(C))
-        self._declare(name + ".bias", torch.zeros(C))
-
     def _declare_block(self, p, dim, res, heads, shift):
         WS = self.ws
         if shift > 0:
             self._declare(p + ".attn_mask", _attn_mask(res, res, shift, WS), "buffer")
-        self._declare_ln(p + ".norm1", dim)
-        self._declare(p + ".attn.relative_position_bias_table", _trunc_normal((2 * WS - 1) ** 2, heads))
+        self._norm(p + ".norm1", dim)
+        self._declare(p + ".attn.relative_position_bias_table", trunc_normal((2 * WS - 1) ** 2, heads))
         self._declare(p + ".attn.relative_position_index", _rel_pos_index(WS), "buffer")
-        self._declare_linear(p + ".attn.qkv", 3 * dim, dim)
-        self._declare_linear(p + ".attn.proj", dim, dim)
-        self._declare_ln(p + ".norm2", dim)
-        self._declare_linear(p + ".mlp.fc1", int(dim * self.mlp_ratio), dim)
-        self._declare_linear(p + ".mlp.fc2", dim, int(dim * self.mlp_ratio))
+        self._linear(p + ".attn.qkv", 3 * dim, dim)
+        self._linear(p + ".attn.proj", dim, dim)
+        self._norm(p + ".norm2", dim)
+        self._linear(p + ".mlp.fc1", int(dim * self.mlp_ratio), dim)
+        self._linear(p + ".mlp.fc2", dim, int(dim * self.mlp_ratio))
 
     def _shift(self, res, blk):
         return 0 if (blk % 2 == 0 or res <= self.ws) else self.ws // 2
@@ -103,42 +88,36 @@ class SwinUnet(HipNet):
     def _declare_all(self):
         E, nl = self.embed, len(self.depths)
         pr = self.img // 4
-        w = torch.empty(E, self.in_chans, 4, 4)
-        torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(self.in_chans * 16)
-        self._declare("swin_unet.patch_embed.proj.weight", w)
-        self._declare("swin_unet.patch_embed.proj.bias", torch.empty(E).uniform_(-bound, bound))
-        self._declare_ln("swin_unet.patch_embed.norm", E)
+        self._conv("swin_unet.patch_embed.proj", E, self.in_chans, (4, 4))
+        self._norm("swin_unet.patch_embed.norm", E)
         for i in range(nl):
             dim, res = E * 2 ** i, pr // 2 ** i
             for b in range(self.depths[i]):
                 self._declare_block(f"swin_unet.layers.{i}.blocks.{b}", dim, res, self.heads[i], self._shift(res, b))
             if i < nl - 1:
-                self._declare_linear(f"swin_unet.layers.{i}.downsample.reduction", 2 * dim, 4 * dim, bias=False)
-                self._declare_ln(f"swin_unet.layers.{i}.downsample.norm", 4 * dim)
+                self._linear(f"swin_unet.layers.{i}.downsample.reduction", 2 * dim, 4 * dim, bias=False)
+                self._norm(f"swin_unet.layers.{i}.downsample.norm", 4 * dim)
         for i in range(nl):
             k = nl - 1 - i
             dim, res = E * 2 ** k, pr // 2 ** k
             if i == 0:
-                self._declare_linear("swin_unet.layers_up.0.expand", 2 * dim, dim, bias=False)
-                self._declare_ln("swin_unet.layers_up.0.norm", dim // 2)
+                self._linear("swin_unet.layers_up.0.expand", 2 * dim, dim, bias=False)
+                self._norm("swin_unet.layers_up.0.norm", dim // 2)
             else:
                 for b in range(self.depths[k]):
                     self._declare_block(f"swin_unet.layers_up.{i}.blocks.{b}", dim, res, self.heads[k],
                                         self._shift(res, b))
                 if i < nl - 1:
-                    self._declare_linear(f"swin_unet.layers_up.{i}.upsample.expand", 2 * dim, dim, bias=False)
-                    self._declare_ln(f"swin_unet.layers_up.{i}.upsample.norm", dim // 2)
+                    self._linear(f"swin_unet.layers_up.{i}.upsample.expand", 2 * dim, dim, bias=False)
+                    self._norm(f"swin_unet.layers_up.{i}.upsample.norm", dim // 2)
         for i in range(1, nl):
             dim = E * 2 ** (nl - 1 - i)
-            self._declare_linear(f"swin_unet.concat_back_dim.{i}", dim, 2 * dim)
-        self._declare_ln("swin_unet.norm", E * 2 ** (nl - 1))
-        self._declare_ln("swin_unet.norm_up", E)
-        self._declare_linear("swin_unet.up.expand", 16 * E, E, bias=False)
-        self._declare_ln("swin_unet.up.norm", E)
-        w = torch.empty(self.num_classes, E, 1, 1)
-        torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-        self._declare("swin_unet.output.weight", w)
+            self._linear(f"swin_unet.concat_back_dim.{i}", dim, 2 * dim)
+        self._norm("swin_unet.norm", E * 2 ** (nl - 1))
+        self._norm("swin_unet.norm_up", E)
+        self._linear("swin_unet.up.expand", 16 * E, E, bias=False)
+        self._norm("swin_unet.up.norm", E)
+        self._conv("swin_unet.output", self.num_classes, E, (1, 1), bias=False)
 
     def load_from(self, config):
         """reference vision_transformer.py:54-89: loads MODEL.PRETRAIN_CKPT when given (the checkpoint is not

@@ -16,20 +16,7 @@ after block_five and block_nine, 1x1x1 output conv.
   'instancenorm'  conv + InstanceNorm3d (no affine, no running statistics: no keys) + ReLU
   'none'          conv + ReLU (ConvBlock keys ``conv.{2s}``); here the conv biases get their real gradient
 """
-import math
-
-import torch
-
 from mis_hip.plan import HipNet
-
-
-def _default_init(shape):
-    """torch's default (transposed) conv init: kaiming_uniform(a=sqrt(5)); fan_in = shape[1] * prod(kernel)."""
-    w = torch.empty(*shape)
-    torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-    fan_in = shape[1] * math.prod(shape[2:])
-    bound = 1.0 / math.sqrt(fan_in)
-    return w, bound
 
 
 class VNet(HipNet):
@@ -58,30 +45,14 @@ class VNet(HipNet):
         ]
         for name, kind, stages, cin, cout in self.layout:
             for s in range(stages):
-                ci = cin if s == 0 else cout
-                if kind == "conv":
-                    shape = (cout, ci, 3, 3, 3)
-                elif kind == "down":
-                    shape = (cout, ci, 2, 2, 2)
-                else:
-                    shape = (ci, cout, 2, 2, 2)            # ConvTranspose3d weight layout
-                w, bound = _default_init(shape)
                 p, bn = self._keys(name, s)
-                self._declare(p + ".weight", w)
-                self._declare(p + ".bias", torch.empty(cout).uniform_(-bound, bound))
-                if normalization in ('batchnorm', 'groupnorm'):
-                    self._declare(bn + ".weight", torch.ones(cout))
-                    self._declare(bn + ".bias", torch.zeros(cout))
-                if normalization == 'batchnorm':
-                    self._declare(bn + ".running_mean", torch.zeros(cout), "buffer")
-                    self._declare(bn + ".running_var", torch.ones(cout), "buffer")
-                    self._declare(bn + ".num_batches_tracked", torch.zeros((), dtype=torch.long), "buffer")
-        w, bound = _default_init((n_classes, f, 1, 1, 1))
-        self._declare("out_conv.weight", w)
-        self._declare("out_conv.bias", torch.empty(n_classes).uniform_(-bound, bound))
+                # "up" is an nn.ConvTranspose3d: not touched by the reference's kaiming / xavier re-initialisation helpers
+                self._conv(p, cout, cin if s == 0 else cout, (3, 3, 3) if kind == "conv" else (2, 2, 2),
+                           transposed=kind == "up")
+                self._norm(bn, cout, affine=normalization in ('batchnorm', 'groupnorm'),
+                           running=normalization == 'batchnorm')
+        self._conv("out_conv", n_classes, f, (1, 1, 1))
         self._materialize()
-        # nn.ConvTranspose3d weights (not touched by the reference's kaiming / xavier re-initialisation helpers)
-        self.transposed_convs = {f"{name}.conv.0.weight" for name, kind, *_ in self.layout if kind == "up"}
 
     def _keys(self, name, s):
         """(conv key, norm key) of stage s: nn.Sequential indices, 3 modules per stage (2 without a norm)."""
