@@ -110,7 +110,6 @@ class RandomRotFlipCrop:
 def crop_batch(pool, indices, gen, recs=None, out=None, label_dtype=torch.int64):
     """One launch: volumes ``indices`` -> (image [B,1,p0,p1,p2] f32, label [B,p0,p1,p2] int64 | uint8) on the device
     (ToTensor's layout, brats2019.py:196-208)."""
-    L = _l.load()
     B = len(indices)
     p = gen.output_size
     if recs is None:
@@ -124,9 +123,8 @@ def crop_batch(pool, indices, gen, recs=None, out=None, label_dtype=torch.int64)
         out = (torch.empty((B, 1) + p, dtype=torch.float32, device="cuda"),
                torch.empty((B,) + p, dtype=label_dtype, device="cuda"))
     assert out[1].dtype in (torch.int64, torch.uint8)
-    _l.check(L.mis_crop_rotflip3d(_l.ptr(pool.img), _l.ptr(pool.lab), _l.ptr(dev), B, p[0], p[1], p[2], _l.ptr(out[0]),
-                                  _l.ptr(out[1]), 8 if out[1].dtype == torch.int64 else 1, _l.stream_ptr()),
-             "mis_crop_rotflip3d")
+    _l.launch("mis_crop_rotflip3d", pool.img, pool.lab, dev, B, p[0], p[1], p[2], out[0], out[1],
+              8 if out[1].dtype == torch.int64 else 1)
     return out
 
 

@@ -162,7 +162,6 @@ def augment_batch(pool, indices, gen, recs=None, out=None):
     ``recs``: pinned uint8 staging tensor of >= B records (allocated if None); ``out``: reusable output pair."""
     if hasattr(gen, "augment"):            # a transform of more than one launch (WeakStrongAugment)
         return gen.augment(pool, indices, recs=recs, out=out)
-    L = _l.load()
     B = len(indices)
     h, w = gen.output_size
     if recs is None:
@@ -175,8 +174,7 @@ def augment_batch(pool, indices, gen, recs=None, out=None):
     if out is None:
         out = (torch.empty((B, 1, h, w), dtype=torch.float32, device="cuda"),
                torch.empty((B, h, w), dtype=torch.uint8, device="cuda"))
-    _l.check(L.mis_augment2d(_l.ptr(pool.img), _l.ptr(pool.lab), _l.ptr(dev), B, h, w, _l.ptr(out[0]), _l.ptr(out[1]),
-                             _l.stream_ptr()), "mis_augment2d")
+    _l.launch("mis_augment2d", pool.img, pool.lab, dev, B, h, w, out[0], out[1])
     return out
 
 
@@ -335,7 +333,6 @@ def zoom_slices(stack, out_size):
     """Nearest-neighbour resize of every slice of a device tensor ``stack`` [Z, H, W] (f32) to ``out_size`` --
     ``scipy.ndimage.zoom(slice, (oh / H, ow / W), order=0)`` for all Z slices in one ``mis_augment2d`` launch
     (mode 0: no augmentation).  Returns [Z, 1, oh, ow] f32 on the device."""
-    L = _l.load()
     assert stack.dim() == 3 and stack.dtype == torch.float32 and stack.is_cuda and stack.is_contiguous()
     Z, H, W = stack.shape
     oh, ow = (int(v) for v in out_size)
@@ -344,6 +341,5 @@ def zoom_slices(stack, out_size):
     host["H"], host["W"] = H, W
     dev = torch.from_numpy(host.view(np.uint8)).cuda()
     out = torch.empty((Z, 1, oh, ow), dtype=torch.float32, device="cuda")
-    _l.check(L.mis_augment2d(_l.ptr(stack), None, _l.ptr(dev), Z, oh, ow, _l.ptr(out), None, _l.stream_ptr()),
-             "mis_augment2d")
+    _l.launch("mis_augment2d", stack, None, dev, Z, oh, ow, out, None)
     return out

@@ -271,6 +271,87 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _address(v):
+    """A pointer argument that is neither None nor a plain torch.Tensor: a Parameter or another tensor subclass becomes its
+    device address, anything else (an int address, a ctypes byref) is ctypes' to convert."""
+    p = getattr(v, "data_ptr", None)
+    return v if p is None else p()
+
+
+_Tensor = torch.Tensor
+
+
+def _operands(args):
+    """The C arguments of a wrapper's operands: tuples -- (view, batch stride), (label, bytes per label), (workspace, bytes) --
+    are flattened in order, a tensor becomes its device address and None stays NULL; ctypes converts the scalars itself.
+    (On the host path of every eager launch: the common kinds are decided by their exact type, most frequent first.)"""
+    out = []
+    add = out.append
+    for a in args:
+        t = type(a)
+        if t is _Tensor:
+            add(a.data_ptr())
+        elif t is int or t is float or a is None:
+            add(a)
+        elif t is tuple:
+            for v in a:
+                t = type(v)
+                add(v.data_ptr() if t is _Tensor else v if (t is int or v is None) else _address(v))
+        else:
+            add(_address(a))
+    return out
+
+
+def launch(name, *args):
+    """Launch the entry point ``name`` on torch's current stream; raises with that name on a non-zero status.  The function is
+    looked up through load() on every call (a tape being recorded stands in for the library), and the stream is the last
+    argument, a StreamPtr: what marks the call as a launch for the tape."""
+    st = getattr(load(), name)(*_operands(args), stream_ptr())
+    if st:
+        check(st, name)
+
+
+def try_launch(name, *args):
+    """``launch`` for entry points that may refuse a shape: False on MIS_ERR_UNSUPPORTED (nothing was launched, nothing lands on
+    a tape, the caller goes on to another entry point), True after a launch; every other status raises."""
+    return _accepted(getattr(load(), name)(*_operands(args), stream_ptr()), name)
+
+
+def supported(name, *args):
+    """The same answer from an entry point without a stream that fills out-parameters for a shape or refuses it."""
+    return _accepted(getattr(load(), name)(*_operands(args)), name)
+
+
+def _accepted(st, name):
+    if st == -2:
+        return False
+    if st:
+        check(st, name)
+    return True
+
+
+def query(name, *args):
+    """The int an entry point without a stream answers (sizes, counts, selectors); a negative answer is an error code and
+    raises with that name."""
+    n = getattr(load(), name)(*_operands(args))
+    if n < 0:
+        check(n, name)
+    return n
+
+
+def select(name, *args):
+    """``query`` for the ``*_select`` entry points, whose negative answer is an answer ("no variant: use the direct kernel"),
+    not an error: it is returned."""
+    return int(getattr(load(), name)(*_operands(args)))
+
+
+def kernel_name(name, *args):
+    """What a ``*_kernel_name`` entry point prints for these arguments: the kernel a launch runs, as rocprofv3 names it."""
+    buf = ctypes.create_string_buffer(128)
+    query(name, *args, buf, 128)
+    return buf.value.decode()
+
+
 def require_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:

@@ -936,17 +936,16 @@ class Plan(PlanBase):
         mode 1 = flipped/transposed filters before the backward); weights change with every SGD update."""
         if self._packs is None:
             convs = [op for op in self.ops if type(op) is ConvOp]
-            L = ops._l.load()
             fj, bj = [], []
             for op in convs:
                 taps = op.w.data[0, 0].numel()
                 mf = ops.conv_wino_pack_mode(op.wino_f, False) if op.wino_f >= 0 else 0
                 mb = ops.conv_wino_pack_mode(op.wino_b, True) if op.wino_b >= 0 else 1
-                op.wp = torch.empty(L.mis_conv_packed_floats(op.cout, op.cin, taps, mf), dtype=torch.float32,
+                op.wp = torch.empty(_lib.query("mis_conv_packed_floats", op.cout, op.cin, taps, mf), dtype=torch.float32,
                                     device="cuda")
                 fj.append((op.w.data, op.wp, mf))
                 if op.need_dx:
-                    op.wpd = torch.empty(L.mis_conv_packed_floats(op.cout, op.cin, taps, mb), dtype=torch.float32,
+                    op.wpd = torch.empty(_lib.query("mis_conv_packed_floats", op.cout, op.cin, taps, mb), dtype=torch.float32,
                                          device="cuda")
                     bj.append((op.w.data, op.wpd, mb))
                 op.batched = True
@@ -965,7 +964,6 @@ class Plan(PlanBase):
         normalisation's backward (ops.conv_dgrad_norm)."""
         if not FUSE_DGRAD_NORM:
             return
-        L = ops._l.load()
         for conv in self.ops:
             if type(conv) is not ConvOp or not conv.need_dx or conv.wino_b not in (0, 1) or conv.ksize != (3, 3, 3):
                 continue
@@ -991,7 +989,7 @@ class Plan(PlanBase):
             if readers != 1:
                 continue
             _, _, D, H, W = norm.x.shape
-            tiles = int(L.mis_conv3d_wino_stat_tiles(D, H, W, conv.wino_b))
+            tiles = _lib.query("mis_conv3d_wino_stat_tiles", D, H, W, conv.wino_b)
             norm.ext_part = torch.zeros(N * C * tiles, 2, dtype=torch.float32, device="cuda")
             norm.ext_tiles = tiles
             norm.ext_sums = torch.zeros(N * C, 2, dtype=torch.float32, device="cuda")

@@ -82,7 +82,6 @@ class _TapedStep:
                 run(*tensors)
                 return
             self._tape_static = tuple(t.clone() for t in tensors)
-            self._tape_src = tuple((t.data_ptr(), tuple(t.shape)) for t in tensors)
             tape = _lib.LaunchTape()
             with tape.recording():
                 run(*self._tape_static)

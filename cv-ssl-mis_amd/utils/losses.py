@@ -27,29 +27,25 @@ def _as3(t):
 class _DiceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, probs, label, weight):
-        L = _l.load()
         probs, B, C, S, bs = _as3(probs)
         label = label.contiguous()
         lb = 1 if label.dtype == torch.uint8 else 8
         if label.dtype not in (torch.uint8, torch.int64):
             label, lb = label.long(), 8
-        ws = torch.empty(L.mis_dice_workspace_bytes(B, C, S), dtype=torch.uint8, device=probs.device)
+        ws = torch.empty(_l.query("mis_dice_workspace_bytes", B, C, S), dtype=torch.uint8, device=probs.device)
         out = torch.empty(1 + C, dtype=torch.float32, device=probs.device)
-        _l.check(L.mis_dice_loss_fwd(_l.ptr(probs), bs, _l.ptr(label), lb, B, C, S, _l.ptr(weight), _l.ptr(out),
-                                     _l.ptr(ws), ws.numel(), _l.stream_ptr()), "mis_dice_loss_fwd")
+        _l.launch("mis_dice_loss_fwd", probs, bs, label, lb, B, C, S, weight, out, ws, ws.numel())
         ctx.save_for_backward(probs, label, ws)
         ctx.geo = (B, C, S, bs, lb)
         return out[0], out[1:]
 
     @staticmethod
     def backward(ctx, gloss, _gdice):
-        L = _l.load()
         probs, label, ws = ctx.saved_tensors
         B, C, S, bs, lb = ctx.geo
         dp = torch.empty_like(probs)
         g = gloss.reshape(1).contiguous().float()
-        _l.check(L.mis_dice_loss_bwd(_l.ptr(probs), bs, _l.ptr(label), lb, B, C, S, _l.ptr(ws), _l.ptr(g),
-                                     _l.ptr(dp), bs, _l.stream_ptr()), "mis_dice_loss_bwd")
+        _l.launch("mis_dice_loss_bwd", probs, bs, label, lb, B, C, S, ws, g, dp, bs)
         return dp, None, None
 
 
@@ -76,25 +72,21 @@ class DiceLoss(nn.Module):
 class _SoftmaxMseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
-        L = _l.load()
         a, B, C, S, bs = _as3(a)
         b, _, _, _, _ = _as3(b)
         out = torch.empty_like(a)
-        _l.check(L.mis_softmax_mse(_l.ptr(a), bs, _l.ptr(b), bs, None, 0, _l.ptr(out), bs, B, C, S, 0,
-                                   _l.stream_ptr()), "mis_softmax_mse")
+        _l.launch("mis_softmax_mse", a, bs, b, bs, None, 0, out, bs, B, C, S, 0)
         ctx.save_for_backward(a, b)
         ctx.geo = (B, C, S, bs)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        L = _l.load()
         a, b = ctx.saved_tensors
         B, C, S, bs = ctx.geo
         g = g.contiguous()
         da = torch.empty_like(a)
-        _l.check(L.mis_softmax_mse(_l.ptr(a), bs, _l.ptr(b), bs, _l.ptr(g), bs, _l.ptr(da), bs, B, C, S, 1,
-                                   _l.stream_ptr()), "mis_softmax_mse")
+        _l.launch("mis_softmax_mse", a, bs, b, bs, g, bs, da, bs, B, C, S, 1)
         return da, None   # "Sends gradients to inputs but not the targets" (losses.py:79)
 
 
@@ -156,6 +148,4 @@ class contrastive_loss_sup(ConLoss):
 def update_ema_variables(model, ema_model, alpha, global_step):
     """reference train_mean_teacher_2D.py:124-128 -- one flat kernel instead of 2 launches per tensor."""
     alpha = min(1 - 1 / (global_step + 1), alpha)
-    L = _l.load()
-    _l.check(L.mis_ema_update(_l.ptr(ema_model.flat_param), _l.ptr(model.flat_param), model.flat_param.numel(),
-                              alpha, _l.stream_ptr()), "mis_ema_update")
+    _l.launch("mis_ema_update", ema_model.flat_param, model.flat_param, model.flat_param.numel(), alpha)
