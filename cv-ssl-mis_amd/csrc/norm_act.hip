@@ -64,6 +64,13 @@ struct DropCfg {
     const float* mask;         // optional explicit scale mask, contiguous [N][C][S] (parity tests)
 };
 
+// act(x * sc + sh), (Leaky)ReLU with `slope`: the forward apply expression, one definition for the kernels that must agree bit
+// for bit (the plain apply pass and the 3-D form with the max-pool inside), so that both contract it the same way
+__device__ __forceinline__ float mis_norm_act1(float x, float sc, float sh, float slope) {
+    const float v = x * sc + sh;
+    return v > 0.f ? v : v * slope;
+}
+
 // scale factors (0 or 1/(1-p)) for the 4 elements starting at logical index idx (multiple of 4)
 __device__ __forceinline__ void drop_scale4(const DropCfg& d, unsigned long long idx, unsigned chan, float s[4]) {
     if (d.mask) {
@@ -282,16 +289,17 @@ __global__ __launch_bounds__(256) void apply_fwd_kernel(const float* __restrict_
         const long long u = ((long long)blockIdx.x * APPLY_U + i) * 256 + threadIdx.x;
         if (u >= units) break;
         const float4 q = *reinterpret_cast<const float4*>(xb + u * 4);
-        float v[4] = {q.x * sc + sh, q.y * sc + sh, q.z * sc + sh, q.w * sc + sh};
-        float4 rq = make_float4(0.f, 0.f, 0.f, 0.f);
+        float v[4];
         if constexpr (RES) {
-            rq = *reinterpret_cast<const float4*>(ra.r + (long long)n * ra.r_bs + (long long)c * g.S + u * 4);
+            v[0] = q.x * sc + sh; v[1] = q.y * sc + sh; v[2] = q.z * sc + sh; v[3] = q.w * sc + sh;
+            const float4 rq = *reinterpret_cast<const float4*>(ra.r + (long long)n * ra.r_bs + (long long)c * g.S + u * 4);
             if (!ra.post) { v[0] += rq.x; v[1] += rq.y; v[2] += rq.z; v[3] += rq.w; }
-        }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : v[j] * slope;
-        if constexpr (RES) {
+            for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : v[j] * slope;
             if (ra.post) { v[0] += rq.x; v[1] += rq.y; v[2] += rq.z; v[3] += rq.w; }
+        } else {
+            v[0] = mis_norm_act1(q.x, sc, sh, slope); v[1] = mis_norm_act1(q.y, sc, sh, slope);
+            v[2] = mis_norm_act1(q.z, sc, sh, slope); v[3] = mis_norm_act1(q.w, sc, sh, slope);
         }
         if (drop) {
             float s[4];
@@ -304,10 +312,10 @@ __global__ __launch_bounds__(256) void apply_fwd_kernel(const float* __restrict_
 }
 
 // Forward apply for an activation that feeds a 2x max-pool (reference unet_3D.py:35-47 conv_k -> maxpool_k, unet.py:56): the
-// thread that writes a 2 (z) x 2 (y) x 8 (x) block of the activation (1 x 2 x 8 in 2-D) also takes its four window maxima
-// and argmax codes (mis_maxpool2_fwd's: dz*4 + dy*2 + dx, first maximum wins, NaN propagates) -- the pooling pass's read
-// of the full-resolution activation is gone.  grid = (ceil(Ho*Wo/4 / 256), Do, N*C); W % 8 == 0.
-template <int PZ>
+// thread that writes a block of the activation also takes its window maxima and argmax codes (mis_maxpool2_fwd's:
+// dz*4 + dy*2 + dx, first maximum wins, NaN propagates) -- the pooling pass's read of the full-resolution activation is
+// gone.  idx may be null (a forward nobody differentiates): the codes are not stored.
+// 2-D form: a thread owns a 2 (y) x 8 (x) block = four windows.  grid = (ceil(Ho*Wo/4 / 256), 1, N*C); W % 8 == 0.
 __global__ __launch_bounds__(256) void apply_fwd_pool_kernel(const float* __restrict__ x, Geo g,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ rstd,
@@ -332,40 +340,117 @@ __global__ __launch_bounds__(256) void apply_fwd_pool_kernel(const float* __rest
     float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     unsigned bi[4] = {0, 0, 0, 0};
 #pragma unroll
-    for (int dz = 0; dz < PZ; ++dz)
+    for (int dy = 0; dy < 2; ++dy) {
+        const unsigned e = (unsigned)((zo * H + (yo * 2 + dy)) * W + xq * 8);
+        float v[8];
 #pragma unroll
-        for (int dy = 0; dy < 2; ++dy) {
-            const unsigned e = (unsigned)(((zo * PZ + dz) * H + (yo * 2 + dy)) * W + xq * 8);
-            float v[8];
+        for (int h = 0; h < 2; ++h) {
+            const float4 q = *reinterpret_cast<const float4*>(xb + e + 4 * h);
+            float t[4] = {q.x * sc + sh, q.y * sc + sh, q.z * sc + sh, q.w * sc + sh};
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float4 q = *reinterpret_cast<const float4*>(xb + e + 4 * h);
-                float t[4] = {q.x * sc + sh, q.y * sc + sh, q.z * sc + sh, q.w * sc + sh};
+            for (int j = 0; j < 4; ++j) t[j] = t[j] > 0.f ? t[j] : t[j] * slope;
+            if (drop) {
+                float s4[4];
+                drop_scale4(d, lbase + e + 4 * h, (unsigned)(n * g.C + c), s4);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = t[j] > 0.f ? t[j] : t[j] * slope;
-                if (drop) {
-                    float s4[4];
-                    drop_scale4(d, lbase + e + 4 * h, (unsigned)(n * g.C + c), s4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[j] *= s4[j];
-                }
-                *reinterpret_cast<float4*>(yb + e + 4 * h) = make_float4(t[0], t[1], t[2], t[3]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[4 * h + j] = t[j];
+                for (int j = 0; j < 4; ++j) t[j] *= s4[j];
             }
+            *reinterpret_cast<float4*>(yb + e + 4 * h) = make_float4(t[0], t[1], t[2], t[3]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const float t = v[2 * j + dx];
-                    if (t > best[j] || t != t) { best[j] = t; bi[j] = dz * 4 + dy * 2 + dx; }
-                }
+            for (int j = 0; j < 4; ++j) v[4 * h + j] = t[j];
         }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const float t = v[2 * j + dx];
+                if (t > best[j] || t != t) { best[j] = t; bi[j] = dy * 2 + dx; }
+            }
+    }
     const long long So = (long long)gridDim.y * Ho * Wo;
     const unsigned o = (unsigned)((zo * Ho + yo) * Wo + xq * 4);
     *reinterpret_cast<float4*>(pooled + (long long)n * p_bs + (long long)c * So + o) =
         make_float4(best[0], best[1], best[2], best[3]);
-    *reinterpret_cast<unsigned*>(idx + (long long)nc * So + o) = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
+    if (idx)
+        *reinterpret_cast<unsigned*>(idx + (long long)nc * So + o) = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
+}
+
+// 3-D form.  A thread owns one float4 column of POOL3_ZB window blocks stacked along z, each 2 (z) x 2 (y) x 4 (x): per
+// block four float4 loads, four float4 stores, two pooled outputs (one float2) and two argmax codes (one ushort).
+// Consecutive lanes take consecutive float4s of a row, then the next row pair, then the next z group of the (n, c)
+// volume: every load and store instruction of a wave covers whole contiguous rows, and the threads of a volume are packed
+// into blocks without a gap per z slice (the 2 x 2 x 8 form strides its float4s by 32 bytes per lane and leaves a quarter
+// of each slice's last block idle at W = 96).  All loads of a thread are issued before its first store.
+// grid = (ceil(ceil(Do/ZB) * Ho * W/4 / 256), N*C); W % 4 == 0, H and D even, S < 2^31.
+constexpr int POOL3_ZB = 2;
+
+__global__ __launch_bounds__(256) void apply_fwd_pool3d_kernel(const float* __restrict__ x, Geo g,
+                                                               const float* __restrict__ mean,
+                                                               const float* __restrict__ rstd,
+                                                               const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float slope, DropCfg d,
+                                                               float* __restrict__ y, long long y_bs,
+                                                               float* __restrict__ pooled, long long p_bs,
+                                                               unsigned char* __restrict__ idx, int D, int H, int W) {
+    constexpr int ZB = POOL3_ZB;
+    const unsigned Do = (unsigned)D >> 1, Ho = (unsigned)H >> 1, Wo = (unsigned)W >> 1, Wq = (unsigned)W >> 2;
+    const unsigned Zg = (Do + ZB - 1) / ZB;
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= Zg * Ho * Wq) return;
+    const unsigned r = t / Wq, xq = t - r * Wq;
+    const unsigned zg = r / Ho, yo = r - zg * Ho;
+    const int nc = blockIdx.y;
+    const int n = nc / g.C, c = nc - n * g.C;
+    const int grp = g.per_sample ? (n * g.C + c) / g.cg : c;
+    const float sc = (gamma ? gamma[c] : 1.f) * rstd[grp];
+    const float sh = (beta ? beta[c] : 0.f) - mean[grp] * sc;
+    const float* __restrict__ xb = x + (long long)n * g.x_bs + (long long)c * g.S;
+    float* __restrict__ yb = y + (long long)n * y_bs + (long long)c * g.S;
+    const unsigned long long lbase = ((unsigned long long)n * g.C + c) * g.S;
+    const bool drop = d.p > 0.f;
+    const unsigned So = Do * Ho * Wo;
+    float4 q[ZB][4];
+#pragma unroll
+    for (int i = 0; i < ZB; ++i) {
+        const unsigned zo = zg * ZB + i;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {       // k = dz*2 + dy
+            q[i][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (zo < Do)
+                q[i][k] = *reinterpret_cast<const float4*>(xb + ((2 * zo + (k >> 1)) * (unsigned)H + 2 * yo + (k & 1)) * (unsigned)W +
+                                                           4 * xq);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < ZB; ++i) {
+        const unsigned zo = zg * ZB + i;
+        if (zo >= Do) break;
+        float best[2] = {-INFINITY, -INFINITY};
+        unsigned bi[2] = {0, 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned e = ((2 * zo + (k >> 1)) * (unsigned)H + 2 * yo + (k & 1)) * (unsigned)W + 4 * xq;
+            float v[4] = {mis_norm_act1(q[i][k].x, sc, sh, slope), mis_norm_act1(q[i][k].y, sc, sh, slope),
+                          mis_norm_act1(q[i][k].z, sc, sh, slope), mis_norm_act1(q[i][k].w, sc, sh, slope)};
+            if (drop) {
+                float s4[4];
+                drop_scale4(d, lbase + e, (unsigned)(n * g.C + c), s4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] *= s4[j];
+            }
+            *reinterpret_cast<float4*>(yb + e) = make_float4(v[0], v[1], v[2], v[3]);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const float tv = v[2 * j + dx];
+                    if (tv > best[j] || tv != tv) { best[j] = tv; bi[j] = k * 2 + dx; }
+                }
+        }
+        const unsigned o = (zo * Ho + yo) * Wo + 2 * xq;
+        *reinterpret_cast<float2*>(pooled + (long long)n * p_bs + (long long)c * So + o) = make_float2(best[0], best[1]);
+        if (idx) *reinterpret_cast<unsigned short*>(idx + (long long)nc * So + o) = (unsigned short)(bi[0] | (bi[1] << 8));
+    }
 }
 
 // ---------------- backward ----------------
@@ -836,7 +921,8 @@ extern "C" int mis_norm_act_fwd(const float* x, long long x_bs, float* y, long l
 }
 
 // mis_norm_act_fwd_g + mis_maxpool2_fwd in one pass: y = drop(act(norm(x))) [N][C][D][H][W], pooled = its 2x max-pool
-// [N][C][D/2 (D > 1)][H/2][W/2] with the argmax codes idx [N*C][So].  W % 8 == 0, H even, D even or 1.
+// [N][C][D/2 (D > 1)][H/2][W/2] with the argmax codes idx [N*C][So] (null: not stored).  H even; 3-D: W % 4 == 0, D even;
+// 2-D (D == 1): W % 8 == 0.
 extern "C" int mis_norm_act_fwd_pool(const float* x, long long x_bs, float* y, long long y_bs, float* pooled,
                                      long long p_bs, unsigned char* idx, int N, int C, int D, int H, int W,
                                      int per_sample, int cg, const float* mean, const float* rstd, const float* gamma,
@@ -847,8 +933,8 @@ extern "C" int mis_norm_act_fwd_pool(const float* x, long long x_bs, float* y, l
     int st = check_geo(x, N, C, S, x_bs);
     if (st) return st;
     if (cg < 1 || C % cg != 0 || (cg > 1 && !per_sample)) return MIS_ERR_ARG;
-    if (!y || !pooled || !idx || !mean || !rstd || y_bs < (long long)C * S) return MIS_ERR_ARG;
-    if (W % 8 || H % 2 || (D > 1 && D % 2) || S >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
+    if (!y || !pooled || !mean || !rstd || y_bs < (long long)C * S) return MIS_ERR_ARG;
+    if (W % (D > 1 ? 4 : 8) || H % 2 || (D > 1 && D % 2) || S >= (1LL << 31)) return MIS_ERR_UNSUPPORTED;
     const int pz = D > 1 ? 2 : 1, Do = D / pz;
     const long long So = (long long)Do * (H / 2) * (W / 2);
     if (p_bs < (long long)C * So) return MIS_ERR_ARG;
@@ -857,13 +943,15 @@ extern "C" int mis_norm_act_fwd_pool(const float* x, long long x_bs, float* y, l
     if (Do > 65535 || (long long)N * C > 65535) return MIS_ERR_UNSUPPORTED;
     const Geo g = make_geo(N, C, S, x_bs, per_sample, cg);
     const DropCfg d{drop_p, drop_salt, state, drop_mask};
-    const dim3 grid((unsigned)(((H / 2) * (W / 8) + 255) / 256), Do, N * C);
-    if (pz == 2)
-        hipLaunchKernelGGL(apply_fwd_pool_kernel<2>, grid, dim3(256), 0, stream, x, g, mean, rstd, gamma, beta, slope, d, y,
+    if (pz == 2) {
+        const long long threads = mis_cdiv(Do, POOL3_ZB) * (H / 2) * (W / 4);
+        hipLaunchKernelGGL(apply_fwd_pool3d_kernel, dim3((unsigned)mis_cdiv(threads, 256), N * C), dim3(256), 0, stream, x, g,
+                           mean, rstd, gamma, beta, slope, d, y, y_bs, pooled, p_bs, idx, D, H, W);
+    } else {
+        const dim3 grid((unsigned)(((H / 2) * (W / 8) + 255) / 256), 1, N * C);
+        hipLaunchKernelGGL(apply_fwd_pool_kernel, grid, dim3(256), 0, stream, x, g, mean, rstd, gamma, beta, slope, d, y,
                            y_bs, pooled, p_bs, idx, H, W);
-    else
-        hipLaunchKernelGGL(apply_fwd_pool_kernel<1>, grid, dim3(256), 0, stream, x, g, mean, rstd, gamma, beta, slope, d, y,
-                           y_bs, pooled, p_bs, idx, H, W);
+    }
     return mis_launch_status();
 }
 
@@ -1097,12 +1185,17 @@ struct HeadArgs {
     const float2* sums;                   // ... and its result
     float* hpart;                         // backward: classifier partials [N*P][K*C + K]
     int P;
+    unsigned long long* bits;             // optional [N][S/4]: the Philox keep bits of every unit (head_drop_bits), written by
+                                          // the forward, read by the backward in place of drawing them again
 };
 
 // Dropout of the 4 voxels of unit u in all C channels.  Philox mode (MASK = false): the C draws in a rolled loop (inlined C
 // times into the unrolled channel loops the generator is 160 KB of code), kept as one bit per element -- all ones and
 // keep = 1 when dropout is off, so the channel loops carry no branch.  MASK = true (explicit scale mask: parity tests)
 // reads the scale.
+// The ten Philox rounds per four elements are most of the vector instructions of the three kernels below (the backward's
+// partial-sum pass streamed at 3.2 TB/s for it, the plain passes at ~5): a training forward may store the word (8 bytes per
+// 256 bytes of input) and both backward kernels then load it (HeadArgs::bits) instead of running the generator again.
 template <int C, bool MASK>
 __device__ __forceinline__ unsigned long long head_drop_bits(const DropCfg& d, int n, long long S, long long u) {
     unsigned long long bits = ~0ull;
@@ -1157,6 +1250,7 @@ __global__ __launch_bounds__(256) void head_fwd_fused_kernel(const HeadArgs a, D
     for (int c = 0; c < C; ++c) q[c] = *reinterpret_cast<const float4*>(xb + (long long)c * a.S);
     const float keep = d.p > 0.f ? 1.f / (1.f - d.p) : 1.f;
     const unsigned long long bits = head_drop_bits<C, MASK>(d, n, a.S, u);
+    if (!MASK && a.bits) a.bits[(long long)n * units + u] = bits;
     float acc[K][4];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -1214,7 +1308,8 @@ __global__ __launch_bounds__(256, K <= 2 ? 3 : 2) void head_bwd_partial_kernel(c
             v[2 * C + K * C + k] += (g4[k].x + g4[k].y) + (g4[k].z + g4[k].w);
         }
         const float* __restrict__ xb = a.x + (long long)n * a.x_bs + u * 4;
-        const unsigned long long bits = head_drop_bits<C, MASK>(d, n, a.S, u);
+        const unsigned long long bits =
+            (!MASK && a.bits) ? a.bits[(long long)n * units + u] : head_drop_bits<C, MASK>(d, n, a.S, u);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const float4 q = *reinterpret_cast<const float4*>(xb + (long long)c * a.S);
@@ -1298,7 +1393,8 @@ __global__ __launch_bounds__(256) void head_bwd_apply_kernel(const HeadArgs a, D
     const float* __restrict__ xb = a.x + (long long)n * a.x_bs + u * 4;
     float* __restrict__ ob = a.dx + (long long)n * a.dx_bs + u * 4;
     const float keep = d.p > 0.f ? 1.f / (1.f - d.p) : 1.f;
-    const unsigned long long bits = head_drop_bits<C, MASK>(d, n, a.S, u);
+    const unsigned long long bits =
+        (!MASK && a.bits) ? a.bits[(long long)n * units + u] : head_drop_bits<C, MASK>(d, n, a.S, u);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const float4 q = *reinterpret_cast<const float4*>(xb + (long long)c * a.S);
@@ -1375,38 +1471,44 @@ extern "C" long long mis_norm_head_workspace_bytes(int N, int C, long long S, in
 
 // logits[N][K][S] = W . drop(act(norm(x))) + b  (mis_norm_act_fwd followed by a 1x1x1 mis_conv_fwd, without the
 // activation in between).  mean / rstd: per channel (per_sample = 0) or per (n, c).
+// drop_bits (may be null; ignored with an explicit drop_mask): [N][S/4] words, one keep bit per element of a unit of 4 voxels x
+// C channels (bit 4c + j), all ones with dropout off -- what mis_norm_head_bwd reads instead of drawing them again.
 extern "C" int mis_norm_head_fwd(const float* x, long long x_bs, int N, int C, long long S, int per_sample,
                                  const float* mean, const float* rstd, const float* gamma, const float* beta,
                                  float slope, float drop_p, unsigned drop_salt, const MisStepState* state,
                                  const float* drop_mask, const float* w, const float* b, int K, float* logits,
-                                 long long l_bs, hipStream_t stream) {
+                                 long long l_bs, unsigned long long* drop_bits, hipStream_t stream) {
     int st = check_geo(x, N, C, S, x_bs);
     if (st) return st;
     if (!mis_norm_head_eligible(C, K) || (per_sample && (gamma || beta))) return MIS_ERR_UNSUPPORTED;
     if (!mean || !rstd || !w || !logits || l_bs < (long long)K * S) return MIS_ERR_ARG;
-    if (l_bs % 4 != 0 || !aligned16(logits)) return MIS_ERR_UNSUPPORTED;
+    if (l_bs % 4 != 0 || !aligned16(logits) || ((uintptr_t)drop_bits & 7)) return MIS_ERR_UNSUPPORTED;
     if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && !state && !drop_mask)) return MIS_ERR_ARG;
     HeadArgs a{};
     a.x = x; a.x_bs = x_bs; a.N = N; a.K = K; a.per_sample = per_sample; a.S = S;
     a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.beta = beta; a.slope = slope; a.w = w; a.b = b;
-    a.logits = logits; a.l_bs = l_bs;
+    a.logits = logits; a.l_bs = l_bs; a.bits = drop_bits;
     const DropCfg d{drop_p, drop_salt, state, drop_mask};
     return head_launch_fwd<16>(a, d, stream);
 }
 
 // Backward of mis_norm_head_fwd from dlogits: dx (gradient at x), dgamma / dbeta (BatchNorm), dw[K][C] and db[K]
 // (null: none) of the classifier.  accumulate_* as in mis_norm_act_bwd / mis_conv_wgrad.
+// drop_bits (may be null; ignored with an explicit drop_mask): the words mis_norm_head_fwd stored for the same x, seed, offset
+// and salt.
 extern "C" int mis_norm_head_bwd(const float* x, long long x_bs, const float* dlogits, long long dl_bs, float* dx,
                                  long long dx_bs, int N, int C, long long S, int per_sample, const float* mean,
                                  const float* rstd, const float* gamma, const float* beta, float slope, float drop_p,
                                  unsigned drop_salt, const MisStepState* state, const float* drop_mask, const float* w,
                                  int K, float* dgamma, float* dbeta, int accumulate_affine, float* dw, float* db,
-                                 int accumulate_w, void* workspace, long long workspace_bytes, hipStream_t stream) {
+                                 int accumulate_w, const unsigned long long* drop_bits, void* workspace,
+                                 long long workspace_bytes, hipStream_t stream) {
     int st = check_geo(x, N, C, S, x_bs);
     if (st) return st;
     if (!mis_norm_head_eligible(C, K) || (per_sample && (gamma || beta))) return MIS_ERR_UNSUPPORTED;
     if (!dlogits || !dx || !mean || !rstd || !w || !dw || !workspace) return MIS_ERR_ARG;
-    if (dl_bs % 4 != 0 || dx_bs % 4 != 0 || !aligned16(dlogits) || !aligned16(dx)) return MIS_ERR_UNSUPPORTED;
+    if (dl_bs % 4 != 0 || dx_bs % 4 != 0 || !aligned16(dlogits) || !aligned16(dx) || ((uintptr_t)drop_bits & 7))
+        return MIS_ERR_UNSUPPORTED;
     if (dl_bs < (long long)K * S || dx_bs < (long long)C * S) return MIS_ERR_ARG;
     if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && !state && !drop_mask)) return MIS_ERR_ARG;
     if (workspace_bytes < mis_norm_head_workspace_bytes(N, C, S, per_sample, K)) return MIS_ERR_WORKSPACE;
@@ -1419,6 +1521,7 @@ extern "C" int mis_norm_head_bwd(const float* x, long long x_bs, const float* dl
     a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.beta = beta; a.slope = slope; a.w = w;
     a.dl = dlogits; a.dl_bs = dl_bs; a.dx = dx; a.dx_bs = dx_bs;
     a.part = part; a.sums = sums; a.hpart = reinterpret_cast<float*>(sums + g.G); a.P = g.P;
+    a.bits = const_cast<unsigned long long*>(drop_bits);
     const DropCfg d{drop_p, drop_salt, state, drop_mask};
     head_launch_partial<16>(a, d, stream);
     hipLaunchKernelGGL(bwd_final_kernel, dim3((g.G + 3) / 4), dim3(256), 0, stream, part, g, sums,

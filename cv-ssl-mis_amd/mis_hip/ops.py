@@ -586,22 +586,33 @@ def norm_head_eligible(C, K, per_sample, gamma, beta, cg=1, no_norm=False):
         per_sample and (gamma is not None or beta is not None))
 
 
+def norm_head_bits(x):
+    """The buffer of a head's dropout decisions (``bits`` of norm_head_fwd / _bwd): one 64-bit word per 4 voxels of a sample."""
+    N, C, D, H, W, S, _ = _geom(x)
+    return torch.empty(N * (S // 4), dtype=torch.int64, device=x.device)
+
+
 def norm_head_fwd(x, logits, per_sample, mean, rstd, gamma, beta, slope, w, b, drop_p=0.0, drop_salt=0, state=None,
-                  drop_mask=None):
-    """logits = W . drop(act(norm(x))) + b without storing the activation (w: [K, C] view of the 1x1x1 conv weight)."""
+                  drop_mask=None, bits=None):
+    """logits = W . drop(act(norm(x))) + b without storing the activation (w: [K, C] view of the 1x1x1 conv weight).
+    ``bits`` (norm_head_bits): the Philox dropout decisions are stored there for norm_head_bwd."""
     N, C, D, H, W, S, xbs = _geom(x)
     _, K, _, _, _, _, lbs = _geom(logits)
+    assert bits is None or (bits.dtype == torch.int64 and bits.is_contiguous() and bits.numel() >= N * (S // 4))
     _l.launch("mis_norm_head_fwd", x, xbs, N, C, S, int(per_sample), mean, rstd, gamma, beta, slope, drop_p, drop_salt, state,
-              drop_mask, w, b, K, logits, lbs)
+              drop_mask, w, b, K, logits, lbs, bits)
 
 
 def norm_head_bwd(x, dlogits, dx, per_sample, mean, rstd, gamma, beta, slope, w, dw, db, drop_p=0.0, drop_salt=0,
-                  state=None, drop_mask=None, dgamma=None, dbeta=None, accumulate_affine=False, accumulate_w=False):
+                  state=None, drop_mask=None, dgamma=None, dbeta=None, accumulate_affine=False, accumulate_w=False, bits=None):
+    """``bits``: what norm_head_fwd stored for this x, seed, offset and salt; read in place of drawing the mask again."""
     N, C, D, H, W, S, xbs = _geom(x)
     _, K, _, _, _, _, dlbs = _geom(dlogits)
     ws = _ws("norm", "mis_norm_head_workspace_bytes", N, C, S, int(per_sample), K)
+    assert bits is None or (bits.dtype == torch.int64 and bits.is_contiguous() and bits.numel() >= N * (S // 4))
     _l.launch("mis_norm_head_bwd", x, xbs, dlogits, dlbs, _view(dx), N, C, S, int(per_sample), mean, rstd, gamma, beta, slope,
-              drop_p, drop_salt, state, drop_mask, w, K, dgamma, dbeta, int(accumulate_affine), dw, db, int(accumulate_w), ws)
+              drop_p, drop_salt, state, drop_mask, w, K, dgamma, dbeta, int(accumulate_affine), dw, db, int(accumulate_w), bits,
+              ws)
 
 
 def group_norm_stats(x, cg, eps, mean, rstd):

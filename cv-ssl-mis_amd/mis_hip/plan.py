@@ -40,6 +40,10 @@ FUSE_FIRST = os.environ.get("MIS_FUSE_FIRST", "1") != "0"
 # max-pool backward on the load path of the producing block's normalisation backward (mis_norm_act_bwd_pool)
 FUSE_POOL = os.environ.get("MIS_FUSE_POOL", "1") != "0"
 FUSE_POOL_FWD = os.environ.get("MIS_FUSE_POOL_FWD", "1") != "0"     # ... and the pool's forward inside the apply pass
+FUSE_POOL_FWD_3D = os.environ.get("MIS_FUSE_POOL_FWD_3D", "1") != "0"      # ... of the 3-D volumes too (its own kernel form)
+# fused head with Philox dropout: the training forward stores its keep bits (8 bytes per 4 voxels x 16 channels), the two
+# backward passes load them instead of running the generator again (drop_bits of mis_norm_head_fwd / _bwd)
+HEAD_DROP_BITS = os.environ.get("MIS_HEAD_DROP_BITS", "1") != "0"
 # weight gradients on a side stream: dW of a layer needs only (x, dy) and nothing of the backward needs dW, so it runs
 # beside the data gradient / normalisation backward of the layers below and fills the CUs their launch tails leave idle
 WGRAD_STREAM = os.environ.get("MIS_WGRAD_STREAM", "1") != "0"
@@ -290,6 +294,8 @@ class NormActOp:
         self.res_post = False    # True: added behind the activation instead (Plan.add's fusion of V-Net's x_up + skip)
         self.head = None         # 1x1x1 classifier ConvOp computed in this op's pass (Plan._fuse_head); head_w / head_b:
         self.head_w = self.head_b = None     # its parameters (their gradients are written by THIS op: dist.param_progress)
+        self.head_bits = None    # the head's stored dropout decisions (HEAD_DROP_BITS), _bits: this pass's, or None
+        self._bits = None
         self.frozen = False
 
     def _affine(self):
@@ -332,14 +338,21 @@ class NormActOp:
             return
         if self.pool is not None and self.pool.fwd_fused:
             pl = self.pool
-            ops.norm_act_fwd_pool(self.x.t, self.y.t, pl.y.t, pl.idx, self.per_sample, self.mean, self.rstd, *self._affine(),
-                                  self.slope, self._p, self.salt, self._state, self._mask, cg=self.cg)
+            # a forward nobody differentiates (the teacher's) does not store the argmax codes
+            ops.norm_act_fwd_pool(self.x.t, self.y.t, pl.y.t, None if (ctx.no_backward and pl.y.shape[2] > 1) else pl.idx,
+                                  self.per_sample, self.mean, self.rstd, *self._affine(), self.slope, self._p, self.salt,
+                                  self._state, self._mask, cg=self.cg)
             return
         if self.head is not None:
             h = self.head
+            self._bits = None
+            if HEAD_DROP_BITS and self._p > 0 and self._mask is None and not ctx.no_backward:
+                if self.head_bits is None:
+                    self.head_bits = ops.norm_head_bits(self.x.t)
+                self._bits = self.head_bits
             ops.norm_head_fwd(self.x.t, h.y.t, self.per_sample, self.mean, self.rstd, *self._affine(), self.slope,
                               h.w.data.view(h.cout, h.cin), None if h.b is None else h.b.data, self._p, self.salt,
-                              self._state, self._mask)
+                              self._state, self._mask, bits=self._bits)
             return
         ops.norm_act_fwd(self.x.t, self.y.t, self.per_sample, self.mean, self.rstd, *self._affine(), self.slope, self._p,
                          self.salt, self._state, self._mask, cg=self.cg)
@@ -377,7 +390,7 @@ class NormActOp:
             ops.norm_head_bwd(self.x.t, h.y.grad(), self.x.grad(), self.per_sample, self.mean, self.rstd, *self._affine(),
                               self.slope, h.w.data.view(h.cout, h.cin), h.w.grad.view(h.cout, h.cin),
                               h.b.grad if (h.b is not None and h.bias_grad) else None, self._p, self.salt, self._state,
-                              self._mask, *self._affine_grad())
+                              self._mask, *self._affine_grad(), bits=self._bits)
             self.x.mark_written()
             return
         ops.norm_act_bwd(self.x.t, self.y.grad(), self.x.grad(), self.per_sample, self.mean, self.rstd, *self._affine(),
@@ -911,10 +924,14 @@ class Plan(PlanBase):
             if (prod is not None and prod.pool is None and prod.head is None and prod.sums is None and not prod.no_norm
                     and W % 4 == 0 and H % 2 == 0 and (D == 1 or D % 2 == 0) and D * H * W < 2 ** 31):
                 prod.pool, op.fused_into = op, prod
-                # forward too (2-D: config 2 10.47 -> 10.41 ms; measured neutral on the 3-D volumes, where the fused
-                # kernel's four row pairs per thread cost what the saved pass gains: kept on the plain pair there)
-                # when the two ops are adjacent and the rows split into 8-float pieces
-                op.fwd_fused = FUSE_POOL_FWD and D == 1 and W % 8 == 0 and prod is self.ops[-1] and y.parent is None
+                # forward too, when the two ops are adjacent (2-D: config 2 10.47 -> 10.41 ms, rows split into 8-float pieces).
+                # 3-D: the 2 x 2 x 8-per-thread form was neutral there (its four row pairs per thread cost what the saved
+                # pass gained); the form with one float4 column per thread and whole rows per load instruction
+                # (apply_fwd_pool3d_kernel) is not: apply + pool of the 96^3 level 272 -> 165 us (student, 8 volumes) and
+                # 123 -> 74 us (teacher), all four levels of both networks 532 -> 342 us per step
+                # (profiles/stream_handoffs_*_by_grid.csv)
+                fusable = (W % 8 == 0) if D == 1 else (FUSE_POOL_FWD_3D and D % 2 == 0)
+                op.fwd_fused = FUSE_POOL_FWD and fusable and prod is self.ops[-1] and y.parent is None
         self.ops.append(op)
         return y
 

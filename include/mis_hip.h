@@ -275,17 +275,24 @@ long long mis_norm_head_workspace_bytes(int N, int C, long long S, int per_sampl
 int mis_norm_head_fwd(const float* x, long long x_bs, int N, int C, long long S, int per_sample, const float* mean,
                       const float* rstd, const float* gamma, const float* beta, float slope, float drop_p,
                       unsigned drop_salt, const MisStepState* state, const float* drop_mask, const float* w,
-                      const float* b, int K, float* logits, long long l_bs, mis_stream_t stream);
+                      const float* b, int K, float* logits, long long l_bs, unsigned long long* drop_bits,
+                      mis_stream_t stream);
 int mis_norm_head_bwd(const float* x, long long x_bs, const float* dlogits, long long dl_bs, float* dx, long long dx_bs,
                       int N, int C, long long S, int per_sample, const float* mean, const float* rstd,
                       const float* gamma, const float* beta, float slope, float drop_p, unsigned drop_salt,
                       const MisStepState* state, const float* drop_mask, const float* w, int K, float* dgamma,
-                      float* dbeta, int accumulate_affine, float* dw, float* db, int accumulate_w, void* workspace,
-                      long long workspace_bytes, mis_stream_t stream);
+                      float* dbeta, int accumulate_affine, float* dw, float* db, int accumulate_w,
+                      const unsigned long long* drop_bits, void* workspace, long long workspace_bytes,
+                      mis_stream_t stream);
+/* drop_bits (NULL: none) keeps the dropout decisions between the two: [N][S/4] 64-bit words, bit 4c + j = "element j of
+ * channel c of this unit of 4 voxels is kept".  The forward stores the words it drew, the backward loads them instead of
+ * running the Philox generator again in both of its passes.  Ignored with an explicit drop_mask; all ones with
+ * drop_p == 0. */
 
 /* mis_norm_act_fwd_g + mis_maxpool2_fwd in one pass (reference unet_3D.py:35-47 conv_k -> maxpool_k; unet.py:56): writes
  * the activation y AND its 2x max-pool `pooled` [N][C][D/2 (D > 1)][H/2][W/2] with the argmax codes idx [N*C][So] (the
- * same values mis_maxpool2_fwd produces).  W % 8 == 0, H even, D even or 1. */
+ * same values mis_maxpool2_fwd produces; idx NULL: the codes are not stored).  H even; D > 1: W % 4 == 0 and D even;
+ * D == 1: W % 8 == 0. */
 int mis_norm_act_fwd_pool(const float* x, long long x_bs, float* y, long long y_bs, float* pooled, long long p_bs,
                           unsigned char* idx, int N, int C, int D, int H, int W, int per_sample, int cg,
                           const float* mean, const float* rstd, const float* gamma, const float* beta, float slope,
