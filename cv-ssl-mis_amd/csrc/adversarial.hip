@@ -22,6 +22,7 @@
 // Long contractions with few tiles are cut into slices (forward: over ci; wgrad: over col), one partial tile per slice
 // in the workspace, added in slice order by a second launch that also applies the epilogue: no atomics, bit-identical.
 #include "tail.h"
+#include "adv_head.h"
 #include "../../include/mis_hip_adversarial.h"
 
 namespace {
@@ -560,8 +561,6 @@ extern "C" int mis_conv_k4s2_wgrad(const float* x, long long x_bs, int Cx, const
 // =====================================================================================================
 namespace {
 
-constexpr int MAXK = 8;
-
 // one workgroup per (n, 4 channels): wave w sums channel c0 + w over the P voxels in a fixed order
 __global__ __launch_bounds__(NT) void head_pool_kernel(const float* __restrict__ a, long long a_bs, int C, long long P,
                                                        float* __restrict__ pooled) {
@@ -574,52 +573,6 @@ __global__ __launch_bounds__(NT) void head_pool_kernel(const float* __restrict__
     if (lane == 0) pooled[(long long)n * C + c] = s / (float)P;
 }
 
-// one workgroup: logits, per-sample cross-entropy and d loss / d logits, then the mean in sample order
-__global__ __launch_bounds__(NT) void head_final_kernel(const float* __restrict__ pooled, const float* __restrict__ w,
-                                                        const float* __restrict__ b, const int* __restrict__ target, int N,
-                                                        int C, int K, float* __restrict__ logits, float* __restrict__ dlogits,
-                                                        float* __restrict__ per_sample, float* __restrict__ loss) {
-    __shared__ float red[4 * MAXK];
-    for (int n = 0; n < N; ++n) {
-        float v[MAXK];
-#pragma unroll
-        for (int k = 0; k < MAXK; ++k) {
-            v[k] = 0.f;
-            if (k < K)
-                for (int c = threadIdx.x; c < C; c += NT) v[k] += w[(long long)k * C + c] * pooled[(long long)n * C + c];
-        }
-        mis_block_sum<MAXK>(v, red);
-        if (threadIdx.x == 0) {
-            float z[MAXK], mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < MAXK; ++k)
-                if (k < K) {
-                    z[k] = v[k] + (b ? b[k] : 0.f);
-                    logits[n * K + k] = z[k];
-                    mx = fmaxf(mx, z[k]);
-                }
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXK; ++k)
-                if (k < K) sum += expf(z[k] - mx);
-            const float lse = mx + logf(sum);
-            const int y = target[n];
-#pragma unroll
-            for (int k = 0; k < MAXK; ++k)
-                if (k < K) {
-                    dlogits[n * K + k] = (expf(z[k] - lse) - (k == y ? 1.f : 0.f)) / (float)N;
-                    if (k == y) per_sample[n] = lse - z[k];
-                }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int n = 0; n < N; ++n) s += per_sample[n];
-        loss[0] = s / (float)N;
-    }
-}
-
 // da[n][c][:] = (sum_k dlogits[n][k] w[k][c]) / P
 __global__ __launch_bounds__(NT) void head_bwd_da_kernel(const float* __restrict__ w, const float* __restrict__ dlogits,
                                                          int C, int K, long long P, float* __restrict__ da, long long da_bs) {
@@ -629,24 +582,6 @@ __global__ __launch_bounds__(NT) void head_bwd_da_kernel(const float* __restrict
     g /= (float)P;
     float* __restrict__ dst = da + (long long)n * da_bs + (long long)c * P;
     for (long long i = threadIdx.x; i < P; i += NT) dst[i] = g;
-}
-
-// dw[k][c] (+)= sum_n dlogits[n][k] pooled[n][c],  db[k] (+)= sum_n dlogits[n][k]   (sample order)
-__global__ __launch_bounds__(NT) void head_bwd_dw_kernel(const float* __restrict__ pooled, const float* __restrict__ dlogits,
-                                                         int N, int C, int K, float* __restrict__ dw, float* __restrict__ db,
-                                                         int accumulate) {
-    const int e = blockIdx.x * NT + threadIdx.x;
-    if (dw && e < K * C) {
-        const int k = e / C, c = e - k * C;
-        float s = 0.f;
-        for (int n = 0; n < N; ++n) s += dlogits[n * K + k] * pooled[(long long)n * C + c];
-        dw[e] = accumulate ? dw[e] + s : s;
-    }
-    if (db && e < K) {
-        float s = 0.f;
-        for (int n = 0; n < N; ++n) s += dlogits[n * K + e];
-        db[e] = accumulate ? db[e] + s : s;
-    }
 }
 
 int head_check(int N, int C, int K, int D, int H, int W) {

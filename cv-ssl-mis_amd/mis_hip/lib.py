@@ -80,7 +80,7 @@ def _read_header(path=HEADER_PATH):
 PROTOTYPES = _read_header()
 # headers beside mis_hip.h that declare one kernel family each (same conventions, same parser): file name -> prototypes
 EXTRA_HEADERS = ("mis_hip_fixmatch.h", "mis_hip_contrastive.h", "mis_hip_dilated.h", "mis_hip_attention_gate.h",
-                 "mis_hip_adversarial.h")
+                 "mis_hip_adversarial.h", "mis_hip_adversarial2d.h")
 EXTRA_PROTOTYPES = {h: _read_header(os.path.join(os.path.dirname(HEADER_PATH), h)) for h in EXTRA_HEADERS}
 
 STEP_STATE_BYTES = 40  # sizeof(MisStepState): static_assert in csrc/common.h

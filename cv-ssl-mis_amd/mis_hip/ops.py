@@ -1252,3 +1252,109 @@ def adam_step(param, grad, m, v, adam_state, lr, betas=(0.9, 0.999), eps=1e-8):
     n = param.numel()
     assert grad.numel() == n and m.numel() == n and v.numel() == n
     _l.launch("mis_adam_step", param, grad, m, v, n, float(lr), float(betas[0]), float(betas[1]), float(eps), adam_state)
+
+
+# ------------------------------------------------------- 2-D adversarial training (csrc/adversarial2d.hip)
+def _geom2d(t):
+    """(N, C, H, W, batch stride) of a 2-D activation: ``[N, C, H, W]`` or the ``[N, C, 1, H, W]`` view a 2-D HipNet hands out."""
+    if t.dim() == 4:
+        t = t.unsqueeze(2)
+    N, C, D, H, W, _, bs = _geom(t)
+    if D != 1:
+        raise RuntimeError(f"expected a 2-D activation [N,C,H,W] or [N,C,1,H,W], got {tuple(t.shape)} (MIS_ERR_ARG)")
+    return N, C, H, W, bs
+
+
+def _k4s2_in2d(x, logits):
+    """Geometry of the two-part input of a 2-D kernel-4 / stride-2 convolution: (N, H, W, x_bs, Cx, l_bs, Cl)."""
+    geo = None
+    xbs = lbs = Cx = Cl = 0
+    if logits is not None:
+        N, Cl, H, W, lbs = _geom2d(logits)
+        geo = (N, H, W)
+    if x is not None:
+        N, Cx, H, W, xbs = _geom2d(x)
+        if geo is not None and geo != (N, H, W):
+            raise RuntimeError(f"conv2d_k4s2: {tuple(x.shape)} and {tuple(logits.shape)} do not belong together (MIS_ERR_ARG)")
+        geo = (N, H, W)
+    if geo is None:
+        raise RuntimeError("conv2d_k4s2: no input (MIS_ERR_ARG)")
+    return (*geo, xbs, Cx, lbs, Cl)
+
+
+def _k4s2_out2d(t, N, H, W, what):
+    """(channels, (tensor, batch stride)) of an output-side tensor of a 2-D kernel-4 / stride-2 convolution of that input;
+    ``t`` None (where the entry point takes NULL): (0, (NULL, 0))."""
+    if t is None:
+        return 0, (None, 0)
+    No, Co, Ho, Wo, bs = _geom2d(t)
+    if (No, 2 * Ho, 2 * Wo) != (N, H, W):
+        raise RuntimeError(f"conv2d_k4s2: {what} {tuple(t.shape)} does not belong to an input of {(N, H, W)} (MIS_ERR_ARG)")
+    return Co, (t, bs)
+
+
+def conv2d_k4s2_fwd(x, logits, w_x, w_l, bias, bias2, y, slope=0.2, drop_scale=None):
+    """y = drop(leaky_relu(bias + bias2 + Conv2d(k=4, s=2, p=1)(cat(softmax(logits), x)), slope)).  ``logits`` / ``w_l``: the
+    channels read through a softmax and their filter (None: none); ``x`` / ``w_x``: the plain ones (None: none)."""
+    N, H, W, xbs, Cx, lbs, Cl = _k4s2_in2d(x, logits)
+    Cout, y_v = _k4s2_out2d(y, N, H, W, "y")
+    assert (w_x is None or (w_x.is_contiguous() and w_x.numel() == Cout * Cx * 16))
+    assert (w_l is None or (w_l.is_contiguous() and w_l.numel() == Cout * Cl * 16))
+    ws = _ws("k4s2", "mis_conv2d_k4s2_fwd_workspace_bytes", N, Cx + Cl, Cout, H, W)
+    _l.launch("mis_conv2d_k4s2_fwd", x, xbs, Cx, logits, lbs, Cl, w_x, w_l, bias, bias2, y_v, N, Cout, H, W, float(slope),
+              drop_scale, ws)
+
+
+def conv2d_k4s2_dgrad(dy, y, w, dx, slope=0.2, drop_scale=None):
+    """dx = the gradient at the input of the convolution with filter ``w`` [Cout, Cin, 4, 4] for the gradient ``dy`` at its
+    activated output ``y`` (None: the plain convolution's gradient)."""
+    N, Cin, H, W, dxbs = _geom2d(dx)
+    Cout, dy_v = _k4s2_out2d(dy, N, H, W, "dy")
+    y_v = _k4s2_out2d(y, N, H, W, "y")[1]
+    assert w.is_contiguous() and w.numel() == Cout * Cin * 16
+    _l.launch("mis_conv2d_k4s2_dgrad", dy_v, y_v, float(slope), drop_scale, w, dx, dxbs, N, Cin, Cout, H, W)
+
+
+def conv2d_k4s2_wgrad(x, logits, dy, y, dw_x, dw_l, dbias=None, dbias2=None, slope=0.2, drop_scale=None, accumulate=False):
+    """dw_l / dw_x (+)= the filter gradient in the two parts of conv2d_k4s2_fwd's input, dbias / dbias2 (+)= the bias
+    gradient; deterministic."""
+    N, H, W, xbs, Cx, lbs, Cl = _k4s2_in2d(x, logits)
+    Cout, dy_v = _k4s2_out2d(dy, N, H, W, "dy")
+    y_v = _k4s2_out2d(y, N, H, W, "y")[1]
+    assert (dw_x is None or (dw_x.is_contiguous() and dw_x.numel() == Cout * Cx * 16))
+    assert (dw_l is None or (dw_l.is_contiguous() and dw_l.numel() == Cout * Cl * 16))
+    ws = _ws("k4s2", "mis_conv2d_k4s2_wgrad_workspace_bytes", N, Cx + Cl, Cout, H, W)
+    _l.launch("mis_conv2d_k4s2_wgrad", x, xbs, Cx, logits, lbs, Cl, dy_v, y_v, float(slope), drop_scale, dw_x, dw_l, dbias,
+              dbias2, N, Cout, H, W, int(accumulate), ws)
+
+
+def adv_head2d_workspace(N, C, K, H, W, pool):
+    """The buffer adv_head2d_fwd leaves the pooled features and d loss / d logits in for adv_head2d_bwd."""
+    nb = _l.query("mis_adv_head2d_workspace_bytes", N, C, K, H, W, int(pool[0]), int(pool[1]))
+    return torch.empty(nb // 4, dtype=torch.float32, device="cuda")
+
+
+def adv_head2d_fwd(a, w, b, target, loss, logits, ws, pool):
+    """loss[0] = cross_entropy(Linear(flatten(AvgPool2d(pool)(a))), target), logits [N, K]; floor-mode windows."""
+    N, C, H, W, abs_ = _geom2d(a)
+    K = w.shape[0]
+    F = C * (H // int(pool[0])) * (W // int(pool[1]))
+    assert w.is_contiguous() and w.numel() == K * F and target.dtype == torch.int32 and target.numel() == N
+    assert logits.is_contiguous() and logits.numel() == N * K
+    _l.require_gpu(w, target, loss, logits, ws)
+    _l.launch("mis_adv_head2d_fwd", a, abs_, w, b, target, loss, logits, N, C, K, H, W, int(pool[0]), int(pool[1]), ws,
+              ws.numel() * 4)
+
+
+def adv_head2d_bwd(w, da, dw, db, ws, pool, shape=None, accumulate=False):
+    """da (None: not wanted; then ``shape`` = the feature's (N, C, H, W)), dw [K, F], db [K] (+)= the head's gradients; da is
+    zero in the rows and columns the floor-mode windows leave out."""
+    if da is None:
+        N, C, H, W = shape
+        da_v = (None, 0)
+    else:
+        N, C, H, W, dabs = _geom2d(da)
+        da_v = (da, dabs)
+    K = w.shape[0]
+    _l.launch("mis_adv_head2d_bwd", w, da_v, dw, db, int(accumulate), N, C, K, H, W, int(pool[0]), int(pool[1]), ws,
+              ws.numel() * 4)

@@ -945,8 +945,9 @@ class TripleViewTrainer(_Step):
 
 
 class AdversarialTrainer(_Step):
-    """Adversarial network training of the 3-D nets (reference code/train_adversarial_network_3D.py:129-175), two phases
-    per step, both recorded on the launch tape:
+    """Adversarial network training (reference code/train_adversarial_network_3D.py:129-175 with FC3DDiscriminator,
+    code/train_adversarial_network_2D.py with networks.discriminator_2d.FCDiscriminator: the discriminator is whichever object
+    is handed in, the batch follows ``model.ndim_spatial``), two phases per step, both recorded on the launch tape:
 
     A (segmenter)      student forward in train mode; the discriminator, frozen and in eval mode (no dropout), judges
                        softmax(outputs[L:]) against the target 1 and hands back its cross-entropy and the gradient at
@@ -1018,10 +1019,12 @@ class AdversarialTrainer(_Step):
         self._advance_schedule()
 
     def step(self, volume_batch, label_batch):
-        """One iteration on device tensors [B, 1, D, H, W] / [B, D, H, W]; returns the device scalar buffer ``[loss, loss_ce,
+        """One iteration on device tensors [B, 1, D, H, W] / [B, D, H, W] (a 2-D model: [B, 1, H, W] / [B, H, W]); returns the device scalar buffer ``[loss, loss_ce,
         loss_dice, consistency_loss, consistency_weight, ...]`` (no host sync); ``dan_out[0]`` is the discriminator's loss."""
-        if volume_batch.dim() != 5:
-            raise ValueError(f"adversarial training runs the 3-D networks on [B, C, D, H, W]; got {tuple(volume_batch.shape)}")
+        nd = 2 + self.model.ndim_spatial
+        if volume_batch.dim() != nd:
+            raise ValueError(f"adversarial training of a {self.model.ndim_spatial}-D network runs on "
+                             f"{'[B, C, D, H, W]' if nd == 5 else '[B, C, H, W]'}; got {tuple(volume_batch.shape)}")
         if not self.labeled_bs < volume_batch.shape[0]:
             raise ValueError(f"adversarial training needs unlabeled samples: batch {volume_batch.shape[0]}, "
                              f"labeled_bs {self.labeled_bs}")

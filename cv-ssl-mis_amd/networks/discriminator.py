@@ -16,7 +16,8 @@ surface, and runs its own static launch sequence instead of a Plan:
   ``loss_backward(params=..., dmap=...)``   the parameter gradients into ``flat_grad`` and / or the gradient at the
       softmax output into ``dmap_buffer()`` (a frozen discriminator forms no parameter gradient).
 
-All buffers are static per batch shape, so both calls can be recorded on a launch tape.  ``FCDiscriminator`` (2-D) is not built.
+All buffers are static per batch shape, so both calls can be recorded on a launch tape.  The 2-D ``FCDiscriminator`` lives in
+networks/discriminator_2d.py; the name here stays a stub that says so.
 """
 import torch
 
@@ -136,7 +137,8 @@ class FC3DDiscriminator(HipNet):
 
 
 class FCDiscriminator:
-    """The 2-D discriminator (reference code/networks/discriminator.py:58-100) is not built."""
+    """The 2-D discriminator (reference code/networks/discriminator.py:58-100) is networks.discriminator_2d.FCDiscriminator;
+    this module keeps the 3-D one only."""
 
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("FCDiscriminator (2-D) is not built on the HIP path; only FC3DDiscriminator is")
+        raise NotImplementedError("FCDiscriminator (2-D) is not in this module: import it from networks.discriminator_2d")
