@@ -1,12 +1,33 @@
-// The part of the discriminator's head that does not know the pool: Linear(C, K) -> cross-entropy on pooled features
-// [N][C], and the Linear's weight gradient.  Shared by the 3-D head (adversarial.hip: one window, the whole feature) and
-// the 2-D head (adversarial2d.hip: floor-mode windows, C = channels x windows).
+// What the 3-D and the 2-D discriminator files (adversarial.hip, adversarial2d.hip) share: the host's check of the two-part
+// input of a first layer and the grid of a streaming pass, and the part of the head that does not know the pool: Linear(C, K) ->
+// cross-entropy on pooled features [N][C], and the Linear's weight gradient (3-D: one window, the whole feature; 2-D:
+// floor-mode windows, C = channels x windows).
+// Not here, on purpose: the softmax on the load path, G = dy * act'(y) * drop and the forward epilogue read alike in both files,
+// but behind one inline function the 3-D kernels compiled to other code (same registers, same results) that measured 0.5 - 1.3 %
+// slower.  The tile loaders and MFMA loops are different designs (element gather against staged rows).
 #pragma once
 #include "common.h"
 
 namespace {
 
+constexpr int MAXCL = 4;      // channels a first layer can read through the softmax
 constexpr int MAXK = 8;
+
+// the two-part input of a first layer: Cx plain channels and Cl softmax-read ones of S elements each
+inline int adv_xsrc_check(const float* x, long long x_bs, int Cx, const float* logits, long long l_bs, int Cl, long long S) {
+    if (Cx < 0 || Cl < 0 || Cx + Cl <= 0) return MIS_ERR_ARG;
+    if ((Cx > 0 && !x) || (Cl > 0 && !logits)) return MIS_ERR_ARG;
+    if ((Cx > 0 && x_bs < Cx * S) || (Cl > 0 && l_bs < Cl * S)) return MIS_ERR_ARG;
+    if (Cl > MAXCL) return MIS_ERR_UNSUPPORTED;
+    return MIS_OK;
+}
+
+// workgroups of 256 threads of a grid-stride pass over ``items``
+inline unsigned stream_grid(long long items) {
+    long long b = mis_cdiv(items, 256);
+    if (b > 2048) b = 2048;
+    return (unsigned)(b < 1 ? 1 : b);
+}
 
 // one workgroup: logits, per-sample cross-entropy and d loss / d logits, then the mean in sample order
 __global__ __launch_bounds__(256) void head_final_kernel(const float* __restrict__ pooled, const float* __restrict__ w,

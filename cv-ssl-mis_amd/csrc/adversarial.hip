@@ -22,7 +22,7 @@
 // Long contractions with few tiles are cut into slices (forward: over ci; wgrad: over col), one partial tile per slice
 // in the workspace, added in slice order by a second launch that also applies the epilogue: no atomics, bit-identical.
 #include "tail.h"
-#include "adv_head.h"
+#include "adv_common.h"
 #include "../../include/mis_hip_adversarial.h"
 
 namespace {
@@ -30,7 +30,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int LDA = 68;
 constexpr int LDX = 80;
-constexpr int MAXCL = 4;
 
 // ------------------------------------------------------------------------------------------------ operand sources
 struct XSrc {
@@ -432,21 +431,6 @@ void wgrad_slices(int Cin, int Cout, const Geo& g, int& slices, long long& cols_
     cols_per = per * 64;
 }
 
-int xsrc_check(const float* x, long long x_bs, int Cx, const float* logits, long long l_bs, int Cl, int D, int H, int W) {
-    if (Cx < 0 || Cl < 0 || Cx + Cl <= 0) return MIS_ERR_ARG;
-    if ((Cx > 0 && !x) || (Cl > 0 && !logits)) return MIS_ERR_ARG;
-    const long long S = (long long)D * H * W;
-    if ((Cx > 0 && x_bs < Cx * S) || (Cl > 0 && l_bs < Cl * S)) return MIS_ERR_ARG;
-    if (Cl > MAXCL) return MIS_ERR_UNSUPPORTED;
-    return MIS_OK;
-}
-
-unsigned stream_grid(long long items) {
-    long long b = mis_cdiv(items, NT);
-    if (b > 2048) b = 2048;
-    return (unsigned)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 
 extern "C" int mis_channel_dropout_scale(float* scale, int N, int C, float p, unsigned salt, const MisStepState* state,
@@ -474,7 +458,7 @@ extern "C" int mis_conv_k4s2_fwd(const float* x, long long x_bs, int Cx, const f
     Geo g;
     int st = geo_check(N, Cout, D, H, W, g);
     if (st) return st;
-    st = xsrc_check(x, x_bs, Cx, logits, l_bs, Cl, D, H, W);
+    st = adv_xsrc_check(x, x_bs, Cx, logits, l_bs, Cl, (long long)D * H * W);
     if (st) return st;
     if (!y || (Cx > 0 && !w_x) || (Cl > 0 && !w_l) || !(slope > 0.f) || y_bs < Cout * g.So) return MIS_ERR_ARG;
     const int Cin = Cx + Cl;
@@ -528,7 +512,7 @@ extern "C" int mis_conv_k4s2_wgrad(const float* x, long long x_bs, int Cx, const
     Geo g;
     int st = geo_check(N, Cout, D, H, W, g);
     if (st) return st;
-    st = xsrc_check(x, x_bs, Cx, logits, l_bs, Cl, D, H, W);
+    st = adv_xsrc_check(x, x_bs, Cx, logits, l_bs, Cl, (long long)D * H * W);
     if (st) return st;
     if (!dy || (Cx > 0 && !dw_x) || (Cl > 0 && !dw_l) || !(slope > 0.f)) return MIS_ERR_ARG;
     if (dy_bs < Cout * g.So || (y && y_bs < Cout * g.So)) return MIS_ERR_ARG;

@@ -34,7 +34,7 @@
 // Long contractions with few tiles are cut into slices (forward: over ci; wgrad: over pixel tiles), one partial tile per slice
 // in the workspace, added in slice order by a second launch that also applies the epilogue: no atomics, bit-identical.
 #include "tail.h"
-#include "adv_head.h"
+#include "adv_common.h"
 #include "../../include/mis_hip_adversarial2d.h"
 
 #include <cstdint>
@@ -48,7 +48,6 @@ constexpr int XSEG = XP / 4;
 constexpr int GP = 24;        // staged G row (dgrad): columns jx0 - 4 .. jx0 + 19
 constexpr int GSEG = GP / 4;
 constexpr int GROWS = 10;     // rows jy0 - 1 .. jy0 + 8 of an 8-row tile
-constexpr int MAXCL = 4;
 
 // ------------------------------------------------------------------------------------------------ row loads
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -730,11 +729,8 @@ int geo_check(int N, int Cout, int H, int W, Geo& g) {
 }
 
 int xsrc_make(const float* x, long long x_bs, int Cx, const float* logits, long long l_bs, int Cl, int H, int W, XSrc& s) {
-    if (Cx < 0 || Cl < 0 || Cx + Cl <= 0) return MIS_ERR_ARG;
-    if ((Cx > 0 && !x) || (Cl > 0 && !logits)) return MIS_ERR_ARG;
-    const long long S = (long long)H * W;
-    if ((Cx > 0 && x_bs < Cx * S) || (Cl > 0 && l_bs < Cl * S)) return MIS_ERR_ARG;
-    if (Cl > MAXCL) return MIS_ERR_UNSUPPORTED;
+    const int st = adv_xsrc_check(x, x_bs, Cx, logits, l_bs, Cl, (long long)H * W);
+    if (st != MIS_OK) return st;
     s = XSrc{x, x_bs, Cx, logits, l_bs, Cl, H, W, (W % 4 == 0 && x_bs % 4 == 0 && al16(x)) ? 1 : 0,
              (W % 4 == 0 && l_bs % 4 == 0 && al16(logits)) ? 1 : 0};
     return MIS_OK;
@@ -766,12 +762,6 @@ void wgrad_slices(int chunks, int Cout, const Geo& g, int& slices, long long& ti
     if (s > ptiles) s = ptiles;
     tiles_per = mis_cdiv(ptiles, s);
     slices = (int)mis_cdiv(ptiles, tiles_per);
-}
-
-unsigned stream_grid(long long items) {
-    long long b = mis_cdiv(items, NT);
-    if (b > 2048) b = 2048;
-    return (unsigned)(b < 1 ? 1 : b);
 }
 
 }  // namespace
@@ -889,7 +879,7 @@ extern "C" int mis_conv2d_k4s2_wgrad(const float* x, long long x_bs, int Cx, con
 // =====================================================================================================
 // Head: AvgPool2d((ph, pw)), stride = window, floor mode -> flatten -> Linear(C nwh nww, K) -> cross-entropy, mean over the
 // samples.  workspace: pooled [N][F], dlogits [N][K], per-sample loss [N], F = C * nwh * nww.  The Linear and the
-// cross-entropy are adv_head.h's, on F features.
+// cross-entropy are adv_common.h's, on F features.
 // =====================================================================================================
 namespace {
 

@@ -1127,7 +1127,7 @@ def upsample_int_bwd(dy, dx, scale, accumulate=False):
     _l.launch("mis_upsample_int_bwd", dy, dybs, dx, dxbs, N, K, d, h, w, int(scale), int(accumulate))
 
 
-# ------------------------------------------------------- adversarial training (csrc/adversarial.hip)
+# ------------------------------------------------------- adversarial training (csrc/adversarial.hip, csrc/adversarial2d.hip)
 ADAM_STATE_BYTES = 16      # int64 step, float 1 - beta1^step, float 1 - beta2^step
 
 
@@ -1138,90 +1138,135 @@ def channel_dropout_scale(scale, p, salt, state):
     _l.launch("mis_channel_dropout_scale", scale, scale.shape[0], scale.shape[1], float(p), int(salt), state)
 
 
+# The kernel-4 / stride-2 convolutions and the head exist per dimension (mis_conv_k4s2_* / mis_adv_head_* in adversarial.hip,
+# mis_conv2d_k4s2_* / mis_adv_head2d_* in adversarial2d.hip); one wrapper each picks the family from the geometry.
+_K4S2 = {2: "conv2d_k4s2", 3: "conv_k4s2"}
+
+
+def _k4s2_geom(t, nd=None):
+    """(N, C, spatial extents, batch stride) of ``[N, C, H, W]``, ``[N, C, 1, H, W]`` (the view a 2-D HipNet hands out) or
+    ``[N, C, D, H, W]``.  ``nd`` None, for an input: a 4-D tensor or D == 1 is 2-D, which is unambiguous because the 3-D entry
+    points refuse an odd D.  An output-side tensor passes its input's ``nd``: the 3-D output of D == 2 has D == 1."""
+    N, C, D, H, W, _, bs = _geom(t.unsqueeze(2) if t.dim() == 4 else t)
+    if nd is None:
+        nd = 2 if D == 1 else 3
+    if nd == 2 and D != 1:
+        raise RuntimeError(f"expected a 2-D activation [N,C,H,W] or [N,C,1,H,W], got {tuple(t.shape)} (MIS_ERR_ARG)")
+    return N, C, (D, H, W)[3 - nd:], bs
+
+
 def _k4s2_in(x, logits):
-    """Geometry of the two-part input of a kernel-4 / stride-2 convolution: (N, D, H, W, x_bs, Cx, l_bs, Cl)."""
-    N = D = H = W = None
+    """Geometry of the two-part input of a kernel-4 / stride-2 convolution: (N, spatial, x_bs, Cx, l_bs, Cl)."""
+    geo = None
     xbs = lbs = Cx = Cl = 0
     if logits is not None:
-        N, Cl, D, H, W, _, lbs = _geom(logits)
+        N, Cl, sp, lbs = _k4s2_geom(logits)
+        geo = (N, sp)
     if x is not None:
-        Nx, Cx, Dx, Hx, Wx, _, xbs = _geom(x)
-        if N is not None and (Nx, Dx, Hx, Wx) != (N, D, H, W):
-            raise RuntimeError(f"conv_k4s2: {tuple(x.shape)} and {tuple(logits.shape)} do not belong together (MIS_ERR_ARG)")
-        N, D, H, W = Nx, Dx, Hx, Wx
-    if N is None:
+        N, Cx, sp, xbs = _k4s2_geom(x)
+        if geo is not None and geo != (N, sp):
+            raise RuntimeError(f"{_K4S2[len(sp)]}: {tuple(x.shape)} and {tuple(logits.shape)} do not belong together "
+                               "(MIS_ERR_ARG)")
+        geo = (N, sp)
+    if geo is None:
         raise RuntimeError("conv_k4s2: no input (MIS_ERR_ARG)")
-    return N, D, H, W, xbs, Cx, lbs, Cl
+    return (*geo, xbs, Cx, lbs, Cl)
 
 
-def _k4s2_out(t, N, D, H, W, what):
-    """(channels, (pointer, batch stride)) of an output-side tensor of a kernel-4 / stride-2 convolution of that input; ``t`` None
+def _k4s2_out(t, N, spatial, what):
+    """(channels, (tensor, batch stride)) of an output-side tensor of a kernel-4 / stride-2 convolution of that input; ``t`` None
     (where the entry point takes NULL): (0, (NULL, 0))."""
     if t is None:
         return 0, (None, 0)
-    No, Co, Do, Ho, Wo, _, bs = _geom(t)
-    if (No, 2 * Do, 2 * Ho, 2 * Wo) != (N, D, H, W):
-        raise RuntimeError(f"conv_k4s2: {what} {tuple(t.shape)} does not belong to an input of {(N, D, H, W)} (MIS_ERR_ARG)")
+    No, Co, so, bs = _k4s2_geom(t, len(spatial))
+    if (No, tuple(2 * e for e in so)) != (N, spatial):
+        raise RuntimeError(f"{_K4S2[len(spatial)]}: {what} {tuple(t.shape)} does not belong to an input of {(N, *spatial)} "
+                           "(MIS_ERR_ARG)")
     return Co, (t, bs)
 
 
 def conv_k4s2_fwd(x, logits, w_x, w_l, bias, bias2, y, slope=0.2, drop_scale=None):
-    """y = drop(leaky_relu(bias + bias2 + Conv3d(k=4, s=2, p=1)(cat(softmax(logits), x)), slope)).  ``logits`` / ``w_l``: the
+    """y = drop(leaky_relu(bias + bias2 + Conv{2,3}d(k=4, s=2, p=1)(cat(softmax(logits), x)), slope)).  ``logits`` / ``w_l``: the
     channels read through a softmax and their filter (None: none); ``x`` / ``w_x``: the plain ones (None: none)."""
-    N, D, H, W, xbs, Cx, lbs, Cl = _k4s2_in(x, logits)
-    Cout, y_v = _k4s2_out(y, N, D, H, W, "y")
-    assert (w_x is None or (w_x.is_contiguous() and w_x.numel() == Cout * Cx * 64))
-    assert (w_l is None or (w_l.is_contiguous() and w_l.numel() == Cout * Cl * 64))
-    ws = _ws("k4s2", "mis_conv_k4s2_fwd_workspace_bytes", N, Cx + Cl, Cout, D, H, W)
-    _l.launch("mis_conv_k4s2_fwd", x, xbs, Cx, logits, lbs, Cl, w_x, w_l, bias, bias2, y_v, N, Cout, D, H, W, float(slope),
-              drop_scale, ws)
+    N, sp, xbs, Cx, lbs, Cl = _k4s2_in(x, logits)
+    Cout, y_v = _k4s2_out(y, N, sp, "y")
+    taps, entry = 4 ** len(sp), "mis_" + _K4S2[len(sp)]
+    assert (w_x is None or (w_x.is_contiguous() and w_x.numel() == Cout * Cx * taps))
+    assert (w_l is None or (w_l.is_contiguous() and w_l.numel() == Cout * Cl * taps))
+    ws = _ws("k4s2", entry + "_fwd_workspace_bytes", N, Cx + Cl, Cout, *sp)
+    _l.launch(entry + "_fwd", x, xbs, Cx, logits, lbs, Cl, w_x, w_l, bias, bias2, y_v, N, Cout, *sp, float(slope), drop_scale,
+              ws)
 
 
 def conv_k4s2_dgrad(dy, y, w, dx, slope=0.2, drop_scale=None):
-    """dx = the gradient at the input of the convolution with filter ``w`` [Cout, Cin, 4, 4, 4] for the gradient ``dy`` at its
+    """dx = the gradient at the input of the convolution with filter ``w`` [Cout, Cin, (4,) 4, 4] for the gradient ``dy`` at its
     activated output ``y`` (None: the plain convolution's gradient)."""
-    N, Cin, D, H, W, _, dxbs = _geom(dx)
-    Cout, dy_v = _k4s2_out(dy, N, D, H, W, "dy")
-    y_v = _k4s2_out(y, N, D, H, W, "y")[1]
-    assert w.is_contiguous() and w.numel() == Cout * Cin * 64
-    _l.launch("mis_conv_k4s2_dgrad", dy_v, y_v, float(slope), drop_scale, w, dx, dxbs, N, Cin, Cout, D, H, W)
+    N, Cin, sp, dxbs = _k4s2_geom(dx)
+    Cout, dy_v = _k4s2_out(dy, N, sp, "dy")
+    y_v = _k4s2_out(y, N, sp, "y")[1]
+    assert w.is_contiguous() and w.numel() == Cout * Cin * 4 ** len(sp)
+    _l.launch("mis_" + _K4S2[len(sp)] + "_dgrad", dy_v, y_v, float(slope), drop_scale, w, dx, dxbs, N, Cin, Cout, *sp)
 
 
 def conv_k4s2_wgrad(x, logits, dy, y, dw_x, dw_l, dbias=None, dbias2=None, slope=0.2, drop_scale=None, accumulate=False):
     """dw_l / dw_x (+)= the filter gradient in the two parts of conv_k4s2_fwd's input, dbias / dbias2 (+)= the bias gradient;
     deterministic."""
-    N, D, H, W, xbs, Cx, lbs, Cl = _k4s2_in(x, logits)
-    Cout, dy_v = _k4s2_out(dy, N, D, H, W, "dy")
-    y_v = _k4s2_out(y, N, D, H, W, "y")[1]
-    assert (dw_x is None or (dw_x.is_contiguous() and dw_x.numel() == Cout * Cx * 64))
-    assert (dw_l is None or (dw_l.is_contiguous() and dw_l.numel() == Cout * Cl * 64))
-    ws = _ws("k4s2", "mis_conv_k4s2_wgrad_workspace_bytes", N, Cx + Cl, Cout, D, H, W)
-    _l.launch("mis_conv_k4s2_wgrad", x, xbs, Cx, logits, lbs, Cl, dy_v, y_v, float(slope), drop_scale, dw_x, dw_l, dbias,
-              dbias2, N, Cout, D, H, W, int(accumulate), ws)
+    N, sp, xbs, Cx, lbs, Cl = _k4s2_in(x, logits)
+    Cout, dy_v = _k4s2_out(dy, N, sp, "dy")
+    y_v = _k4s2_out(y, N, sp, "y")[1]
+    taps, entry = 4 ** len(sp), "mis_" + _K4S2[len(sp)]
+    assert (dw_x is None or (dw_x.is_contiguous() and dw_x.numel() == Cout * Cx * taps))
+    assert (dw_l is None or (dw_l.is_contiguous() and dw_l.numel() == Cout * Cl * taps))
+    ws = _ws("k4s2", entry + "_wgrad_workspace_bytes", N, Cx + Cl, Cout, *sp)
+    _l.launch(entry + "_wgrad", x, xbs, Cx, logits, lbs, Cl, dy_v, y_v, float(slope), drop_scale, dw_x, dw_l, dbias, dbias2, N,
+              Cout, *sp, int(accumulate), ws)
 
 
-def adv_head_workspace(N, C, K):
-    """The buffer adv_head_fwd leaves the pooled features and d loss / d logits in for adv_head_bwd."""
-    return torch.empty(_l.query("mis_adv_head_workspace_bytes", N, C, K) // 4, dtype=torch.float32, device="cuda")
+# The head's family is its window's: ``pool`` of two is AvgPool2d in floor mode (any number of windows, flattened), ``pool`` of
+# three or None is AvgPool3d over the whole feature, the one window the 3-D entry points take.
+def adv_head_workspace(N, C, K, H=None, W=None, pool=None):
+    """The buffer adv_head_fwd leaves the pooled features and d loss / d logits in for adv_head_bwd; the 2-D head's depends on
+    the feature's extent ``H``, ``W`` and the ``pool`` of two."""
+    if pool is None:
+        nb = _l.query("mis_adv_head_workspace_bytes", N, C, K)
+    else:
+        nb = _l.query("mis_adv_head2d_workspace_bytes", N, C, K, H, W, int(pool[0]), int(pool[1]))
+    return torch.empty(nb // 4, dtype=torch.float32, device="cuda")
 
 
 def adv_head_fwd(a, w, b, target, loss, logits, ws, pool=None):
-    """loss[0] = cross_entropy(Linear(avg_pool(a)), target), logits [N, K]; ``pool`` defaults to the feature's extent."""
-    N, C, D, H, W, _, abs_ = _geom(a)
+    """loss[0] = cross_entropy(Linear(flatten(avg_pool(a))), target), logits [N, K]; ``pool`` defaults to the 3-D feature's
+    extent."""
+    nd = 2 if pool is not None and len(pool) == 2 else 3
+    N, C, ext, abs_ = _k4s2_geom(a, nd)
+    pool = ext if pool is None else tuple(int(p) for p in pool)
     K = w.shape[0]
-    pool = (D, H, W) if pool is None else tuple(int(p) for p in pool)
-    assert w.is_contiguous() and w.numel() == K * C and target.dtype == torch.int32 and target.numel() == N
+    F = C * (ext[0] // pool[0]) * (ext[1] // pool[1]) if nd == 2 else C
+    assert w.is_contiguous() and w.numel() == K * F and target.dtype == torch.int32 and target.numel() == N
     assert logits.is_contiguous() and logits.numel() == N * K
     _l.require_gpu(w, target, loss, logits, ws)
-    _l.launch("mis_adv_head_fwd", a, abs_, w, b, target, loss, logits, N, C, K, D, H, W, pool[0], pool[1], pool[2], ws,
+    _l.launch("mis_adv_head2d_fwd" if nd == 2 else "mis_adv_head_fwd", a, abs_, w, b, target, loss, logits, N, C, K, *ext, *pool,
+              ws, ws.numel() * 4)
+
+
+def adv_head_bwd(w, da, dw, db, ws, pool=None, shape=None, accumulate=False):
+    """da (None: not wanted; then ``shape`` = the feature's (N, C, extents...)), dw [K, F], db [K] (+)= the head's gradients;
+    under a ``pool`` of two da is zero in the rows and columns the floor-mode windows leave out."""
+    nd = 2 if pool is not None and len(pool) == 2 else 3
+    if da is None:
+        (N, C, *ext), da_v = shape, (None, 0)
+    else:
+        N, C, ext, dabs = _k4s2_geom(da, nd)
+        da_v = (da, dabs)
+    K = w.shape[0]
+    win = (int(pool[0]), int(pool[1])) if nd == 2 else ()
+    _l.launch("mis_adv_head2d_bwd" if nd == 2 else "mis_adv_head_bwd", w, da_v, dw, db, int(accumulate), N, C, K, *ext, *win, ws,
               ws.numel() * 4)
 
 
-def adv_head_bwd(w, da, dw, db, ws, shape=None, accumulate=False):
-    """da (None: not wanted; then ``shape`` = the feature's (N, C, D, H, W)), dw [K, C], db [K] (+)= the head's gradients."""
-    N, C, D, H, W = shape if da is None else da.shape
-    K = w.shape[0]
-    _l.launch("mis_adv_head_bwd", w, _view(da), dw, db, int(accumulate), N, C, K, D, H, W, ws, ws.numel() * 4)
+# the 2-D names: the same functions
+conv2d_k4s2_fwd, conv2d_k4s2_dgrad, conv2d_k4s2_wgrad = conv_k4s2_fwd, conv_k4s2_dgrad, conv_k4s2_wgrad
+adv_head2d_workspace, adv_head2d_fwd, adv_head2d_bwd = adv_head_workspace, adv_head_fwd, adv_head_bwd
 
 
 def adversarial_tail(logits, label, labeled_bs, dmap, cons_loss, out, dlogits=None, cons_weight=0.0, state=None,
@@ -1252,109 +1297,3 @@ def adam_step(param, grad, m, v, adam_state, lr, betas=(0.9, 0.999), eps=1e-8):
     n = param.numel()
     assert grad.numel() == n and m.numel() == n and v.numel() == n
     _l.launch("mis_adam_step", param, grad, m, v, n, float(lr), float(betas[0]), float(betas[1]), float(eps), adam_state)
-
-
-# ------------------------------------------------------- 2-D adversarial training (csrc/adversarial2d.hip)
-def _geom2d(t):
-    """(N, C, H, W, batch stride) of a 2-D activation: ``[N, C, H, W]`` or the ``[N, C, 1, H, W]`` view a 2-D HipNet hands out."""
-    if t.dim() == 4:
-        t = t.unsqueeze(2)
-    N, C, D, H, W, _, bs = _geom(t)
-    if D != 1:
-        raise RuntimeError(f"expected a 2-D activation [N,C,H,W] or [N,C,1,H,W], got {tuple(t.shape)} (MIS_ERR_ARG)")
-    return N, C, H, W, bs
-
-
-def _k4s2_in2d(x, logits):
-    """Geometry of the two-part input of a 2-D kernel-4 / stride-2 convolution: (N, H, W, x_bs, Cx, l_bs, Cl)."""
-    geo = None
-    xbs = lbs = Cx = Cl = 0
-    if logits is not None:
-        N, Cl, H, W, lbs = _geom2d(logits)
-        geo = (N, H, W)
-    if x is not None:
-        N, Cx, H, W, xbs = _geom2d(x)
-        if geo is not None and geo != (N, H, W):
-            raise RuntimeError(f"conv2d_k4s2: {tuple(x.shape)} and {tuple(logits.shape)} do not belong together (MIS_ERR_ARG)")
-        geo = (N, H, W)
-    if geo is None:
-        raise RuntimeError("conv2d_k4s2: no input (MIS_ERR_ARG)")
-    return (*geo, xbs, Cx, lbs, Cl)
-
-
-def _k4s2_out2d(t, N, H, W, what):
-    """(channels, (tensor, batch stride)) of an output-side tensor of a 2-D kernel-4 / stride-2 convolution of that input;
-    ``t`` None (where the entry point takes NULL): (0, (NULL, 0))."""
-    if t is None:
-        return 0, (None, 0)
-    No, Co, Ho, Wo, bs = _geom2d(t)
-    if (No, 2 * Ho, 2 * Wo) != (N, H, W):
-        raise RuntimeError(f"conv2d_k4s2: {what} {tuple(t.shape)} does not belong to an input of {(N, H, W)} (MIS_ERR_ARG)")
-    return Co, (t, bs)
-
-
-def conv2d_k4s2_fwd(x, logits, w_x, w_l, bias, bias2, y, slope=0.2, drop_scale=None):
-    """y = drop(leaky_relu(bias + bias2 + Conv2d(k=4, s=2, p=1)(cat(softmax(logits), x)), slope)).  ``logits`` / ``w_l``: the
-    channels read through a softmax and their filter (None: none); ``x`` / ``w_x``: the plain ones (None: none)."""
-    N, H, W, xbs, Cx, lbs, Cl = _k4s2_in2d(x, logits)
-    Cout, y_v = _k4s2_out2d(y, N, H, W, "y")
-    assert (w_x is None or (w_x.is_contiguous() and w_x.numel() == Cout * Cx * 16))
-    assert (w_l is None or (w_l.is_contiguous() and w_l.numel() == Cout * Cl * 16))
-    ws = _ws("k4s2", "mis_conv2d_k4s2_fwd_workspace_bytes", N, Cx + Cl, Cout, H, W)
-    _l.launch("mis_conv2d_k4s2_fwd", x, xbs, Cx, logits, lbs, Cl, w_x, w_l, bias, bias2, y_v, N, Cout, H, W, float(slope),
-              drop_scale, ws)
-
-
-def conv2d_k4s2_dgrad(dy, y, w, dx, slope=0.2, drop_scale=None):
-    """dx = the gradient at the input of the convolution with filter ``w`` [Cout, Cin, 4, 4] for the gradient ``dy`` at its
-    activated output ``y`` (None: the plain convolution's gradient)."""
-    N, Cin, H, W, dxbs = _geom2d(dx)
-    Cout, dy_v = _k4s2_out2d(dy, N, H, W, "dy")
-    y_v = _k4s2_out2d(y, N, H, W, "y")[1]
-    assert w.is_contiguous() and w.numel() == Cout * Cin * 16
-    _l.launch("mis_conv2d_k4s2_dgrad", dy_v, y_v, float(slope), drop_scale, w, dx, dxbs, N, Cin, Cout, H, W)
-
-
-def conv2d_k4s2_wgrad(x, logits, dy, y, dw_x, dw_l, dbias=None, dbias2=None, slope=0.2, drop_scale=None, accumulate=False):
-    """dw_l / dw_x (+)= the filter gradient in the two parts of conv2d_k4s2_fwd's input, dbias / dbias2 (+)= the bias
-    gradient; deterministic."""
-    N, H, W, xbs, Cx, lbs, Cl = _k4s2_in2d(x, logits)
-    Cout, dy_v = _k4s2_out2d(dy, N, H, W, "dy")
-    y_v = _k4s2_out2d(y, N, H, W, "y")[1]
-    assert (dw_x is None or (dw_x.is_contiguous() and dw_x.numel() == Cout * Cx * 16))
-    assert (dw_l is None or (dw_l.is_contiguous() and dw_l.numel() == Cout * Cl * 16))
-    ws = _ws("k4s2", "mis_conv2d_k4s2_wgrad_workspace_bytes", N, Cx + Cl, Cout, H, W)
-    _l.launch("mis_conv2d_k4s2_wgrad", x, xbs, Cx, logits, lbs, Cl, dy_v, y_v, float(slope), drop_scale, dw_x, dw_l, dbias,
-              dbias2, N, Cout, H, W, int(accumulate), ws)
-
-
-def adv_head2d_workspace(N, C, K, H, W, pool):
-    """The buffer adv_head2d_fwd leaves the pooled features and d loss / d logits in for adv_head2d_bwd."""
-    nb = _l.query("mis_adv_head2d_workspace_bytes", N, C, K, H, W, int(pool[0]), int(pool[1]))
-    return torch.empty(nb // 4, dtype=torch.float32, device="cuda")
-
-
-def adv_head2d_fwd(a, w, b, target, loss, logits, ws, pool):
-    """loss[0] = cross_entropy(Linear(flatten(AvgPool2d(pool)(a))), target), logits [N, K]; floor-mode windows."""
-    N, C, H, W, abs_ = _geom2d(a)
-    K = w.shape[0]
-    F = C * (H // int(pool[0])) * (W // int(pool[1]))
-    assert w.is_contiguous() and w.numel() == K * F and target.dtype == torch.int32 and target.numel() == N
-    assert logits.is_contiguous() and logits.numel() == N * K
-    _l.require_gpu(w, target, loss, logits, ws)
-    _l.launch("mis_adv_head2d_fwd", a, abs_, w, b, target, loss, logits, N, C, K, H, W, int(pool[0]), int(pool[1]), ws,
-              ws.numel() * 4)
-
-
-def adv_head2d_bwd(w, da, dw, db, ws, pool, shape=None, accumulate=False):
-    """da (None: not wanted; then ``shape`` = the feature's (N, C, H, W)), dw [K, F], db [K] (+)= the head's gradients; da is
-    zero in the rows and columns the floor-mode windows leave out."""
-    if da is None:
-        N, C, H, W = shape
-        da_v = (None, 0)
-    else:
-        N, C, H, W, dabs = _geom2d(da)
-        da_v = (da, dabs)
-    K = w.shape[0]
-    _l.launch("mis_adv_head2d_bwd", w, da_v, dw, db, int(accumulate), N, C, K, H, W, int(pool[0]), int(pool[1]), ws,
-              ws.numel() * 4)

@@ -76,6 +76,13 @@ def _adversarial():
                                    use_tape=False)
 
 
+def _adversarial_2d():
+    from networks.discriminator_2d import FCDiscriminator
+    dan = FCDiscriminator(num_classes=C, ndf=8, pool=(1, 1))
+    return step.AdversarialTrainer(_nets_2d("unet", 1)[0], dan, labeled_bs=L, num_classes=C, iter_num=1200, seed=7,
+                                   use_tape=False)
+
+
 def _simple(cls, n, **kw):
     return lambda: cls(*_nets_2d("unet", n), labeled_bs=L, num_classes=C, iter_num=1200, seed=7, use_tape=False, **kw)
 
@@ -101,6 +108,7 @@ CONFIGS = {
     "cnn_meet_vit/unet": (_simple(step.CnnMeetVitTrainer, 3), lambda: _batch_2d(EDGE_2D), ()),
     "triple_view/unet": (_simple(step.TripleViewTrainer, 3), lambda: _batch_2d(EDGE_2D), ()),
     "adversarial/unet_3D": (_adversarial, lambda: _batch_3d(EDGE_3D), ()),
+    "adversarial/unet": (_adversarial_2d, lambda: _batch_2d(32), ()),       # conv4 leaves 2 x 2: four windows of (1, 1)
 }
 
 

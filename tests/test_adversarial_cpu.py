@@ -125,6 +125,17 @@ def test_discriminator_spec_and_command_line_are_the_references():
     assert hasattr(step, "AdversarialTrainer") and hasattr(train_common, "run_adversarial")
 
 
+def test_both_discriminators_declare_their_layer_law_on_one_body():
+    import adversarial2d_oracle as ao2
+    from networks.discriminator import SLOPE, FC3DDiscriminator, _K4S2Discriminator
+    from networks.discriminator_2d import FCDiscriminator
+    assert FCDiscriminator.LAYER_ACT == ao2.LAYER_ACT
+    assert SLOPE == ao.SLOPE and FC3DDiscriminator.LAYER_ACT == ((SLOPE, True),) * 3 + ((SLOPE, False),)
+    for cls in (FC3DDiscriminator, FCDiscriminator):
+        assert cls.loss_forward is _K4S2Discriminator.loss_forward and cls.loss_backward is _K4S2Discriminator.loss_backward
+        assert cls._static is _K4S2Discriminator._static
+
+
 def test_plain_sum_over_the_taps_agrees_with_the_convolution_operator():
     for name in ("all-padding/offset", "ragged/uniform", "thin/relu_scaled", "cube-5-20/relu_scaled", "views/relu_scaled"):
         c = ao.case(name)
