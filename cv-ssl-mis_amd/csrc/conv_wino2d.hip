@@ -300,8 +300,7 @@ using W2V3 = W2Cfg<4, 16, 2, 3>;
 extern "C" int mis_conv2d_wino_select(int N, int Cin, int Cout, int H, int W) {
     if (N <= 0 || Cin < 8 || Cin % 4 || Cout <= 0 || Cout % 16 || H <= 0 || W <= 0) return -1;
     if (((long long)Cin + 32) * H * W * 4 >= (1LL << 30)) return -1;
-    static const bool wide = [] { const char* e = getenv("MIS_W2_WIDE"); return !(e && e[0] == '0'); }();
-    if (wide && H % 8 == 0 && W % 32 == 0) return Cout % 32 == 0 ? 3 : 2;      // 8 x 32-pixel boxes: 128-byte output rows
+    if (H % 8 == 0 && W % 32 == 0) return Cout % 32 == 0 ? 3 : 2;      // 8 x 32-pixel boxes: 128-byte output rows
     if (H % 16 || W % 16) return -1;
     return Cout % 32 == 0 ? 1 : 0;
 }

@@ -344,8 +344,7 @@ using Wg2W2 = Wg2Cfg<2, 2, 16>;
 extern "C" int mis_conv2d_wino_wgrad_select(int N, int Cin, int Cout, int H, int W) {
     if (N <= 0 || Cin < 8 || Cout < 8 || H <= 0 || W <= 0) return -1;
     if (((long long)33 * H * W + W + 64) * 4 >= (1LL << 31)) return -1;
-    static const bool wide = [] { const char* e = getenv("MIS_W2_WIDE"); return !(e && e[0] == '0'); }();
-    if (wide && H % 4 == 0 && W % 32 == 0) return Cout > 16 ? 3 : 2;
+    if (H % 4 == 0 && W % 32 == 0) return Cout > 16 ? 3 : 2;
     if (H % 8 || W % 16) return -1;
     return Cout > 16 ? 1 : 0;
 }

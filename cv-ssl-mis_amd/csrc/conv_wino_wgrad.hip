@@ -1356,12 +1356,6 @@ int launch_ring3(WgArgs a, float* dw, int accumulate, hipStream_t stream) {
 
 unsigned long long* g_wr_prof = nullptr;
 
-// MIS_WGRAD_RING=0: the box kernels of round 2 for every level (A/B switch)
-bool ring_enabled() {
-    static const bool on = [] { const char* e = getenv("MIS_WGRAD_RING"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 bool variant_fits(int variant, int D, int H, int W) {
     switch (variant) {
         case 0: return W % 32 == 0 && H % 4 == 0 && D % 2 == 0;
@@ -1372,11 +1366,6 @@ bool variant_fits(int variant, int D, int H, int W) {
         case 6: return W % 24 == 0 && H % 8 == 0 && D % 2 == 0;
     }
     return false;
-}
-
-bool flat_enabled() {
-    static const bool on = [] { const char* e = getenv("MIS_WGRAD_FLAT"); return !(e && e[0] == '0'); }();
-    return on;
 }
 
 }  // namespace
@@ -1398,14 +1387,12 @@ extern "C" int mis_conv3d_wino_wgrad_kernel_name(int variant, char* name, int na
 extern "C" int mis_conv3d_wino_wgrad_select(int N, int Cin, int Cout, int D, int H, int W) {
     if (N <= 0 || Cin < 8 || Cout < 8 || D <= 0 || H <= 0 || W <= 0) return -1;
     if (((long long)17 * D * H * W + (long long)H * W + W + 64) * 4 >= (1LL << 31)) return -1;
-    if (ring_enabled()) {
-        if (variant_fits(3, D, H, W)) return 3;
-        if (variant_fits(4, D, H, W)) return 4;
-        if (variant_fits(6, D, H, W)) return 6;
-    }
+    if (variant_fits(3, D, H, W)) return 3;
+    if (variant_fits(4, D, H, W)) return 4;
+    if (variant_fits(6, D, H, W)) return 6;
     for (int v = 0; v < 3; ++v)
         if (variant_fits(v, D, H, W)) return v;
-    if (flat_enabled() && flat_fits(N, Cin, Cout, D, H, W)) return 5;       // 12^3: the flat form
+    if (flat_fits(N, Cin, Cout, D, H, W)) return 5;       // 12^3: the flat form
     return -1;
 }
 

@@ -74,10 +74,6 @@ struct GemmArgs {
 
 enum { EP_NONE = 0, EP_GELU_FWD = 1, EP_GELU_BWD = 2, EP_RESIDUAL = 3, EP_LNHEAD = 4, EP_RESIDUAL_LN = 5 };
 
-// an integer knob of the environment, knob(getenv("MIS_GEMM_.."), default): the callers keep it in a function-local static
-// (read once, at first use), each knob in one place
-int knob(const char* value, int dflt) { return value ? atoi(value) : dflt; }
-
 // same functions as token_ops.hip::gelu_kernel (common.h)
 __device__ __forceinline__ float gelu_f(float x) { return mis_gelu(x); }
 __device__ __forceinline__ float gelu_grad_f(float x) { return mis_gelu_grad(x); }
@@ -166,16 +162,16 @@ __global__ __launch_bounds__(256) void gemm_split_batch_kernel(const SplitJob* _
 // products (attention_impl.inc) as bf16x3 products; 0 = fp32 MFMA everywhere.  Default 7 (MIS_GEMM_BF3 overrides at load;
 // mis_gemm_set_split_precision at run time: bench.py times both).
 std::atomic<int>& gemm_bf3_state() {
-    static std::atomic<int> m{knob(getenv("MIS_GEMM_BF3"), 7) & 7};
+    static std::atomic<int> m{(getenv("MIS_GEMM_BF3") ? atoi(getenv("MIS_GEMM_BF3")) : 7) & 7};
     return m;
 }
 bool gemm_bf3() { return gemm_bf3_state().load(std::memory_order_relaxed) & 1; }
 bool gemm_bf3_tn() { return gemm_bf3_state().load(std::memory_order_relaxed) & 2; }
 
 // ------------------------------------------------------------------------------------------------ NT
-// NW waves per workgroup: 4 (2 x 2 wave tiles of BMT/2 x BN/2) or 8 (4 x 2 wave tiles of BMT/4 x BN/2: the same tile, stages and
-// LDS, twice the waves per SIMD -- the operand stage is what limits residency (52 KB: three workgroups per CU), the kernel needs
-// ~75 registers, and what the k-loop lacks is waves to hide its per-k-step DMA wait and barrier behind: profiles/r06_gemm_nt_pmc.txt)
+// NW waves per workgroup: 4 (2 x 2 wave tiles of BMT/2 x BN/2) is the one form compiled.  The code also holds for 8 (4 x 2 wave
+// tiles of BMT/4 x BN/2: the same tile, stages and LDS, twice the waves per SIMD), which lost inside the step (DESIGN.md,
+// "Run-time switches") and is not instantiated; NW stays a template parameter because it is part of the kernels' names
 template <int BMT, int BN, int PREC = 0, int NW = 4>
 struct NtCfg {
     static constexpr int WROWS = BMT / (NW / 2);          // rows of a wave tile
@@ -1842,16 +1838,23 @@ __global__ __launch_bounds__(256) void gemm_reduce_kernel(const GemmArgs a) {
 // into the GemmArgs the kernel reads), the reduce launch.  run() launches a plan, plan_name() prints it, the *_workspace_bytes
 // queries read its slices: what a profile row says and what a workspace holds cannot drift from what runs.
 
+// ---- thresholds of the rules below (each was an A/B switch once; the measurements that settled them: DESIGN.md, "Run-time switches")
+constexpr int NT_BF3_PCT = 50;         // cost of a bf16x3 k-loop in percent of the fp32 one: its K = 32 products run it ~2x faster
+constexpr int B3_KMAX_SHORT = 96;      // pre-split form: up to this K the short-contraction kernel on fp32 B keeps the shape
+constexpr int REGA_KMIN = 96;          // register-A form: the shortest contraction it takes (three k-blocks of 32)
+constexpr int REGA_TILES = 512;        // ... needs this many 128 x 96 tiles: three resident workgroups on each CU
+// ... and, from the per-shape sweep at 48 images (scripts/gemm_nt_bench.py, profiles/r06_gemm_nt_rega.txt), is ahead of the
+// staged kernels for the 10^5-row stage (M >= REGA_MSQ) and, from 3 x 10^4 rows (REGA_MMIN), where the output is wider than the
+// contraction; behind them below that.  N == 96 (proj / fc2 of a 96-channel block) goes to it from REGA_MMIN rows whatever K:
+// the register-A kernels carry the residual add AND the next LayerNorm in their epilogue (mis_gemm_nt_residual_ln) -- a
+// LayerNorm pass less outweighs the few us the staged kernel is ahead by at 7 x 10^4 rows
+constexpr int REGA_MMIN = 30000, REGA_MSQ = 100000;
+constexpr int REGA_WALK = 768;         // register-A walking form: grid cap, three workgroups per CU
+
 // ---- tile rules and cost models
 // tile edge of the TN form / tile width of the NT form: 96 when it removes padding
 int tn_tile(int M, int N) { return (M % 96 == 0 && N % 96 == 0 && (M % 128 != 0 || N % 128 != 0)) ? 96 : 128; }
 int nt_tile_n(int N) { return (N % 96 == 0 && N % 128 != 0) ? 96 : 128; }
-// pre-split B: a 64 x 96 tile keeps three workgroups per CU (52 KB of LDS; 64 x 128 needs 64 KB: two)
-int nt_tile_n_b3(int N) {       // (MIS_GEMM_B3_RULE=0 sweeps only)
-    static const int pref = knob(getenv("MIS_GEMM_B3_BN"), 96);
-    if (pref == 96 && N % 96 == 0) return 96;
-    return nt_tile_n(N);
-}
 
 // NT form: rows per tile (128 / 64) and K slices.  Split-K only when the tiles cannot fill the chip (deep SwinUnet stages,
 // the ViT of UNETR: 60 .. 114 tiles of 128 rows) and K is long: every slice costs a write + read of the M x N partial
@@ -1860,9 +1863,7 @@ int nt_tile_n_b3(int N) {       // (MIS_GEMM_B3_RULE=0 sweeps only)
 // 114 tiles 158 us).  64-row tiles double the tile count instead: UNETR's M = 1728, N = K = 768 Linears are 84 tiles x 3
 // slices + reduction (49 + 20 us) or 162 tiles unsplit -- the cost model below (workgroup time ~ rows x K / slices, +
 // a fixed share per round, + the reduction) picks between them.
-void nt_choice(int M, int N, int K, int& bm, int& ks, int rows_arg = 0, int bn_arg = 0) {
-    static const int force_env = knob(getenv("MIS_GEMM_BM"), 0);
-    const int force = rows_arg ? rows_arg : force_env;
+void nt_choice(int M, int N, int K, int& bm, int& ks, int force = 0, int bn_arg = 0) {      // force: 64 / 128 rows, 0 = choose
     const long long tn = mis_cdiv(N, bn_arg ? bn_arg : nt_tile_n(N));
     if (force != 128 && mis_cdiv(M, 128) * tn >= 512) {      // plenty of tiles: 64 rows = three resident workgroups per CU
         bm = 64; ks = 1;                                      // instead of two (SwinUnet 36.2 -> 35.6 ms per step)
@@ -1878,12 +1879,11 @@ void nt_choice(int M, int N, int K, int& bm, int& ks, int rows_arg = 0, int bn_a
         if (s < 2) s = 1;
         const long long rounds = mis_cdiv(tiles * s, 256);
         // units: one row of a tile over one k; 128 rows x 768 k = 40 us measured -> 2458 units / us.  bf16x3 products run the
-        // k-loop ~2x faster (MIS_GEMM_NT_BF3_SCALE percent of the fp32 k-loop cost), the fixed costs stay: fewer slices pay
-        static const int bf3_pct = knob(getenv("MIS_GEMM_NT_BF3_SCALE"), 50);
-        const long long kloop = (long long)rows * mis_cdiv(K, s) * (gemm_bf3() ? bf3_pct : 100) / 100;
+        // k-loop ~2x faster (NT_BF3_PCT percent of the fp32 k-loop cost), the fixed costs stay: fewer slices pay
+        const long long kloop = (long long)rows * mis_cdiv(K, s) * (gemm_bf3() ? NT_BF3_PCT : 100) / 100;
         long long cost = rounds * (kloop + 128 * 96);
         if (s > 1) cost += 49152 + (long long)(0.0039 * (double)s * M * N);
-        if (rows == 128) cost += cost / 12;      // near-ties go to 64 rows (per-shape A/B, scripts/gemm_shapes_ab.py)
+        if (rows == 128) cost += cost / 12;      // near-ties go to 64 rows (per-shape A/B)
         if (best < 0 || cost < best) { best = cost; bm = rows; ks = (int)s; }
     }
 }
@@ -1904,8 +1904,7 @@ int tn_slices(int M, int N, int K) {
     // slices x tiles ~ three workgroups per CU for the short contractions (deep Swin stages, UNETR's 1 728 token rows); with
     // the register prefetch of the k-loop a long contraction (>= 32 768 rows) runs better on half as many, longer slices
     // (less partial traffic): SwinUnet 28.9 -> 28.5 ms per step, UNETR keeps 43.5 (44.5 with 384 everywhere)
-    static const int forced = knob(getenv("MIS_GEMM_TN_SLOTS"), 0);
-    const int slots = forced ? forced : (K >= 32768 ? 384 : 768);
+    const int slots = K >= 32768 ? 384 : 768;
     long long ks = slots / tiles;
     const long long kmax = mis_cdiv(K, 4 * BK);   // at least 4 k-steps per slice
     if (ks > kmax) ks = kmax;
@@ -1916,8 +1915,7 @@ int tn_slices(int M, int N, int K) {
 
 // the register-only TN form serves this shape (widths multiples of 96, 8-byte aligned float2 rows, 32-bit operand offsets)
 bool tn_reg_ok(const float* A, long long lda, const float* B, long long ldb, const float* C, long long ldc, int M, int N, int K) {
-    static const bool on = knob(getenv("MIS_GEMM_TN_REG"), 1) != 0;
-    return on && M % RT == 0 && N % RT == 0 && lda % 2 == 0 && ldb % 2 == 0 && ldc % 2 == 0 &&
+    return M % RT == 0 && N % RT == 0 && lda % 2 == 0 && ldb % 2 == 0 && ldc % 2 == 0 &&
            !((uintptr_t)A & 7) && !((uintptr_t)B & 7) && !((uintptr_t)C & 7) && K >= 64 &&
            (long long)K * lda * 4 < (1LL << 31) && (long long)K * ldb * 4 < (1LL << 31);
 }
@@ -1932,22 +1930,15 @@ int tn_reg_slices(int M, int N, int K) {
 }
 
 // Tile shape and k slices of the pre-split form, from per-shape sweeps of the SwinUnet Linears at 16, 24, 32 (256 x 256) and 48
-// images (scripts/gemm_nt_bench.py --split --batch B with MIS_GEMM_B3_RULE=0 MIS_GEMM_BM / MIS_GEMM_B3_BN; 20 shapes each).
-// K <= 96 stays with the short-contraction kernel: a 64-row tile re-fetches its B panel for three k-steps of work and the
+// images (scripts/gemm_nt_bench.py --split --batch B, with the tile forced by then-switches; 20 shapes each).
+// K <= B3_KMAX_SHORT = 96 stays with the short-contraction kernel: a 64-row tile re-fetches its B panel for three k-steps of work and the
 // planes are 1.5x the bytes (118 -> 133 us at 150528 x 384 x 96).  Otherwise 64 x 96 tiles (52 KB of LDS: three workgroups
 // per CU; best or within noise of the best for 60 of the 68 shapes), except wide N with many tiles (N >= 1536 a multiple of
 // 128, >= 1000 tiles of 64 x 96): 128 x 128, which halves the B-panel traffic per output and the re-reads of A (2352 x 3072
 // x 768: 79 -> 63 us; 9408 x 1536 x 384: 74 -> 69).  Sums of the 20 shapes, fp32-B kernels -> this rule: 48 images 1432 ->
-// 1307 us, 32: 1352 -> 1184, 24: 897 -> 832, 16: 708 -> 653.  MIS_GEMM_B3_RULE=0: the tile choice of the fp32-B path.
+// 1307 us, 32: 1352 -> 1184, 24: 897 -> 832, 16: 708 -> 653.
 bool b3_choice(int M, int N, int K, int& bm, int& bn, int& ks) {
-    static const bool rule = knob(getenv("MIS_GEMM_B3_RULE"), 1) != 0;
-    static const int kmin = knob(getenv("MIS_GEMM_B3_KMIN"), 97);
-    if (K < kmin) return false;
-    if (!rule) {
-        bn = nt_tile_n_b3(N);
-        nt_rule(M, N, K, bm, ks);
-        return true;
-    }
+    if (K <= B3_KMAX_SHORT) return false;
     const bool wide = N % 128 == 0 && N >= 1536 && mis_cdiv(M, 64) * mis_cdiv(N, 96) >= 1000;
     bn = wide ? 128 : (N % 96 == 0 ? 96 : nt_tile_n(N));
     nt_choice(M, N, K, bm, ks, wide ? 128 : 64, bn);
@@ -1956,32 +1947,21 @@ bool b3_choice(int M, int N, int K, int& bm, int& bn, int& ks) {
 
 // the short-contraction kernel serves: float4 epilogue, no split-K, no pixel-shuffle store, K <= 192, many tiles
 bool nt_short(const GemmArgs& a) {
-    static const int force = knob(getenv("MIS_GEMM_SHORT"), -1);
-    if (force == 0 || a.KS > 1 || !a.vec4 || a.ex_P || a.K % 4 || a.K3) return false;
+    if (a.KS > 1 || !a.vec4 || a.ex_P || a.K % 4 || a.K3) return false;
     // bf16x3: the K = 32 products of the general kernel win from K = 192 on (72 vs 75 us at 37632 x 576 x 192); at K = 96 the
     // short kernel's residency still pays (150528 x 384 x 96: 120 vs 132 us, x 288: 93 vs 92, scripts/gemm_nt_bench.py)
-    if (gemm_bf3() && force != 1 && a.K > 96) return false;
-    if (force == 1) return true;
+    if (gemm_bf3() && a.K > 96) return false;
     return a.K <= 192 && mis_cdiv(a.M, 64) * mis_cdiv(a.N, nt_tile_n(a.N)) >= 1536;
 }
 
 // the register-A kernel serves: bf16x3 products, pre-split B in the natural element order, N a multiple of 96, the float4
-// epilogue, no split-K, no pixel-shuffle store, enough 128-row tiles for three workgroups per CU (MIS_GEMM_REGA=0: never)
+// epilogue, no split-K, no pixel-shuffle store, enough 128-row tiles for three workgroups per CU.  The split-precision mask is
+// the only mutable input: a plan made and a launch issued under the same mask agree
 bool nt_rega_shape(int M, int N, int K) {
-    static const int on = knob(getenv("MIS_GEMM_REGA"), 1);
-    static const int kmin = knob(getenv("MIS_GEMM_REGA_KMIN"), 96);
-    static const int tmin = knob(getenv("MIS_GEMM_REGA_TILES"), 512);
-    static const int mmin = knob(getenv("MIS_GEMM_REGA_MMIN"), 30000);
-    if (!on || !gemm_bf3() || N % 96 || N % 4 || K % 4 || K < kmin) return false;
+    if (!gemm_bf3() || N % 96 || N % 4 || K % 4 || K < REGA_KMIN) return false;
     if ((long long)M * 4 >= (1LL << 31)) return false;
-    // per-shape sweep at 48 images (scripts/gemm_nt_bench.py --rega, profiles/r06_gemm_nt_rega.txt): ahead of the staged kernels
-    // for the 10^5-row stage and, at 4 x 10^4 rows, where the output is wider than the contraction; behind them below that
-    static const int msq = knob(getenv("MIS_GEMM_REGA_MSQ"), 100000);
-    // N == 96 (proj / fc2 of a 96-channel block): the register-A kernels carry the residual add AND the next LayerNorm in their
-    // epilogue (mis_gemm_nt_residual_ln) -- a LayerNorm pass less outweighs the few us the staged kernel is ahead by at 7 x 10^4 rows
-    static const int n96 = knob(getenv("MIS_GEMM_REGA_N96"), 1);
-    if (M < mmin || (M < msq && N <= K && !(n96 && N == 96))) return false;
-    return mis_cdiv(M, 128) * (N / 96) >= tmin;
+    if (M < REGA_MMIN || (M < REGA_MSQ && N <= K && N != 96)) return false;
+    return mis_cdiv(M, 128) * (N / 96) >= REGA_TILES;
 }
 
 // (Round 4 also tried the register-only form for the NT GEMMs -- forward and dX: lanes load float4 A[m0 + 16 t + i][k0 + 4 kk ..]
@@ -1992,7 +1972,7 @@ bool nt_rega_shape(int M, int N, int K) {
 // works because ITS operands are contraction-major and a lane group reads 128 contiguous bytes.  The NT GEMMs need the transpose
 // that the LDS stage provides.  Removed; scripts/gemm_nt_bench.py is the measurement.)
 
-// ---- instantiations: runtime (family, BM, BN, EP, PREC, waves) -> compiled kernel, once per family
+// ---- instantiations: runtime (family, BM, BN, EP, PREC) -> compiled kernel, once per family
 using LaunchFn = int (*)(unsigned grid, const GemmArgs& a, hipStream_t stream);
 struct Inst { LaunchFn launch = nullptr; int block = 0, lds = 0; };      // launch == nullptr: no such kernel is compiled
 
@@ -2018,33 +1998,21 @@ enum { F_NT, F_NT_SHORT, F_NT_REGA, F_NT_REGA_RES, F_TN, F_TN_REG };
 
 struct Plan {
     int status = MIS_OK;
-    int family = F_NT, bm = 0, bn = 0, ep = EP_NONE, prec = 0, waves = 4;      // the instantiation ...
+    int family = F_NT, bm = 0, bn = 0, ep = EP_NONE, prec = 0;      // the instantiation ...
     Inst k;                                                                    // ... its launcher, block and LDS bytes
     unsigned grid = 0, reduce_blocks = 0;      // reduce_blocks > 0: gemm_reduce_kernel follows
     int slices = 1;      // k slices a workspace must hold (KS, kchunk and the tile counts are in the GemmArgs)
 };
 
-template <int BMT, int BN, int EP, int PREC, int NW>
-Inst nt_k() { return inst<&gemm_nt_kernel<BMT, BN, EP, PREC, NW>, NW * 64, NtCfg<BMT, BN, PREC, NW>::LDS_BYTES>(); }
-
-// MIS_GEMM_NT_WAVES=8: eight waves per workgroup for the 64 x 96 tiles of the pre-split form.  Measured (profiles/r06_gemm_nt_waves.txt):
-// alone, most shapes gain 3 .. 10 % (six waves per SIMD hide the k-step's DMA wait and barrier), the split-K shapes lose 4 .. 11 %,
-// 1305 -> 1293 us over the 20 shapes of a step; INSIDE the step, where the weight-gradient and teacher streams already fill the idle
-// issue slots, it is 0.1 .. 0.15 ms SLOWER (SwinUnet 18.69 -> 18.80 ms, cross teaching 18.95 -> 19.12).  Default: four.
-int nt_waves(const Plan& p) {
-    static const int w = knob(getenv("MIS_GEMM_NT_WAVES"), 4);
-    return (w == 8 && p.bm == 64 && p.bn == 96 && p.prec == 2 && p.ep != EP_LNHEAD) ? 8 : 4;
-}
+constexpr int NT_WAVES = 4;      // waves per workgroup of every NT instantiation (eight lost inside the step: DESIGN.md)
+template <int BMT, int BN, int EP, int PREC>
+Inst nt_k() { return inst<&gemm_nt_kernel<BMT, BN, EP, PREC, NT_WAVES>, NT_WAVES * 64, NtCfg<BMT, BN, PREC, NT_WAVES>::LDS_BYTES>(); }
 
 template <int BMT, int BN>
 Inst nt_inst(const Plan& p) {
     return for_ep<EP_NONE, EP_GELU_FWD, EP_GELU_BWD, EP_RESIDUAL>(p.ep, [&](auto e) {
         constexpr int EP = decltype(e)::value;
-        if (p.waves == 8) {
-            if constexpr (BMT == 64 && BN == 96) return p.prec == 2 ? nt_k<BMT, BN, EP, 2, 8>() : Inst{};
-            return Inst{};
-        }
-        return p.prec == 2 ? nt_k<BMT, BN, EP, 2, 4>() : p.prec == 1 ? nt_k<BMT, BN, EP, 1, 4>() : nt_k<BMT, BN, EP, 0, 4>();
+        return p.prec == 2 ? nt_k<BMT, BN, EP, 2>() : p.prec == 1 ? nt_k<BMT, BN, EP, 1>() : nt_k<BMT, BN, EP, 0>();
     });
 }
 
@@ -2063,8 +2031,8 @@ Inst instantiation(const Plan& p) {
     switch (p.family) {
     case F_NT:
         if (p.ep == EP_LNHEAD) {      // the fused tail of FinalPatchExpand_X4: 64 x 96 tiles on fp32 B, four waves
-            if (p.bm != 64 || p.bn != 96 || p.prec > 1 || p.waves != 4) return {};
-            return p.prec ? nt_k<64, 96, EP_LNHEAD, 1, 4>() : nt_k<64, 96, EP_LNHEAD, 0, 4>();
+            if (p.bm != 64 || p.bn != 96 || p.prec > 1) return {};
+            return p.prec ? nt_k<64, 96, EP_LNHEAD, 1>() : nt_k<64, 96, EP_LNHEAD, 0>();
         }
         if (p.bn != 96 && p.bn != 128) return {};
         if (p.bm == 64) return p.bn == 96 ? nt_inst<64, 96>(p) : nt_inst<64, 128>(p);
@@ -2140,7 +2108,6 @@ Plan plan_nt(GemmArgs& a) {
         p.status = fill_grid(a, mis_cdiv(a.N, p.bn), mis_cdiv(a.M, 64), 1);
     } else {
         p.ep = a.KS > 1 ? EP_NONE : a.ep;      // split-K slices write raw partials (the epilogue runs in gemm_reduce_kernel)
-        p.waves = nt_waves(p);
         p.status = fill_grid(a, mis_cdiv(a.N, p.bn), mis_cdiv(a.M, p.bm), a.KS);
     }
     return finish(p, a, a.n_blocks_padded);
@@ -2152,8 +2119,7 @@ Plan plan_nt_rega(GemmArgs& a) {
     p.bm = 128; p.bn = 96; p.ep = a.ep; p.prec = 2;
     if (!nt_rega_shape(a.M, a.N, a.K) || (a.ex_P && a.ep != EP_LNHEAD) || !a.vec4) { p.status = MIS_ERR_UNSUPPORTED; return p; }
     a.KS = 1; a.kchunk = a.K;
-    static const int res_on = knob(getenv("MIS_GEMM_REGA_RES"), 1);
-    if (res_on && a.K3 <= 96) {
+    if (a.K3 <= 96) {
         // persistent: two workgroups per CU, split evenly over the column panels; a walker's four waves want >= 2 slabs each
         p.family = F_NT_REGA_RES;
         const long long tiles_n = a.N / 96, slabs = mis_cdiv(a.M, 32);
@@ -2165,9 +2131,9 @@ Plan plan_nt_rega(GemmArgs& a) {
     }
     p.family = F_NT_REGA;
     p.status = fill_grid(a, a.N / 96, mis_cdiv(a.M, 128), 1);
-    // persistent above three workgroups per CU (KS carries the grid size; MIS_GEMM_REGA_WALK=0: one workgroup per tile)
-    static const int walk = knob(getenv("MIS_GEMM_REGA_WALK"), 768);
-    a.KS = (walk > 0 && a.n_blocks_padded > (unsigned)walk) ? walk / MIS_NUM_XCD * MIS_NUM_XCD : (int)a.n_blocks_padded;
+    // persistent above three workgroups per CU (KS carries the grid size)
+    static_assert(REGA_WALK % MIS_NUM_XCD == 0, "whole rounds over the XCDs");
+    a.KS = a.n_blocks_padded > (unsigned)REGA_WALK ? REGA_WALK : (int)a.n_blocks_padded;
     return finish(p, a, (unsigned)a.KS);
 }
 
@@ -2215,7 +2181,7 @@ int run_nt(GemmArgs& a, const float* workspace, long long workspace_bytes, hipSt
 int plan_name(const Plan& p, char* name, int name_len) {
     if (p.status) return p.status;
     switch (p.family) {
-    case F_NT: snprintf(name, name_len, "gemm_nt_kernel<%d, %d, %d, %d, %d>", p.bm, p.bn, p.ep, p.prec, p.waves); break;
+    case F_NT: snprintf(name, name_len, "gemm_nt_kernel<%d, %d, %d, %d, %d>", p.bm, p.bn, p.ep, p.prec, NT_WAVES); break;
     case F_NT_SHORT: snprintf(name, name_len, "gemm_nt_short_kernel<%d, %d, %d>", p.bn, p.ep, p.prec); break;
     case F_NT_REGA: snprintf(name, name_len, "gemm_nt_rega_kernel<%d, %d>", p.bn, p.ep); break;
     case F_NT_REGA_RES: snprintf(name, name_len, "gemm_nt_rega_res_kernel<%d>", p.ep); break;

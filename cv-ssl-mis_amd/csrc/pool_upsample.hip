@@ -591,7 +591,7 @@ __global__ __launch_bounds__(256) void upsample_tri2_bwd_kernel(const UpBwdArgs 
 // dy[4j .. 4j+3] plus the two neighbours dy[4j-1], dy[4j+4].
 //   dx[i] = 0.25 dy[2i-1] + 0.75 dy[2i] + 0.75 dy[2i+1] + 0.25 dy[2i+2]   with dy[-1] := dy[0], dy[2n] := dy[2n-1]
 // along each axis (separable).  Gather form, fixed order: deterministic.
-template <int ZPT>       // z cells per thread (2: 4 x 8 x 32 tile, 47.5 KB of LDS; 1: 2 x 8 x 32 tile, 28.5 KB)
+template <int ZPT>       // z cells per thread (2, the one form compiled: 4 x 8 x 32 tile, 47.5 KB of LDS)
 struct Tri2 {
     static constexpr int TZ = 2 * ZPT, TY = 8, TX = 32;
     static constexpr int RZ = 2 * TZ + 2, RY = 2 * TY + 2, RQ = (2 * TX + 8) / 4, PITCH = RQ * 4;   // 10 x 18 x 72
@@ -828,16 +828,12 @@ extern "C" int mis_upsample2_fwd(const float* x, long long x_bs, float* y, long 
     if ((y_bs & 1) || ((uintptr_t)y & 7)) return MIS_ERR_UNSUPPORTED;   // float2 stores (Wo = 2W is even)
     if (!grid_ok(a.Do, (long long)N * C)) return MIS_ERR_UNSUPPORTED;
     // z-marching form, 4 input planes per thread (measured 300 -> 237 us at 48^3 -> 96^3 x 32 channels x 8; 8 planes per
-    // thread and an x-pair per thread with float4 stores are slower: 242 / 276 us); MIS_TRI2_FWD_Z=0: the one-cell kernel
-    static const int zmarch = getenv("MIS_TRI2_FWD_Z") ? atoi(getenv("MIS_TRI2_FWD_Z")) : 4;
-    static const int bi2_lds = getenv("MIS_BI2_FWD_LDS") ? atoi(getenv("MIS_BI2_FWD_LDS")) : 1;
-    if (!a.align && D > 1 && So < (1LL << 31) && zmarch >= 8 && D >= 8 && (long long)H * W * N * C >= 256 * 512)
-        hipLaunchKernelGGL(upsample_tri2_fwd_z_kernel<8>, dim3((H * W + 255) / 256, (D + 7) / 8, N * C), dim3(256), 0, stream, a);
-    else if (!a.align && D > 1 && So < (1LL << 31) && zmarch >= 4 && D >= 4 && (long long)H * W * N * C >= 256 * 256)
+    // thread and an x-pair per thread with float4 stores are slower: 242 / 276 us); small volumes: the one-cell kernel
+    if (!a.align && D > 1 && So < (1LL << 31) && D >= 4 && (long long)H * W * N * C >= 256 * 256)
         hipLaunchKernelGGL(upsample_tri2_fwd_z_kernel<4>, dim3((H * W + 255) / 256, (D + 3) / 4, N * C), dim3(256), 0, stream, a);
     else if (!a.align && D > 1 && So < (1LL << 31))
         hipLaunchKernelGGL(upsample_tri2_fwd_kernel, dim3((H * W + 255) / 256, D, N * C), dim3(256), 0, stream, a);
-    else if (a.align && D == 1 && a.Wo % 4 == 0 && H > 1 && W > 1 && !(y_bs & 3) && !((uintptr_t)y & 15) && bi2_lds &&
+    else if (a.align && D == 1 && a.Wo % 4 == 0 && H > 1 && W > 1 && !(y_bs & 3) && !((uintptr_t)y & 15) &&
              (long long)N * C <= 65535)
         hipLaunchKernelGGL(upsample_bi2_fwd_lds_kernel, dim3((a.Wo + BF_TX - 1) / BF_TX, (a.Ho + BF_TY - 1) / BF_TY, N * C),
                            dim3(256), 0, stream, a);
@@ -867,18 +863,14 @@ extern "C" int mis_upsample2_bwd(const float* dy, long long dy_bs, float* dx, lo
     } else if (D > 1 && So < (1LL << 31) && W % 2 == 0 && W >= 4 && !(dy_bs & 3) && !((uintptr_t)dy & 15) &&
                !(dx_bs & 1) && !((uintptr_t)dx & 7)) {
         // float4-aligned dy rows (Wo = 2W is a multiple of 4, So a multiple of 8) and float2-aligned dx rows
-        static const int zpt = getenv("MIS_TRI2_ZPT") ? atoi(getenv("MIS_TRI2_ZPT")) : 2;
+        constexpr int ZPT = 2;
         const int tiles_x = (int)mis_cdiv(W, 32), tiles_y = (int)mis_cdiv(H, 8);
-        const int tiles_z = (int)mis_cdiv(D, 2 * zpt);
+        const int tiles_z = (int)mis_cdiv(D, 2 * ZPT);
         const long long nb = (long long)tiles_x * tiles_y * tiles_z * N * C;
         if (nb > 0x7fffffffLL) return MIS_ERR_UNSUPPORTED;
         const unsigned nbp = (unsigned)(mis_cdiv(nb, MIS_NUM_XCD) * MIS_NUM_XCD);
-        if (zpt == 1)
-            hipLaunchKernelGGL(upsample_tri2_bwd_lds_kernel<1>, dim3(nbp), dim3(256), Tri2<1>::LDS_FLOATS * 4, stream, a,
-                               tiles_x, tiles_y, tiles_z, (unsigned)nb, nbp);
-        else
-            hipLaunchKernelGGL(upsample_tri2_bwd_lds_kernel<2>, dim3(nbp), dim3(256), Tri2<2>::LDS_FLOATS * 4, stream, a,
-                               tiles_x, tiles_y, tiles_z, (unsigned)nb, nbp);
+        hipLaunchKernelGGL(upsample_tri2_bwd_lds_kernel<ZPT>, dim3(nbp), dim3(256), Tri2<ZPT>::LDS_FLOATS * 4, stream, a,
+                           tiles_x, tiles_y, tiles_z, (unsigned)nb, nbp);
     } else if (D > 1 && So < (1LL << 31)) {
         constexpr int ZR = 4;
         hipLaunchKernelGGL(upsample_tri2_bwd_kernel<ZR>, dim3((H * ((W + 1) / 2) + 255) / 256, (D + ZR - 1) / ZR, N * C),

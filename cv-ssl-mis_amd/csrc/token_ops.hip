@@ -1535,8 +1535,7 @@ extern "C" int mis_ln_head_fwd(const float* x, long long ldx, const float* gamma
     if (!x || !gamma || !beta || !w || !mean || !rstd || !logits || B <= 0 || S <= 0 || C <= 0) return MIS_ERR_ARG;
     if (C % 4 || C > 128 || ldx % 4 || !a16(x) || !a16(gamma) || !a16(beta) || !a16(w)) return MIS_ERR_UNSUPPORTED;
     const long long M = (long long)B * S;
-    static const bool l8 = !(getenv("MIS_LN96_LANES8") && getenv("MIS_LN96_LANES8")[0] == '0');
-    if (C == 96 && l8 && NC >= 2 && NC <= 4) {
+    if (C == 96 && NC >= 2 && NC <= 4) {
         long long blocks8 = mis_cdiv(M, 64);
         if (blocks8 > 8192) blocks8 = 8192;
 #define MIS_LNH_F8(N_) hipLaunchKernelGGL(ln96_head_fwd_kernel<N_>, dim3((unsigned)blocks8), dim3(256), 0, stream, x, ldx, gamma, \
@@ -1608,12 +1607,11 @@ static int ln_head_bwd_impl(const float* x, long long ldx, const float* gamma, c
     const int slabs = (int)mis_cdiv(M, COL_SLAB_ROWS);
     float2* pln = reinterpret_cast<float2*>(workspace);
     float* pw = reinterpret_cast<float*>(pln + (long long)slabs * C);
-    static const bool l8 = !(getenv("MIS_LN96_LANES8") && getenv("MIS_LN96_LANES8")[0] == '0');
 #define MIS_LNH_B8(N_) hipLaunchKernelGGL(ln96_head_bwd_kernel<N_>, dim3(slabs), dim3(256), 0, stream, x, ldx, gamma, beta, w, mean, \
                                           rstd, dlogits, dl_bs, dx, lddx, accumulate_dx, M, S, (long long)COL_SLAB_ROWS, pln, pw, ex_P, ex_H, ex_W)
 #define MIS_LNH_B(N_) hipLaunchKernelGGL(ln_head_bwd_kernel<N_>, dim3(slabs), dim3(256), 0, stream, x, ldx, gamma, beta, w, mean, \
                                          rstd, dlogits, dl_bs, dx, lddx, accumulate_dx, M, S, C, (long long)COL_SLAB_ROWS, pln, pw, ex_P, ex_H, ex_W)
-    if (C == 96 && l8) {
+    if (C == 96) {
         switch (NC) {
             case 2: MIS_LNH_B8(2); break;
             case 3: MIS_LNH_B8(3); break;

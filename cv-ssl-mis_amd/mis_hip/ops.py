@@ -171,11 +171,11 @@ def space_to_depth2d(src, dst, fine_shape, to_depth, bias=None, accumulate=False
 
 def conv_k2s2_eligible(cin, cout, coarse, up):
     """(cin, cout) and the COARSE (Do, Ho, Wo) the in-place kernel-2 / stride-2 kernels serve (conv_k2s2.hip)."""
-    return K2S2 and bool(_l.query("mis_conv_k2s2_eligible", int(cin), int(cout), *[int(v) for v in coarse], int(up)))
+    return bool(_l.query("mis_conv_k2s2_eligible", int(cin), int(cout), *[int(v) for v in coarse], int(up)))
 
 
 def conv_k2s2_wgrad_eligible(cf, cc, coarse):
-    return K2S2 and bool(_l.query("mis_conv_k2s2_wgrad_eligible", int(cf), int(cc), *[int(v) for v in coarse]))
+    return bool(_l.query("mis_conv_k2s2_wgrad_eligible", int(cf), int(cc), *[int(v) for v in coarse]))
 
 
 # When set to a set(), the ops below add a short tag of the path they dispatched (tests assert that the full-batch
@@ -241,7 +241,6 @@ def _ksize(k):
     return tuple(k)
 
 
-K2S2 = _os.environ.get("MIS_K2S2", "1") != "0"      # kernel-2 / stride-2 (de)convolutions in place (conv_k2s2.hip)
 WINO = int(_os.environ.get("MIS_WINO", "3"))      # bit 0: Winograd form of the 3x3x3 convolutions, bit 1: of the 3x3 ones
 # diagnostics (numerics studies, tests/test_parity_gpu.py): the 3-D forward / data gradient resp. weight gradient alone on the
 # direct kernels, and the smallest volume edge W the 3-D Winograd kernels are used for
@@ -254,15 +253,12 @@ WINO2D = 10       # ids >= WINO2D: variant id - WINO2D of the 2-D kernels (conv_
 
 
 # 1x1x1 convolutions of small volumes with many channels (the space-to-depth form of V-Net's deep kernel-2 / stride-2 layers):
-# batched GEMM instead of the spatially tiled direct kernel (conv1x1_gemm.hip).  MIS_CONV1X1_GEMM=0 switches it off
-CONV1X1_GEMM = _os.environ.get("MIS_CONV1X1_GEMM", "1") != "0"
-CONV1X1_GEMM_MAX_S = int(_os.environ.get("MIS_CONV1X1_GEMM_MAX_S", "4096"))
+# batched GEMM instead of the spatially tiled direct kernel (conv1x1_gemm.hip), up to this many voxels
+CONV1X1_GEMM_MAX_S = 4096
 
 
 def conv1x1_gemm_eligible(x, y, cin, cout):
     """x / y: 5-D NCDHW views with dense (C, D, H, W); few voxels, many channels, sizes the GEMM's float4 rows need."""
-    if not CONV1X1_GEMM:
-        return False
     try:
         _, _, _, _, _, S, xbs = _geom(x)
         _, _, _, _, _, _, ybs = _geom(y)
@@ -284,8 +280,6 @@ def conv1x1_gemm(x, wt, bias, y, accumulate=False):
 
 def conv1x1_wgrad_eligible(a, b):
     """a / b: the two 5-D NCDHW operands of the weight gradient (same N, D, H, W)."""
-    if not CONV1X1_GEMM:
-        return False
     try:
         _, _, _, _, _, S, abs_ = _geom(a)
         _, _, _, _, _, _, bbs = _geom(b)

@@ -29,9 +29,6 @@ from .dist import param_progress
 
 _net_ids = itertools.count(1)
 
-# conv -> norm pairs: the conv epilogue emits the statistics (mis_conv_fwd_stats); MIS_FUSE_STATS=0 keeps the
-# separate statistics pass (A/B timing)
-FUSE_CONV_STATS = os.environ.get("MIS_FUSE_STATS", "1") != "0"
 # norm + act + dropout + 1x1x1 classifier of the 3-D nets as one pass over the last conv's output (norm_act.hip, mis_norm_head_*)
 FUSE_HEAD = os.environ.get("MIS_FUSE_HEAD", "1") != "0"
 # first layer (1 -> 16 channels, its input needs no gradient): the normalisation's backward apply pass on the load path of
@@ -47,12 +44,6 @@ HEAD_DROP_BITS = os.environ.get("MIS_HEAD_DROP_BITS", "1") != "0"
 # weight gradients on a side stream: dW of a layer needs only (x, dy) and nothing of the backward needs dW, so it runs
 # beside the data gradient / normalisation backward of the layers below and fills the CUs their launch tails leave idle
 WGRAD_STREAM = os.environ.get("MIS_WGRAD_STREAM", "1") != "0"
-# first stage of the InstanceNorm + ReLU backward (sum dz, sum dz * x) in the epilogue of the Winograd data-gradient launch
-# that produces the gradient at the activation (mis_conv3d_wino_dgrad_norm): the partial-sum pass over da and x is not run
-FUSE_DGRAD_NORM = os.environ.get("MIS_FUSE_DGRAD_NORM", "1") != "0"
-PROGRESS_SYNC_MAIN = os.environ.get("MIS_PROGRESS_SYNC_MAIN", "0") == "1"
-# residual blocks (UNETR / SwinUNETR): normalise + add the shortcut + activate in one pass, forward and backward
-NORM_RES = os.environ.get("MIS_NORM_RES", "1") != "0"
 
 
 class Buf:
@@ -796,7 +787,7 @@ class PlanBase:
         side = None
         if WGRAD_STREAM and not getattr(self.net, "frozen", False):
             if self._wgrad_stream is None:
-                self._wgrad_stream = _lib.side_stream("wgrad")
+                self._wgrad_stream = torch.cuda.Stream()      # the default priority, like the main stream
             side = self._wgrad_stream
         ctx.wgrad_stream = side
         ctx.deferred = [] if side is not None else None      # see defer(): finishing launches queued for the side stream
@@ -854,7 +845,7 @@ class Plan(PlanBase):
         op.frozen = bool(getattr(self.net, "frozen", False))
         # conv -> norm: let the conv epilogue produce the statistics (no separate pass over the conv output)
         prev = self.ops[-1] if self.ops else None
-        if FUSE_CONV_STATS and not no_norm and type(prev) is ConvOp and prev.y is x and prev.dilation == 1:
+        if not no_norm and type(prev) is ConvOp and prev.y is x and prev.dilation == 1:
             N, C, D, H, W = x.shape
             T = ops.conv_stat_tiles(N, prev.cin, prev.cout, D, H, W, prev.ksize, wino=prev.wino_f)
             if T > 0:
@@ -875,7 +866,7 @@ class Plan(PlanBase):
     @staticmethod
     def can_norm_res_act(x):
         """Geometry the one-pass form serves (the float4 kernels): voxel count a multiple of 4."""
-        return NORM_RES and (x.shape[2] * x.shape[3] * x.shape[4]) % 4 == 0
+        return (x.shape[2] * x.shape[3] * x.shape[4]) % 4 == 0
 
     def norm_res_act(self, x, res, y, per_sample, gamma=None, beta=None, running=None, slope=0.0):
         """y = act(norm(x) + res): the tail of a residual block in one pass (ops.norm_res_act_fwd); no dropout."""
@@ -902,7 +893,7 @@ class Plan(PlanBase):
         ``fuse``: the caller guarantees that ``a`` -- the output of the norm/activation op just appended --
         has no other reader; that op then writes act(norm(x)) + b itself (one pass, forward and backward) and ``a`` is returned."""
         prev = self.ops[-1] if self.ops else None
-        if (fuse and NORM_RES and type(prev) is NormActOp and prev.y is a and a.parent is None and prev.res is None
+        if (fuse and type(prev) is NormActOp and prev.y is a and a.parent is None and prev.res is None
                 and prev.pool is None and prev.sums is None and not prev.no_norm and prev.drop_p == 0.0 and prev.cg == 1
                 and not (prev.per_sample and (prev.gamma is not None or prev.beta is not None))
                 and self.can_norm_res_act(a)):
@@ -978,9 +969,9 @@ class Plan(PlanBase):
     def _fuse_dgrad_norm(self):
         """conv_a -> InstanceNorm -> ReLU -> conv_b (reference UnetConv3, utils.py:99-123): when the activation between
         the two convolutions has no other reader, conv_b's Winograd data gradient also forms the partial sums of the
-        normalisation's backward (ops.conv_dgrad_norm)."""
-        if not FUSE_DGRAD_NORM:
-            return
+        normalisation's backward (ops.conv_dgrad_norm): the first stage of the InstanceNorm + ReLU backward (sum dz,
+        sum dz * x) in the epilogue of the launch that produces the gradient at the activation
+        (mis_conv3d_wino_dgrad_norm); the partial-sum pass over da and x is not run."""
         for conv in self.ops:
             if type(conv) is not ConvOp or not conv.need_dx or conv.wino_b not in (0, 1) or conv.ksize != (3, 3, 3):
                 continue
@@ -1143,16 +1134,8 @@ def progress_reporter(on_progress, main, side, before=None):
     ``before()`` runs ahead of every callback that IS made (the plans finish their queued parameter-gradient sums there: a
     range that is not reported yet may keep its finishing launches queued, so they batch up between two buckets)."""
     probe = getattr(getattr(on_progress, "__self__", None), "would_issue", None)
-    if PROGRESS_SYNC_MAIN:          # A/B switch (scripts/ddp_overhead.py): the compute stream waits at every report
-        probe = None
 
     def report(lo):
-        if PROGRESS_SYNC_MAIN and side is not None:
-            if before is not None:
-                before()
-            _lib.wait_stream(main, side)
-            _lib.tape_call(on_progress, lo)
-            return
         if probe is not None and not probe(lo):
             return
         if before is not None:

@@ -182,7 +182,7 @@ class _Step(_TapedStep):
             return side_fn(), res
         main = torch.cuda.current_stream()
         if self._side is None:
-            self._side = _lib.side_stream("side")
+            self._side = torch.cuda.Stream()
         _lib.wait_stream(self._side, main)
         with torch.cuda.stream(self._side):
             side_res = side_fn()

@@ -19,9 +19,6 @@ from .plan import Act, PlanBase, TAct, defer, defer_final, run_deferred      # n
 
 # GEMM epilogue fusions (GELU into fc1 / fc2-dX, DropPath + residual add into proj / fc2); MIS_SWIN_FUSE=0 runs the
 # separate element-wise passes (A/B timing, and the reference point of the fusion tests)
-LN_HEAD = os.environ.get("MIS_LN_HEAD", "1") != "0"        # last LayerNorm + output head in one pass (LnHeadOp)
-UNSHUFFLE = os.environ.get("MIS_LN_HEAD_UNSHUFFLE", "1") != "0"   # ... whose backward stores dx through FinalPatchExpand_X4's inverse shuffle
-EXPAND_HEAD = os.environ.get("MIS_EXPAND_HEAD", "1") != "0"       # ... and its forward inside the expand GEMM's epilogue
 FUSE = int(os.environ.get("MIS_SWIN_FUSE", "7"))      # bit 0: GELU forward, bit 1: GELU backward, bit 2: residual
 
 
@@ -61,7 +58,7 @@ class LinearOp:
         if (FUSE & 4) and self.res is not None:
             r = self.res
             scales = r.prepare(ctx)
-            ln = r.ln_next if LN_EPILOGUE else None
+            ln = r.ln_next
             if ln is not None and tops.gemm_residual_ln(self.x.t, self._b3(ctx), r.out.t, r.a.t, ln.g.data, ln.b.data, ln.y.t,
                                                         ln.mean, ln.rstd, bias=bias, rowscale=scales, rows_per_scale=r.rps):
                 r.skip_fwd = True        # the residual add AND the LayerNorm that reads it ran in this GEMM's epilogue
@@ -128,8 +125,6 @@ class LinearOp:
 
 # LayerNorm backward + the backward of the residual add in front of it in one pass (MIS_SWIN_LNRES=0: two passes)
 LNRES = os.environ.get("MIS_SWIN_LNRES", "1") != "0"
-# 96-channel blocks: the LayerNorm that follows a residual add runs in the producing GEMM's epilogue (register-A kernels, round 6)
-LN_EPILOGUE = os.environ.get("MIS_LN_EPILOGUE", "1") != "0"
 
 
 def pair_ln_residual(ops_list):
@@ -161,7 +156,7 @@ def split_linear_weights(plan, transposed):
             # planes in the element order of the kernel that will read them: the register-A kernel (many token rows, float4
             # epilogue) wants the natural order; the pixel-shuffle / LayerNorm-head stores of the expand layers stay staged
             # (the final expand with LayerNorm + head in its epilogue has a register-A form: LnHeadOp.eligible shapes, K <= 96)
-            staged_only = isinstance(op, ExpandLinearOp) and not (EXPAND_HEAD and op.ln_head is not None and op.w2.shape[1] <= 96 and op.geo[3] == 96)
+            staged_only = isinstance(op, ExpandLinearOp) and not (op.ln_head is not None and op.w2.shape[1] <= 96 and op.geo[3] == 96)
             if transposed:
                 if op.need_dx and op.wT_batched:
                     op.bT3 = tops.SplitB(op.wT, rows=op.y.rows)
@@ -187,7 +182,7 @@ class LayerNormOp:
         self.res_bwd = None      # the ResidualOp right in front of this op whose output is x (pair_ln_residual)
 
     def fwd(self, ctx):
-        if self.skip_fwd:           # ran in the epilogue of the GEMM that produced x (LinearOp.fwd, LN_EPILOGUE)
+        if self.skip_fwd:           # ran in the epilogue of the GEMM that produced x (LinearOp.fwd)
             self.skip_fwd = False
             return
         tops.layernorm_fwd(self.x.t, self.y.t, self.g.data, self.b.data, self.mean, self.rstd)
@@ -365,7 +360,7 @@ class ExpandLinearOp(LinearOp):
 
     def fwd(self, ctx):
         B, H, W, c, P = self.geo
-        h = self.ln_head if EXPAND_HEAD else None
+        h = self.ln_head
         keep = None if ctx.no_backward else self.sh.t     # the shuffled tokens: only the backward reads them
         if h is not None and tops.gemm_expand_ln_head(self.x.t, self.w2, keep, B, H, W, P, c, h.g.data, h.b.data, h.w2,
                                                       h.mean, h.rstd, h.logits.t, b3=self._b3(ctx)):
@@ -441,7 +436,7 @@ class LnHeadOp:
 
     @staticmethod
     def eligible(C, num_classes):
-        return LN_HEAD and C % 4 == 0 and C <= 128 and 2 <= num_classes <= 4
+        return C % 4 == 0 and C <= 128 and 2 <= num_classes <= 4
 
     def fwd(self, ctx):
         if self.skip_fwd:         # the expand GEMM's epilogue did this op's forward (mis_gemm_expand_ln_head)
@@ -452,7 +447,7 @@ class LnHeadOp:
 
     def bwd(self, ctx):
         e = self.expand           # the ExpandLinearOp whose pixel-shuffled output is this op's input (set by the plan), or None
-        if UNSHUFFLE and e is not None and not self.x.written and not e.y.written:
+        if e is not None and not self.x.written and not e.y.written:
             # dx goes straight into the gradient of the expand Linear's (un-shuffled) output: no rearrange pass
             B, H, W, c, P = e.geo
             tops.ln_head_bwd(self.x.t, self.g.data, self.b.data, self.w2, self.mean, self.rstd, self.logits.grad(),

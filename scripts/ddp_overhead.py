@@ -2,7 +2,7 @@
 and the gradient bucketer active -- per-op progress reports, bucket all-reduces issued behind the weight-gradient side
 stream -- against the plain single-GPU step.  One GPU is enough: a world of 1 exercises the same stream choreography.
 
-    python scripts/ddp_overhead.py [workload ...]           (MIS_PROGRESS_SYNC_MAIN=1: the pre-round-3 reporting)"""
+    python scripts/ddp_overhead.py [workload ...]"""
 import os
 import sys
 import time

@@ -1,5 +1,5 @@
-"""dW GEMMs of SwinUnet (24 + 24 images of 224 x 224) through mis_gemm_dw: time per shape.  MIS_GEMM_TN_REG=0 selects the staged
-(LDS) kernel, default the register-only one (gemm.hip): run twice to compare."""
+"""dW GEMMs of SwinUnet (24 + 24 images of 224 x 224) through mis_gemm_dw: time per shape (the register-only
+kernel where it serves the shape, gemm.hip)."""
 import os
 import sys
 
@@ -37,4 +37,4 @@ for T, Cout, Cin in shapes:
     fl = 2.0 * T * Cout * Cin
     tot += t
     print(f"T={T:7d} {Cin:5d} -> {Cout:5d}: {t:8.1f} us  {fl / t / 1e6:6.1f} TF ({fl / t / 1e6 / 157.3:.3f})  rel err {err:.1e}", flush=True)
-print(f"sum {tot:.1f} us  [MIS_GEMM_TN_REG={os.environ.get('MIS_GEMM_TN_REG', '1')}]")
+print(f"sum {tot:.1f} us")
