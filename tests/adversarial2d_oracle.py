@@ -20,7 +20,8 @@ import torch
 import torch.nn.functional as F
 
 import conv_oracle as co
-from adversarial_oracle import K, MARGIN, UNDECIDED_CAP, SLOPE, act_drop, adam, decided, tail, undecided_share  # noqa: F401
+from oracle_kit import one_thread          # noqa: F401  (re-exported: the tests evaluate their fp32 forms under it)
+from adversarial_oracle import K, MARGIN, Check, print_report, UNDECIDED_CAP, SLOPE, act_drop, adam, decided, tail, undecided_share  # noqa: F401
 
 F64, F32 = torch.float64, torch.float32
 KINDS, MEASURES = co.KINDS, co.MEASURES
@@ -85,15 +86,6 @@ def conv_taps(x, w, b=None):
         for e in range(4):
             y = y + torch.einsum("oc,nchw->nohw", w[:, :, a, e], xp[:, :, a:a + H:2, e:e + W:2])
     return y if b is None else y + b.reshape(1, -1, 1, 1)
-
-
-def one_thread(fn):
-    threads = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return fn()
-    finally:
-        torch.set_num_threads(threads)
 
 
 def reference_torch(c, dtype, conv_fn=conv):

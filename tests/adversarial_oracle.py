@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 import conv_oracle as co
 import loss_tail_oracle as lto
+import oracle_kit as kit
 
 F64, F32 = torch.float64, torch.float32
 KINDS, MEASURES = co.KINDS, co.MEASURES
@@ -87,12 +88,7 @@ def reference64(c):
 
 
 def reference32(c):
-    threads = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return reference_torch(c, F32)
-    finally:
-        torch.set_num_threads(threads)
+    return kit.one_thread(reference_torch, c, F32)
 
 
 def plain64(c):
@@ -271,3 +267,38 @@ GOLDEN_LATTICE = 12     # the map gradient is stored at every 12th voxel per axi
 
 def lattice(t):
     return t[..., 5::GOLDEN_LATTICE, 5::GOLDEN_LATTICE, 5::GOLDEN_LATTICE]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the gate of the adversarial GPU tests (3-D kernels, 2-D kernels, the golden iteration)
+# ---------------------------------------------------------------------------------------------------------------------
+STATS = []        # every figure of the 3-D tests: (case, label, kind, measure, e32, hip)
+
+
+class Check:
+    """The gate on one tensor: got against ref64, e32 from the fp32 evaluation r32 of the same expression."""
+
+    def __init__(self, name, floor=FLOOR, stats=STATS, over_the_gate=None, width=14):
+        self.name, self.width = name, width
+        self.gate = kit.Gate(K, floor, over_the_gate, stats)
+
+    def __call__(self, label, kind, got, ref, r32, dim=1):
+        ref = ref.detach().double()
+        got, r32 = got.detach().cpu().double().reshape(ref.shape), r32.detach().double().reshape(ref.shape)
+        if ref.dim() < 2:
+            got, ref, r32, dim = got.reshape(1, -1), ref.reshape(1, -1), r32.reshape(1, -1), 0
+        e = co.measure(r32, ref, dim)
+        self.gate.tensor(self.name, label, kind, got, ref, lambda g, r: co.measure(g, r, dim), {ms: e[ms] for ms in co.MEASURES},
+                         (self.name,), width=self.width)
+
+    def done(self):
+        self.gate.done(self.name)
+
+
+def print_report(prefix, stats, floor, width=14):
+    """Worst ratio per (group, tensor, measure) of the rows a test file collected."""
+    for (group, label, m), r in kit.worst_rows(((cid.split(":")[0] if ":" in cid else "conv", label, m), cid, e32, ehip,
+                                                max(e32, floor[kind] / K)) for cid, label, kind, m, e32, ehip in stats):
+        print(f"\n[{prefix}] {group:8s} {label:{width}s} {m:3s} e32 {r['lo']:.1e} .. {r['hi']:.1e}  hip max {r['hip']:.2e}  "
+              f"worst hip/max(e32, floor/K) {r['ratio']:.2f} ({r['at']})", end="")
+    print()

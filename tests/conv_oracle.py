@@ -24,11 +24,12 @@ measure(got, ref64, dim) gives two figures per tensor: ``max`` = the largest |er
 rms(error) / rms(reference); plus ``zero_ok``: a channel whose reference is exactly zero is exactly zero in ``got``.
 """
 import functools
-import math
 import zlib
 
 import torch
 import torch.nn.functional as F
+
+from oracle_kit import ceil2, one_thread          # noqa: F401  (ceil2 re-exported: other files round their floors with it)
 
 F64, F32 = torch.float64, torch.float32
 KINDS = ("y", "dx", "dw")
@@ -91,12 +92,7 @@ def reference64(c):
 
 
 def reference32(c):
-    threads = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return reference_torch(c, F32)
-    finally:
-        torch.set_num_threads(threads)
+    return one_thread(reference_torch, c, F32)
 
 
 def _taps(k):
@@ -439,10 +435,3 @@ def yardstick(name, kind, m):
         v = max(v, ew[kind][m])
     return v
 
-
-def ceil2(v):
-    """v rounded up to two significant digits (how the FLOOR constants are written)."""
-    if v <= 0:
-        return 0.0
-    e = math.floor(math.log10(v)) - 1
-    return float(f"{math.ceil(v / 10 ** e - 1e-9) * 10 ** e:.1e}")

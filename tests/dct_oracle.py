@@ -13,6 +13,13 @@ import torch.nn.functional as F
 from oracle.losses import consistency_weight, dice_loss
 from oracle.step import lr_for_step
 
+# flag names of code/train_deep_co_training_2D_ViT.py; the triple-view script takes the same ones (tests/test_triple_cpu.py)
+REF_FLAGS_VIT = ["--root_path", "--exp", "--model", "--max_iterations", "--batch_size", "--deterministic", "--base_lr",
+                 "--patch_size", "--seed", "--num_classes", "--cfg", "--opts", "--zip", "--cache-mode", "--resume",
+                 "--accumulation-steps", "--use-checkpoint", "--amp-opt-level", "--tag", "--eval", "--throughput",
+                 "--labeled_bs", "--labeled_num", "--ema_decay", "--consistency_type", "--consistency",
+                 "--consistency_rampup"]
+
 
 def dct_step(net, student, momentum, volume, label, rot_k, iter_num, *, labeled_bs, num_classes, base_lr=0.01,
              max_iterations=30000, consistency=0.1, rampup=200.0, sgd_momentum=0.9, weight_decay=1e-4, drop=None,

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_oracle as co
+from oracle_kit import one_thread
 
 F64, F32 = torch.float64, torch.float32
 KINDS, MEASURES = co.KINDS, co.MEASURES
@@ -79,12 +80,7 @@ def reference64(c):
 
 
 def reference32(c):
-    threads = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return reference_torch(c, F32)
-    finally:
-        torch.set_num_threads(threads)
+    return one_thread(reference_torch, c, F32)
 
 
 def plain64(c):

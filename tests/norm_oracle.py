@@ -24,6 +24,9 @@ import zlib
 import torch
 import torch.nn.functional as F
 
+import oracle_kit as kit
+from oracle_kit import ceil2          # noqa: F401  (re-exported: other files round their floors with it)
+
 F64, F32 = torch.float64, torch.float32
 EPS = float(torch.tensor(1e-5, dtype=F32))       # the kernels receive eps as a float
 KINK_ULPS = 16.0
@@ -47,8 +50,7 @@ def rel(a, ref, each=False):
     """|a - ref|max / |ref|max, or with ``each`` the largest per-element relative error."""
     if each:
         return ((a.double() - ref).abs() / ref.abs()).max().item()
-    m = ref.abs().max().item()
-    return (a.double() - ref).abs().max().item() / m if m > 0 else 0.0
+    return kit.rel(a, ref)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -502,10 +504,14 @@ def references(name):
     return r64, r32, e32
 
 
-def ceil2(v):
-    """v rounded up to two significant digits (how the FLOOR constants are written)."""
-    import math
-    if v <= 0:
-        return 0.0
-    e = math.floor(math.log10(v)) - 1
-    return float(f"{math.ceil(v / 10 ** e - 1e-9) * 10 ** e:.1e}")
+# The ``stat`` rule of tests/test_norm_edges_gpu.py (its K and FLOOR["stat"], measured there): kept here because
+# tests/test_conv_edges_gpu.py holds the statistics of the split Winograd forward to the same rule.
+K = 6.0
+FLOOR_STAT = 1.2e-7
+
+
+def finalize_factor(mean64, var64):
+    """Conditioning of one-pass statistics from fp32 partials: the factor rstd and running_var get per group in
+    mis_norm_stats_finalize's tests (tests/test_norm_edges_gpu.py; tests/test_conv_edges_gpu.py holds the split Winograd
+    forward's to it too)."""
+    return 1.0 + mean64 ** 2 / (var64 + EPS)

@@ -62,22 +62,24 @@ max(e32, FLOOR / K): the error in units of fp32 noise, the gate is at 6.
     gate (OVER_THE_GATE is empty).  The highest ratios are data gradients onto few channels (ragged-20x12: 3 channels, the `map`
     form), where torch's own fp32 error is at 1e-7 and the floor decides.
 """
-import json
-import os
+import functools
 
 import pytest
 import torch
 
 import adversarial2d_oracle as ao
-import conv_oracle as co
-from test_norm_edges_gpu import NAN, _in, _Out
+import oracle_kit as kit
+from oracle_kit import NAN, nan as _nan
 
 pytestmark = pytest.mark.gpu
 
 K, FLOOR = ao.K, ao.FLOOR
 # A tensor over the gate is a finding, named here with its measured ratio; the gate itself stays where it is and the test fails.
 OVER_THE_GATE = {}
+LEAD, TRAIL = 1, 2            # channels of the wider buffer before / after a slice
+_in, _out = functools.partial(kit.place, lead=LEAD, trail=TRAIL), functools.partial(kit.Out, lead=LEAD, trail=TRAIL)
 STATS = []        # (case, label, kind, measure, e32, hip)
+_checker = functools.partial(ao.Check, floor=FLOOR, stats=STATS, over_the_gate=OVER_THE_GATE, width=22)
 F64 = torch.float64
 
 
@@ -89,57 +91,9 @@ def _ops():
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    if not STATS:
-        return
-    rows = {}
-    for cid, label, kind, m, e32, ehip in STATS:
-        group = cid.split(":")[0] if ":" in cid else "conv"
-        r = rows.setdefault((group, label, m), dict(lo=1e9, hi=0.0, ratio=0.0, hip=0.0, at=""))
-        r["lo"], r["hi"], r["hip"] = min(r["lo"], e32), max(r["hi"], e32), max(r["hip"], ehip)
-        ratio = ehip / max(e32, FLOOR[kind] / K)
-        if ratio > r["ratio"]:
-            r["ratio"], r["at"] = ratio, cid
-    for (group, label, m), r in sorted(rows.items()):
-        print(f"\n[adversarial2d] {group:8s} {label:22s} {m:3s} e32 {r['lo']:.1e} .. {r['hi']:.1e}  hip max {r['hip']:.2e}  "
-              f"worst hip/max(e32, floor/K) {r['ratio']:.2f} ({r['at']})", end="")
-    print()
-    path = os.environ.get("MIS_ADVERSARIAL2D_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"stats": STATS}, f)
-
-
-class _Check:
-    """The gate on one tensor: got against ref64, e32 from the fp32 evaluation r32 of the same expression."""
-
-    def __init__(self, name):
-        self.name, self.bad = name, []
-
-    def __call__(self, label, kind, got, ref, r32, dim=1):
-        ref = ref.detach().double()
-        got = got.detach().cpu().double().reshape(ref.shape)
-        assert torch.isfinite(got).all(), (self.name, label, "not finite")
-        r32 = r32.detach().double().reshape(ref.shape)
-        if ref.dim() < 2:
-            got, ref, r32, dim = got.reshape(1, -1), ref.reshape(1, -1), r32.reshape(1, -1), 0
-        m = co.measure(got, ref, dim)
-        e = co.measure(r32, ref, dim)
-        assert m["zero_ok"], (self.name, label, "a channel whose reference is exactly 0 is not met exactly")
-        for ms in co.MEASURES:
-            tol = max(K * e[ms], FLOOR[kind])
-            STATS.append((self.name, label, kind, ms, e[ms], m[ms]))
-            print(f"[{self.name}] {label:22s} {ms:3s} e32 {e[ms]:.2e} hip {m[ms]:.2e} ratio "
-                  f"{m[ms] / max(e[ms], FLOOR[kind] / K):.2f} tol {tol:.2e}")
-            if not m[ms] <= tol:
-                self.bad.append((label, ms, f"e32 {e[ms]:.3e}", f"hip {m[ms]:.3e}", f"tol {tol:.3e}"))
-
-    def done(self):
-        torch.cuda.synchronize()
-        assert not self.bad, (self.name, self.bad)
-
-
-def _nan(*shape):
-    return torch.full(shape, NAN, device="cuda")
+    if STATS:
+        ao.print_report("adversarial2d", STATS, FLOOR, width=22)
+        kit.report(STATS, "MIS_ADVERSARIAL2D_STATS", {"stats": STATS})
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -148,7 +102,7 @@ def _nan(*shape):
 @pytest.mark.parametrize("name", ao.names())
 def test_conv_forward_data_gradient_weight_gradient(name):
     ops = _ops()
-    chk = _Check(name)
+    chk = _checker(name)
     c = ao.case(name)
     r64, r32, _ = ao.references(name)
     N, Cin, Cout, H, W = c["shape"]
@@ -158,7 +112,7 @@ def test_conv_forward_data_gradient_weight_gradient(name):
     wd, bd = c["w"].cuda(), c["b"].cuda()
     ys = []
     for _ in range(2):
-        y = _Out(osh, lay)
+        y = _out(osh, lay)
         ops.conv2d_k4s2_fwd(xv, None, wd, None, bd, None, y.v, slope=1.0)
         assert y.untouched()
         ys.append(y.v)
@@ -166,7 +120,7 @@ def test_conv_forward_data_gradient_weight_gradient(name):
     assert torch.equal(ys[0], ys[1]), (name, "the forward is not run-to-run bit-identical")
     dxs = []
     for _ in range(2):
-        dx = _Out((N, Cin, H, W), lay)
+        dx = _out((N, Cin, H, W), lay)
         ops.conv2d_k4s2_dgrad(dyv, None, wd, dx.v, slope=1.0)
         assert dx.untouched()
         dxs.append(dx.v)
@@ -217,7 +171,7 @@ def test_activation_and_dropout_epilogue(name):
     both gradients.  The decisions are compared where the float64 pre-activation is outside the margin; the values are
     held to the oracle evaluated on the decisions the kernel took."""
     ops = _ops()
-    chk = _Check("act:" + name)
+    chk = _checker("act:" + name)
     c = ao.case(name)
     r64, r32, _ = ao.references(name)
     N, Cin, Cout, H, W = c["shape"]
@@ -259,7 +213,7 @@ def test_first_layer_reads_softmax_of_logits(shape):
     written separately, and the gradient at the softmax output (the `map` gradient, Cin <= 4); 4-D and [N, C, 1, H, W] views."""
     ops = _ops()
     N, Cl, Cx, Cout, H, W = shape
-    chk = _Check(f"first:{shape}")
+    chk = _checker(f"first:{shape}")
     g = torch.Generator().manual_seed(sum(shape))
     lg = (torch.randn(N, Cl, H, W, generator=g, dtype=F64) * 2).float()
     im = torch.randn(N, Cx, H, W, generator=g, dtype=F64).float()
@@ -308,7 +262,7 @@ HEAD_CASES = [(1, 20, (2, 2), (1, 1)), (3, 37, (5, 5), (2, 2)), (3, 20, (16, 16)
 @pytest.mark.parametrize("N,C,ext,pool", HEAD_CASES)
 def test_head_windowed_pool_linear_cross_entropy(N, C, ext, pool):
     ops = _ops()
-    chk = _Check(f"head:{N}x{C}x{ext}/{pool}")
+    chk = _checker(f"head:{N}x{C}x{ext}/{pool}")
     g = torch.Generator().manual_seed(N * 1000 + C + ext[0])
     nwh, nww = ext[0] // pool[0], ext[1] // pool[1]
     Fe = C * nwh * nww
@@ -344,7 +298,7 @@ def test_whole_chain_against_the_oracle_on_the_decisions_it_took(name):
     from networks.discriminator_2d import FCDiscriminator
     ndf, H, W, pool, N, _, _ = ao.CHAINS[name]
     C = ao.CHAIN_CLASSES
-    chk = _Check(f"chain:{name}")
+    chk = _checker(f"chain:{name}")
     img, lg, sd, masks, target, pool = ao.chain_inputs(name)
     dan = FCDiscriminator(C, ndf, 1, pool=pool)
     dan.load_state_dict(sd)

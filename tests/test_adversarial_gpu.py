@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import adversarial_oracle as ao
-from test_adversarial_kernels_gpu import _Check, _one_thread
+from oracle_kit import one_thread as _one_thread
 
 pytestmark = pytest.mark.gpu
 
@@ -167,7 +167,7 @@ def test_the_goldens_reference_iteration_is_reproduced_within_the_gate():
     ops = _ops()
     g = np.load(ao.__file__.replace("adversarial_oracle.py", "golden/adversarial_3d.npz"))
     gold = lambda k: torch.from_numpy(np.asarray(g[k])).double()
-    chk = _Check("golden")
+    chk = ao.Check("golden")
     vol, logits, _ = ao.golden_inputs(B, C, SIZE)
     sd0 = ao.golden_state_dict(C, 4, 1)
     masks = ao.golden_masks(4, B)

@@ -67,23 +67,24 @@ max(e32, FLOOR / K): the error in units of fp32 noise, the gate is at 6.  55 cas
     onto few channels, where torch's own fp32 error is at 1e-7 and the floor decides.  The Adam rows measure the UPDATE
     (parameter - initial parameter): both fp32 evaluations round the parameter itself, which is 1e-3 of an update of 1e-4.
 """
-import json
-import os
+import functools
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 import adversarial_oracle as ao
-import conv_oracle as co
-from test_norm_edges_gpu import NAN, _in, _Out
+import oracle_kit as kit
+from oracle_kit import NAN, nan as _nan, one_thread as _one_thread
 
 pytestmark = pytest.mark.gpu
 
 K, FLOOR = ao.K, ao.FLOOR
 # A tensor over the gate is a finding, named here with its measured ratio: {case: {(label, measure)}}.
 OVER_THE_GATE = {}
-STATS = []        # (case, label, kind, measure, e32, hip)
+LEAD, TRAIL = 1, 2            # channels of the wider buffer before / after a slice
+_in, _out = functools.partial(kit.place, lead=LEAD, trail=TRAIL), functools.partial(kit.Out, lead=LEAD, trail=TRAIL)
+_checker = functools.partial(ao.Check, floor=FLOOR, over_the_gate=OVER_THE_GATE)      # rows go to ao.STATS
+STATS = ao.STATS   # (case, label, kind, measure, e32, hip); tests/test_adversarial_gpu.py adds its golden's rows
 F64 = torch.float64
 
 
@@ -95,69 +96,9 @@ def _ops():
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    if not STATS:
-        return
-    rows = {}
-    for cid, label, kind, m, e32, ehip in STATS:
-        group = cid.split(":")[0] if ":" in cid else "conv"
-        r = rows.setdefault((group, label, m), dict(lo=1e9, hi=0.0, ratio=0.0, hip=0.0, at=""))
-        r["lo"], r["hi"], r["hip"] = min(r["lo"], e32), max(r["hi"], e32), max(r["hip"], ehip)
-        ratio = ehip / max(e32, FLOOR[kind] / K)
-        if ratio > r["ratio"]:
-            r["ratio"], r["at"] = ratio, cid
-    for (group, label, m), r in sorted(rows.items()):
-        print(f"\n[adversarial] {group:8s} {label:14s} {m:3s} e32 {r['lo']:.1e} .. {r['hi']:.1e}  hip max {r['hip']:.2e}  "
-              f"worst hip/max(e32, floor/K) {r['ratio']:.2f} ({r['at']})", end="")
-    print()
-    path = os.environ.get("MIS_ADVERSARIAL_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"stats": STATS}, f)
-
-
-def _one_thread(fn):
-    threads = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return fn()
-    finally:
-        torch.set_num_threads(threads)
-
-
-class _Check:
-    """The gate on one tensor: got against ref64, e32 from the fp32 evaluation r32 of the same expression."""
-
-    def __init__(self, name):
-        self.name, self.bad = name, []
-
-    def __call__(self, label, kind, got, ref, r32, dim=1):
-        ref = ref.detach().double()
-        got = got.detach().cpu().double().reshape(ref.shape)
-        assert torch.isfinite(got).all(), (self.name, label, "not finite")
-        if ref.dim() < 2:
-            got, ref, r32, dim = got.reshape(1, -1), ref.reshape(1, -1), r32.detach().double().reshape(1, -1), 0
-        m = co.measure(got, ref, dim)
-        e = co.measure(r32.detach().double().reshape(ref.shape), ref, dim)
-        assert m["zero_ok"], (self.name, label, "a channel whose reference is exactly 0 is not met exactly")
-        for ms in co.MEASURES:
-            tol = max(K * e[ms], FLOOR[kind])
-            STATS.append((self.name, label, kind, ms, e[ms], m[ms]))
-            print(f"[{self.name}] {label:14s} {ms:3s} e32 {e[ms]:.2e} hip {m[ms]:.2e} ratio "
-                  f"{m[ms] / max(e[ms], FLOOR[kind] / K):.2f} tol {tol:.2e}")
-            if not m[ms] <= tol:
-                self.bad.append((label, ms, f"e32 {e[ms]:.3e}", f"hip {m[ms]:.3e}", f"tol {tol:.3e}"))
-
-    def done(self):
-        torch.cuda.synchronize()
-        known = OVER_THE_GATE.get(self.name)
-        if known:
-            assert {(b[0], b[1]) for b in self.bad} == known, (self.name, "expected over the gate", known, "found", self.bad)
-            pytest.xfail(f"{self.name}: {self.bad}")
-        assert not self.bad, (self.name, self.bad)
-
-
-def _nan(*shape):
-    return torch.full(shape, NAN, device="cuda")
+    if STATS:
+        ao.print_report("adversarial", STATS, FLOOR)
+        kit.report(STATS, "MIS_ADVERSARIAL_STATS", {"stats": STATS})
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -166,7 +107,7 @@ def _nan(*shape):
 @pytest.mark.parametrize("name", ao.names())
 def test_conv_forward_data_gradient_weight_gradient(name):
     ops = _ops()
-    chk = _Check(name)
+    chk = _checker(name)
     c = ao.case(name)
     r64, r32, _ = ao.references(name)
     N, Cin, Cout, D, H, W = c["shape"]
@@ -176,7 +117,7 @@ def test_conv_forward_data_gradient_weight_gradient(name):
     wd, bd = c["w"].cuda(), c["b"].cuda()
     ys = []
     for _ in range(2):
-        y = _Out(osh, lay)
+        y = _out(osh, lay)
         ops.conv_k4s2_fwd(xv, None, wd, None, bd, None, y.v, slope=1.0)
         assert y.untouched()
         ys.append(y.v)
@@ -184,7 +125,7 @@ def test_conv_forward_data_gradient_weight_gradient(name):
     assert torch.equal(ys[0], ys[1]), (name, "the forward is not run-to-run bit-identical")
     dxs = []
     for _ in range(2):
-        dx = _Out((N, Cin, D, H, W), lay)
+        dx = _out((N, Cin, D, H, W), lay)
         ops.conv_k4s2_dgrad(dyv, None, wd, dx.v, slope=1.0)
         assert dx.untouched()
         dxs.append(dx.v)
@@ -225,7 +166,7 @@ def test_activation_and_dropout_epilogue(name):
     both gradients.  The decisions are compared where the float64 pre-activation is outside the margin; the values are
     held to the oracle evaluated on the decisions the kernel took."""
     ops = _ops()
-    chk = _Check("act:" + name)
+    chk = _checker("act:" + name)
     c = ao.case(name)
     r64, r32, _ = ao.references(name)
     N, Cin, Cout, D, H, W = c["shape"]
@@ -267,7 +208,7 @@ def test_first_layer_reads_softmax_of_logits(shape):
     written separately, and the gradient at the softmax output."""
     ops = _ops()
     N, Cl, Cx, Cout, D, H, W = shape
-    chk = _Check(f"first:{shape}")
+    chk = _checker(f"first:{shape}")
     g = torch.Generator().manual_seed(sum(shape))
     lg = (torch.randn(N, Cl, D, H, W, generator=g, dtype=F64) * 2).float()
     im = torch.randn(N, Cx, D, H, W, generator=g, dtype=F64).float()
@@ -329,7 +270,7 @@ HEAD_CASES = [(1, 4, (1, 1, 1)), (3, 20, (2, 3, 1)), (2, 64, (1, 1, 1)), (4, 512
 @pytest.mark.parametrize("N,C,ext", HEAD_CASES)
 def test_head_pool_linear_cross_entropy(N, C, ext):
     ops = _ops()
-    chk = _Check(f"head:{N}x{C}x{ext}")
+    chk = _checker(f"head:{N}x{C}x{ext}")
     g = torch.Generator().manual_seed(N * 1000 + C)
     a = torch.randn(N, C, *ext, generator=g, dtype=F64).float()
     w = (torch.randn(2, C, generator=g, dtype=F64) / C ** 0.5).float()
@@ -363,7 +304,7 @@ TAIL_CASES = [(2, 1, 2, (3, 5, 7), 0.1), (4, 2, 2, (8, 8, 8), 0.05), (3, 1, 3, (
 @pytest.mark.parametrize("B,L,C,ext,w", TAIL_CASES)
 def test_adversarial_tail(B, L, C, ext, w):
     ops = _ops()
-    chk = _Check(f"tail:{B},{L},{C},{ext},{w}")
+    chk = _checker(f"tail:{B},{L},{C},{ext},{w}")
     g = torch.Generator().manual_seed(B * 100 + L * 10 + C)
     lg = (torch.randn(B, C, *ext, generator=g, dtype=F64) * 2).float()
     lab = torch.randint(0, C, (B,) + ext, generator=g).to(torch.uint8)
@@ -389,7 +330,7 @@ def test_adversarial_tail(B, L, C, ext, w):
 def test_adam_step(n, first):
     """Steps ``first`` and ``first + 1`` (1 and 2: the fresh state; 1000: the bias correction far along)."""
     ops = _ops()
-    chk = _Check(f"adam:{n},{first}")
+    chk = _checker(f"adam:{n},{first}")
     g = torch.Generator().manual_seed(n + first)
     p0 = torch.randn(n, generator=g, dtype=F64).float()
     grads = [(torch.randn(n, generator=g, dtype=F64) * 10.0 ** (-2 * i)).float() for i in range(2)]
@@ -449,7 +390,7 @@ def _chain_inputs(N, C, size, ndf, seed):
 def test_whole_chain_against_the_oracle_on_the_decisions_it_took(ndf, size, pool):
     from networks.discriminator import FC3DDiscriminator
     N, C = 3 if size == 16 else 2, 2
-    chk = _Check(f"chain:{ndf}@{size}")
+    chk = _checker(f"chain:{ndf}@{size}")
     vol, lg, sd = _chain_inputs(N, C, size, ndf, ndf + size)
     masks = ao.golden_masks(ndf, N)
     target = (torch.arange(N) < (N + 1) // 2).int()

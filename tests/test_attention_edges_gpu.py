@@ -72,6 +72,7 @@ older test; a library whose 2-D bf16x3 products lose one third-order piece (a.h 
 (w7-2x14x14x3-s3/peaked out: 1.07e-4 against 1.3e-5) and passes every older test.
 """
 import ctypes
+import functools
 import json
 import os
 import subprocess
@@ -81,6 +82,8 @@ import pytest
 import torch
 
 import attention_oracle as ao
+import oracle_kit as kit
+from oracle_kit import NAN
 
 pytestmark = pytest.mark.gpu
 
@@ -91,9 +94,8 @@ FLOOR = {"out": 8.3e-6,      # largest e32 of the matrix: 8.27e-6 (full-2x70x3/o
 # {case: {(label, measure)}}: tensors known to sit over the gate, by name, each with its measured figure in a comment.  Strict
 # and narrow as in tests/test_conv_edges_gpu.py: the case xfails only when exactly these entries are over the gate.
 OVER_THE_GATE = {}
-NAN = float("nan")
-SENT = -777.0
 LEAD, TRAIL = 4, 8            # columns of the wider buffer before / after a slice (16-byte aligned, row strides % 4 == 0)
+_in, _out = functools.partial(kit.place, lead=LEAD, trail=TRAIL), functools.partial(kit.Out, lead=LEAD, trail=TRAIL)
 STATS = []                    # (group, case, label, kind, measure, e32, hip, kernel)
 KERNELS_2D = {"mfma_f32": ("attn_fwd_mfma_kernel<0>", "attn_bwd_mfma_kernel<0> + attn_dtable_sum_kernel"),
               "mfma_bf16x3": ("attn_fwd_mfma_kernel<1>", "attn_bwd_mfma_kernel<1> + attn_dtable_sum_kernel"),
@@ -108,14 +110,8 @@ def _tops():
 
 
 def _print_report():
-    rows = {}
-    for group, cid, label, kind, m, e32, ehip, kernel in STATS:
-        r = rows.setdefault((kernel, kind, m), dict(lo=1e9, hi=0.0, ratio=0.0, hip=0.0, at=""))
-        r["lo"], r["hi"], r["hip"] = min(r["lo"], e32), max(r["hi"], e32), max(r["hip"], ehip)
-        ratio = ehip / max(e32, FLOOR[kind] / K)
-        if ratio >= r["ratio"]:
-            r["ratio"], r["at"] = ratio, f"{cid} {label}"
-    for (kernel, kind, m), r in sorted(rows.items()):
+    for (kernel, kind, m), r in kit.worst_rows(((kernel, kind, m), f"{cid} {label}", e32, ehip, max(e32, FLOOR[kind] / K))
+                                               for group, cid, label, kind, m, e32, ehip, kernel in STATS):
         print(f"\n[attention edges] {kernel:74s} {kind:6s} {m:3s} e32 {r['lo']:.1e} .. {r['hi']:.1e}  hip max {r['hip']:.2e}  "
               f"worst hip/max(e32, floor/K) {r['ratio']:.2f} ({r['at']})", end="")
     print()
@@ -127,64 +123,24 @@ def _report():
     if not STATS:
         return
     _print_report()
-    path = os.environ.get("MIS_ATTN_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"stats": STATS}, f)
+    kit.report(STATS, "MIS_ATTN_STATS", {"stats": STATS})
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # buffers and comparison
 # ---------------------------------------------------------------------------------------------------------------------
-def _in(t, layout):
-    """Device copy of a [rows][cols] input: dense, or a column slice of a wider NaN-filled buffer."""
-    if layout == "dense":
-        return t.cuda()
-    buf = torch.full((t.shape[0], LEAD + t.shape[1] + TRAIL), NAN, device="cuda")
-    v = buf[:, LEAD:LEAD + t.shape[1]]
-    v.copy_(t.cuda())
-    return v
-
-
-class _Out:
-    """A NaN-filled [rows][cols] output: dense, or a column slice of a wider sentinel-filled buffer."""
-
-    def __init__(self, shape, layout):
-        if layout == "dense":
-            self.buf = None
-            self.v = torch.full(tuple(shape), NAN, device="cuda")
-        else:
-            self.buf = torch.full((shape[0], LEAD + shape[1] + TRAIL), SENT, device="cuda")
-            self.v = self.buf[:, LEAD:LEAD + shape[1]]
-            self.v.fill_(NAN)
-
-    def untouched(self):
-        cols = self.v.shape[1]
-        return self.buf is None or bool((self.buf[:, :LEAD] == SENT).all() and (self.buf[:, LEAD + cols:] == SENT).all())
-
-
 class _Check:
     def __init__(self, group, name):
         self.group, self.name = group, name
         self.c = ao.case(name)
         self.z = ao.sizes(self.c)
         self.r64 = ao.references(name)[0]
-        self.bad = []
+        self.gate = kit.Gate(K, FLOOR, OVER_THE_GATE, STATS)
 
     def __call__(self, kind, got, kernel, label="", ref=None, e32=None):
-        ref = self.r64[kind] if ref is None else ref
-        got = got.detach().cpu().double().reshape(ref.shape)
-        assert torch.isfinite(got).all(), (self.name, label or kind, "not finite")
-        m = ao.measure(got, ref)
-        assert m["zero_ok"], (self.name, label or kind, "a column whose reference is exactly 0 is not met exactly")
-        for ms in ao.MEASURES:
-            e = ao.yardstick(self.name, kind, ms) if e32 is None else e32[ms]
-            tol = max(K * e, FLOOR[kind])
-            STATS.append((self.group, self.name, label or kind, kind, ms, e, m[ms], kernel))
-            print(f"[{self.group} {self.name}] {label or kind:10s} {ms:3s} e32 {e:.2e} hip {m[ms]:.2e} tol {tol:.2e}  {kernel}")
-            if not m[ms] <= tol:
-                self.bad.append((label or kind, ms, f"e32 {e:.3e}", f"hip {m[ms]:.3e}", f"tol {tol:.3e}", kernel))
-        return m
+        return self.gate.tensor(self.name, label or kind, kind, got, self.r64[kind] if ref is None else ref, ao.measure,
+                                {ms: ao.yardstick(self.name, kind, ms) if e32 is None else e32[ms] for ms in ao.MEASURES},
+                                (self.group, self.name), (kernel,), width=10)
 
     def accumulated(self, dt, launch):
         """``launch(dtable, accumulate=True)`` onto a non-zero table gradient: base + the gradient ``dt`` of the plain launch (held
@@ -197,12 +153,7 @@ class _Check:
         assert bool((err <= 2.0 ** -24 * want.abs()).all()), (self.name, "accumulate_table", err.max().item())
 
     def done(self):
-        torch.cuda.synchronize()
-        known = OVER_THE_GATE.get(self.name)
-        if known:
-            assert {(b[0], b[1]) for b in self.bad} == known, (self.name, "expected over the gate", known, "found", self.bad)
-            pytest.xfail(f"{self.name}: {self.bad}")
-        assert not self.bad, (self.name, self.bad)
+        self.gate.done(self.name)
 
 
 def _layout(c):
@@ -224,7 +175,7 @@ def _run_win2d(group, name, expect, qkv_view=None, split_refused=False):
     qkv = qkv_view if qkv_view is not None else _in(c["qkv"], lay)
     dout, table = _in(c["dout"], lay), c["table"].cuda()
     kf, kb = (f"ws{ws} {k}" for k in KERNELS_2D[expect])
-    out = _Out((T, C), lay)
+    out = _out((T, C), lay)
     assert tops.window_attention_path(B, H, W, nH, qkv, out.v, window=ws) == expect
     tops.window_attention_fwd(qkv, out.v, table, B, H, W, nH, shift, scale, window=ws)
     chk("out", out.v, kf)
@@ -234,7 +185,7 @@ def _run_win2d(group, name, expect, qkv_view=None, split_refused=False):
         assert tops.window_attention_path(B, H, W, nH, qkv, dout, dq, window=ws) == expect
         tops.window_attention_bwd(qkv, dout, dq, table, dt, B, H, W, nH, shift, scale, accumulate_table=accumulate, window=ws)
 
-    dq, dq2 = _Out((T, 3 * C), lay), _Out((T, 3 * C), lay)
+    dq, dq2 = _out((T, 3 * C), lay), _out((T, 3 * C), lay)
     dt, dt2 = torch.full_like(table, NAN), torch.full_like(table, NAN)
     bwd(dq.v, dt)
     chk("dqkv", dq.v, kb)
@@ -242,7 +193,7 @@ def _run_win2d(group, name, expect, qkv_view=None, split_refused=False):
     bwd(dq2.v, dt2)
     assert torch.equal(dq.v, dq2.v) and torch.equal(dt, dt2), (name, "the backward is not deterministic")
     assert dq.untouched() and dq2.untouched()
-    dq3 = _Out((T, 3 * C), lay)
+    dq3 = _out((T, 3 * C), lay)
     chk.accumulated(dt, lambda t, acc: bwd(dq3.v, t, acc))
     assert torch.equal(dq.v, dq3.v)
     partials = tops.window_attention_table_partials(B, H, W, nH, window=ws)
@@ -312,8 +263,7 @@ def _valu_child(name):
     rows, cols = ctypes.c_longlong(0), ctypes.c_int(0)
     assert lib.load().mis_window_attention_table_partials(B, H, W, nH, ws, ctypes.byref(rows), ctypes.byref(cols)) == -2
     print("STATS " + json.dumps(STATS))
-    torch.cuda.synchronize()
-    assert not chk.bad, (name, chk.bad)
+    chk.done()
 
 
 @pytest.mark.parametrize("name", ao.names("valu"))
@@ -348,12 +298,12 @@ def test_full_attention(name):
     T, C, scale = z["T"], z["C"], z["scale"]
     lay = _layout(c)
     qkv, dout = _in(c["qkv"], lay), _in(c["dout"], lay)
-    out = _Out((T, C), lay)
+    out = _out((T, C), lay)
     stats = torch.full((B * nH * N * 2,), NAN, device="cuda")
     tops.full_attention_fwd(qkv, out.v, stats, B, N, nH, scale)
     chk("out", out.v, "full_attn_fwd_kernel")
     assert out.untouched() and torch.isfinite(stats).all()
-    dq, dq2 = _Out((T, 3 * C), lay), _Out((T, 3 * C), lay)
+    dq, dq2 = _out((T, 3 * C), lay), _out((T, 3 * C), lay)
     tops.full_attention_bwd(qkv, dout, dq.v, stats, B, N, nH, scale)
     chk("dqkv", dq.v, "full_attn_bwd_kernel<false> + <true>")
     tops.full_attention_bwd(qkv, dout, dq2.v, stats, B, N, nH, scale)
@@ -380,7 +330,7 @@ def test_window_attention_3d(name):
         from oracle.swinunetr import region_ids
         region = region_ids(z["pdims"], z["win"], z["shift"]).to(torch.int32).contiguous().cuda()
     qkv, dout, table = _in(c["qkv"], lay), _in(c["dout"], lay), c["table"].cuda()
-    out = _Out((T, C), lay)
+    out = _out((T, C), lay)
     stats = torch.full((BW * nH * n * 2,), NAN, device="cuda")
     tops.win3d_attn_fwd(qkv, out.v, stats, table, region, BW, nW, n, nH)
     chk("out", out.v, "attn3d_fwd_kernel")
@@ -390,7 +340,7 @@ def test_window_attention_3d(name):
     def bwd(dq, dt, accumulate=False):
         tops.win3d_attn_bwd(qkv, out.v, dout, dq, stats, table, region, dt, BW, nW, n, nH, accumulate_table=accumulate)
 
-    dq, dq2, dq3 = (_Out((T, 3 * C), lay) for _ in range(3))
+    dq, dq2, dq3 = (_out((T, 3 * C), lay) for _ in range(3))
     dt, dt2 = torch.full_like(table, NAN), torch.full_like(table, NAN)
     bwd(dq.v, dt)
     chk("dqkv", dq.v, kb)

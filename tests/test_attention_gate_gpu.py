@@ -33,13 +33,14 @@ Measured on an MI355X (this file's own run; `MIS_ATTN_GATE_STATS=<file>` writes 
 e32 here is from the GPU machine's run of the CPU operators (32 threads); FLOOR is from one thread (the CPU test).  The adjoint's
 e32 is torch's scatter order over up to 16^3 outputs per cell; the kernel's wave tree stays at 1.6e-7.  510 figures, 63 tests.
 """
-import json
-import os
+import functools
 
 import pytest
 import torch
 
 import attention_gate_cases as ac
+import oracle_kit as kit
+from oracle_kit import NAN, SENT
 
 pytestmark = pytest.mark.gpu
 
@@ -49,9 +50,8 @@ FLOOR = {"att": 1.5e-7,       # largest e32 of the attention maps: 1.42e-7 (map-
          "dx": 3.1e-7,        # of dx / datt / df: 3.03e-7 (datt of apply-C5-1x1x1)
          "sum": 7.8e-7,       # of dpsi_w / dpsi_b / dphi_b: 7.74e-7 (dpsi_w of map-Ci1-3x5x7)
          "upT": 2.5e-6}       # of the up-sampling adjoint: 2.46e-6 (up8-K2-4x2x6)
-NAN = float("nan")
-SENT = -777.0
 LEAD, TRAIL = 1, 2            # channels of the wider buffer before / after a slice
+_out = functools.partial(kit.Out, lead=LEAD, trail=TRAIL)
 STATS = []
 LAYOUTS = ("dense", "slice")
 
@@ -62,60 +62,32 @@ def _ops():
 
 
 def _in(t, layout):
-    """the fp32 device copy of an input; ``slice``: inside a wider buffer of NaN"""
-    t = t.float().cuda()
-    if layout == "dense" or t.dim() != 5:
-        return t.contiguous()
-    buf = torch.full((t.shape[0], LEAD + t.shape[1] + TRAIL) + tuple(t.shape[2:]), NAN, device="cuda")
-    buf[:, LEAD:LEAD + t.shape[1]] = t
-    return buf[:, LEAD:LEAD + t.shape[1]]
-
-
-def _out(shape, layout, fill=None):
-    """(buffer, view): the view is NaN (or ``fill``: what an accumulating call finds); ``slice``: a sentinel around it"""
-    C = shape[1]
-    if layout == "dense":
-        buf = torch.full(shape, NAN, device="cuda")
-        view = buf
-    else:
-        buf = torch.full((shape[0], LEAD + C + TRAIL) + tuple(shape[2:]), SENT, device="cuda")
-        view = buf[:, LEAD:LEAD + C]
-        view.fill_(NAN)
-    if fill is not None:
-        view.copy_(fill.float())
-    return buf, view
-
-
-def _intact(buf, view, layout):
-    if layout == "slice":
-        C = view.shape[1]
-        assert bool((buf[:, :LEAD] == SENT).all()) and bool((buf[:, LEAD + C:] == SENT).all()), "sentinel overwritten"
+    """the fp32 device copy of an input; ``slice``: the 5-D tensors inside a wider buffer of NaN"""
+    return kit.place(t.float().contiguous(), layout if t.dim() == 5 else "dense", LEAD, TRAIL)
 
 
 def _check(label, out, hip, ref, e32, base=None):
     """``base``: what an accumulating call found in the output (float64 of the fp32 values)"""
     hip = hip.detach().cpu().double()
     assert tuple(hip.shape) == tuple(ref.shape), (label, out, hip.shape, ref.shape)
-    assert bool(torch.isfinite(hip).all()), (label, out, "not finite")
+    gate = kit.Gate(K, FLOOR)
+    gate.finite(hip, (label, out))
     kind = ac.KIND_OF[out.split("+")[0]]
-    tol = max(K * e32, FLOOR[kind])
     if base is None:
         err = float((hip - ref).abs().max() / ref.abs().max())
     else:
         rounding = 2.0 ** -24 * float((base + ref).abs().max())
         err = max(float((hip - (base + ref)).abs().max()) - rounding, 0.0) / float(ref.abs().max())
+    tol = gate.judge(label, out, kind, "max", e32, err)
     STATS.append(dict(case=label, out=out, kind=kind, e32=e32, hip=err, tol=tol, floor=K * e32 < FLOOR[kind]))
     print(f"[attention gate] {label:28s} {out:10s} e32 {e32:.2e}  hip {err:.2e}  hip / tolerance {err / tol:.2f}")
-    assert err <= tol, (label, out, err, tol)
+    gate.done(label)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _stats_file():
     yield
-    path = os.environ.get("MIS_ATTN_GATE_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump(STATS, f)
+    kit.report(STATS, "MIS_ATTN_GATE_STATS")
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
@@ -126,22 +98,24 @@ def test_gate_map_forward_and_backward(ci, grid, layout):
     i = c["in"]
     theta, phi = _in(i["theta"], layout), _in(i["phi"], layout)
     psi_w, psi_b = i["psi_w"].float().cuda(), i["psi_b"].float().cuda()
-    abuf, att = _out(c["att"].shape, layout)
+    abuf = _out(c["att"].shape, layout)
+    att = abuf.v
     ops.attn_gate_map_fwd(theta, phi, psi_w, psi_b, att)
     _check(label, "att", att, c["att"], c["e32"]["att"])
-    _intact(abuf, att, layout)
+    assert abuf.untouched(), "sentinel overwritten"
     # backward from the oracle's maps (rounded to fp32), so that the two directions are judged separately
     datt, att_in = _in(i["datt"], layout), _in(c["att"], layout)
     runs = []
     for accumulate in (False, True, False):
         base_w, base_b, base_p = (i[k].float().double() for k in ("dw0", "db0", "dp0"))
-        fbuf, df = _out(c["df"].shape, layout)
+        fbuf = _out(c["df"].shape, layout)
+        df = fbuf.v
         dw = base_w.float().cuda() if accumulate else torch.full((ac.G, ci), NAN, device="cuda")
         db = base_b.float().cuda() if accumulate else torch.full((ac.G,), NAN, device="cuda")
         dp = base_p.float().cuda() if accumulate else torch.full((ac.G * ci,), NAN, device="cuda")
         ops.attn_gate_map_bwd(datt, att_in, theta, phi, psi_w, df, dw, db, dp, accumulate=accumulate)
         torch.cuda.synchronize()
-        _intact(fbuf, df, layout)
+        assert fbuf.untouched(), "sentinel overwritten"
         if accumulate:
             _check(label, "dpsi_w+", dw, c["dpsi_w"], c["e32"]["dpsi_w"], base_w)
             _check(label, "dpsi_b+", db, c["dpsi_b"], c["e32"]["dpsi_b"], base_b)
@@ -165,19 +139,22 @@ def test_gate_apply_forward_and_backward(ch, grid, layout):
     label = f"apply-C{ch}-{'x'.join(map(str, grid))}-{layout}"
     i = c["in"]
     x, att = _in(i["x"], layout), _in(i["att"], layout)
-    ybuf, y = _out(c["y"].shape, layout)
+    ybuf = _out(c["y"].shape, layout)
+    y = ybuf.v
     ops.attn_gate_apply_fwd(x, att, y)
     _check(label, "y", y, c["y"], c["e32"]["y"])
-    _intact(ybuf, y, layout)
+    assert ybuf.untouched(), "sentinel overwritten"
     dy = _in(i["dy"], layout)
     runs = []
     for accumulate in (False, True, False):
-        xbuf, dx = _out(c["dx"].shape, layout, fill=i["dx0"] if accumulate else None)
-        abuf, datt = _out(c["datt"].shape, layout)
+        xbuf = _out(c["dx"].shape, layout, fill=i["dx0"] if accumulate else None)
+        dx = xbuf.v
+        abuf = _out(c["datt"].shape, layout)
+        datt = abuf.v
         ops.attn_gate_apply_bwd(dy, x, att, dx, datt, accumulate=accumulate)
         torch.cuda.synchronize()
-        _intact(xbuf, dx, layout)
-        _intact(abuf, datt, layout)
+        assert xbuf.untouched(), "sentinel overwritten"
+        assert abuf.untouched(), "sentinel overwritten"
         if accumulate:
             _check(label, "dx+", dx, c["dx"], c["e32"]["dx"], i["dx0"].float().double())
         else:

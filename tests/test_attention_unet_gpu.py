@@ -19,9 +19,8 @@ import pytest
 import torch
 
 import attention_unet_oracle as ao
-import test_norm_edges_gpu as ne
-from test_parity_gpu import F64_LOGIT
-from test_pnet_gpu import _check_grads
+import norm_oracle as no
+from net_gate import F64_LOGIT, check_grads as _check_grads
 
 pytestmark = pytest.mark.gpu
 
@@ -84,7 +83,7 @@ def test_train_mode_forward_backward_and_eval_forward_match_the_reference(gold, 
     m.backward_raw(dl.contiguous())
     torch.cuda.synchronize()
     e32 = dict(zip(params, (float(v) for v in gold["e32"])))
-    _check_grads(m, {k: torch.from_numpy(gold[f"grad/{k}"]) for k in params}, e32, "attention_unet golden")
+    _check_grads(m, {k: torch.from_numpy(gold[f"grad/{k}"]) for k in params}, e32, "pnet attention_unet golden")
     sd = m.state_dict()
     buffers = [str(k) for k in gold["keys"] if not ao.is_param(str(k))]
     e32_after = dict(zip([k for k in buffers if not k.endswith("num_batches_tracked")], (float(v) for v in gold["e32_after"])))
@@ -93,7 +92,7 @@ def test_train_mode_forward_backward_and_eval_forward_match_the_reference(gold, 
         if k.endswith("num_batches_tracked"):
             assert int(sd[k]) == int(ref) == 1
             continue
-        tol = max(ne.K * e32_after[k], ne.FLOOR["stat"])
+        tol = max(no.K * e32_after[k], no.FLOOR_STAT)
         e = float((sd[k].cpu().double() - ref).abs().max() / ref.abs().max())
         assert e <= tol, (k, e, tol)
     m.eval()

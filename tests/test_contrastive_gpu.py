@@ -17,7 +17,6 @@ and fp32 both on the LeakyReLU branches the pass took (_score_flat_grads).
 
 MIS_CONTRASTIVE_STATS=<file> writes every figure of the tail matrix (profiles/contrastive_tail_stats.json).
 """
-import json
 import os
 import subprocess
 import sys
@@ -28,13 +27,14 @@ import torch
 import torch.multiprocessing as mp
 
 import contrastive_oracle as co
+import oracle_kit as kit
 import patch_nce_oracle as pno
+from oracle_kit import NAN, same_bits as _same
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "cv-ssl-mis_amd")
-NAN = float("nan")
 PAD = 8
 ULP = 2.0 ** -23
 STATS = []
@@ -49,20 +49,10 @@ def _ops():
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    path = os.environ.get("MIS_CONTRASTIVE_STATS")
-    if path and STATS:
+    if STATS:
         worst = {k: max((r[k] for r in STATS), default=0.0) for k in ("e32_scalar", "hip_scalar", "e32_tensor", "hip_tensor")}
-        with open(path, "w") as f:
-            json.dump(dict(floor_scalar=co.FLOOR_SCALAR, floor_tensor=co.FLOOR_TENSOR, K=co.K, worst=worst, cases=STATS), f,
-                      indent=1)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
+        kit.report(STATS, "MIS_CONTRASTIVE_STATS", dict(floor_scalar=co.FLOOR_SCALAR, floor_tensor=co.FLOOR_TENSOR, K=co.K,
+                                                        worst=worst, cases=STATS), indent=1)
 
 
 def _np_sd(net):
@@ -215,26 +205,6 @@ def test_frozen_head_launches_no_weight_gradient_and_packs_once():
 # ---------------------------------------------------------------------------------------------------------------------
 # the tail
 # ---------------------------------------------------------------------------------------------------------------------
-def _place(t, layout, like=None):
-    """(buffer, view) of a CPU tensor [n, C, 1, H, W] (or of NaNs shaped ``like``): dense, batch-strided, or two rows into a
-    strided buffer."""
-    src = like if t is None else t
-    n, row = src.shape[0], src[0].numel()
-    off = 2 if layout == "offset" else 0
-    width = row + (0 if layout == "dense" else PAD)
-    buf = torch.full((n + off, width), NAN, device="cuda")
-    if t is not None:
-        buf[off:, :row] = t.reshape(n, row).cuda()
-    return buf, buf[off:, :row].view(src.shape)
-
-
-def _untouched_outside(buf, view):
-    rest = buf.clone()
-    n, row = view.shape[0], view[0].numel()
-    rest[rest.shape[0] - n:, :row].fill_(NAN)
-    return bool(torch.isnan(rest).all())
-
-
 def _state(w):
     ops = _ops()
     st = ops.new_step_state()
@@ -245,10 +215,10 @@ def _state(w):
 def _launch(c, x, layout, wmode="float", grad=True):
     ops = _ops()
     own, other, label, el, eu = x
-    vo, vt = _place(own, layout)[1], _place(other, layout)[1]
-    ve = [None if e is None else _place(e, layout)[1] for e in (el, eu)]
+    vo, vt = kit.place_rows(own, layout, PAD)[1], kit.place_rows(other, layout, PAD)[1]
+    ve = [None if e is None else kit.place_rows(e, layout, PAD)[1] for e in (el, eu)]
     out = torch.full((16,), NAN, device="cuda")
-    d = _place(None, layout, like=own) if grad else None
+    d = kit.place_rows(None, layout, PAD, like=own) if grad else None
     ops.scratch(1, "tail").view(torch.float32).fill_(NAN)
     wkw = dict(cons_weight=c["w"]) if wmode == "float" else dict(state=_state(c["w"]))
     ops.contrastive_cross_tail(vo, vt, label.cuda(), c["L"], out, dlogits=d and d[1], extra_l=ve[0], extra_u=ve[1], **wkw)
@@ -263,7 +233,7 @@ def test_contrastive_tail_matches_float64(c):
     out, d = _launch(c, x, c["layout"])
     assert torch.isfinite(out[:6]).all() and torch.isnan(out[6:]).all(), out           # six scalars and nothing else
     buf, view = d
-    assert torch.isfinite(view).all() and _untouched_outside(buf, view)                # every element once, nothing else
+    assert torch.isfinite(view).all() and kit.untouched_outside(buf, view)                # every element once, nothing else
     got = out[:6].cpu().double()
     hs = co.scalar_rels(got, out64)
     ht = co.rel(view.cpu(), d64)

@@ -44,15 +44,15 @@ FLOOR / K): the error in units of fp32 noise, the gate is at 6.  16 cases + 2, a
     gradients onto few channels (8 .. 16 products per tap), where torch's own fp32 error is at 1e-7 and the floor decides.
 """
 import ctypes
-import json
-import os
+import functools
 
 import pytest
 import torch
 
 import conv_oracle as co
 import dilated_oracle as do
-from test_norm_edges_gpu import NAN, _in, _Out
+import oracle_kit as kit
+from oracle_kit import NAN
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +60,8 @@ K, FLOOR = do.K, do.FLOOR
 # A tensor over the gate is a finding, named here with its measured ratio: {case: {(kind, measure)}}.  Strict: the case xfails
 # only when exactly these entries are over the gate.
 OVER_THE_GATE = {}
+LEAD, TRAIL = 1, 2            # channels of the wider buffer before / after a slice
+_in, _out = functools.partial(kit.place, lead=LEAD, trail=TRAIL), functools.partial(kit.Out, lead=LEAD, trail=TRAIL)
 STATS = []        # (case, label, kind, measure, e32, hip, kernel)
 
 
@@ -101,21 +103,12 @@ def _report():
     yield
     if not STATS:
         return
-    rows = {}
-    for cid, label, kind, m, e32, ehip, kernel in STATS:
-        r = rows.setdefault((kernel, kind, m), dict(lo=1e9, hi=0.0, ratio=0.0, hip=0.0, at=""))
-        r["lo"], r["hi"], r["hip"] = min(r["lo"], e32), max(r["hi"], e32), max(r["hip"], ehip)
-        ratio = ehip / max(e32, FLOOR[kind] / K)
-        if ratio > r["ratio"]:
-            r["ratio"], r["at"] = ratio, f"{cid} {label}"
-    for (kernel, kind, m), r in sorted(rows.items()):
+    for (kernel, kind, m), r in kit.worst_rows(((kernel, kind, m), f"{cid} {label}", e32, ehip, max(e32, FLOOR[kind] / K))
+                                               for cid, label, kind, m, e32, ehip, kernel in STATS):
         print(f"\n[dilated] {kernel:56s} {kind:2s} {m:3s} e32 {r['lo']:.1e} .. {r['hi']:.1e}  hip max {r['hip']:.2e}  "
               f"worst hip/max(e32, floor/K) {r['ratio']:.2f} ({r['at']})", end="")
     print()
-    path = os.environ.get("MIS_DILATED_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"stats": STATS}, f)
+    kit.report(STATS, "MIS_DILATED_STATS", {"stats": STATS})
 
 
 class _Check:
@@ -123,30 +116,16 @@ class _Check:
         self.name = name
         self.c = do.case(name)
         self.r64, self.r32, self.e32 = do.references(name)
-        self.bad = []
+        self.gate = kit.Gate(K, FLOOR, OVER_THE_GATE, STATS)
 
     def __call__(self, kind, got, kernel, label="", ref=None, e32=None):
-        ref = self.r64[kind] if ref is None else ref
-        got = got.detach().cpu().double().reshape(ref.shape)
-        assert torch.isfinite(got).all(), (self.name, kind, "not finite")
-        m = co.measure(got, ref, co.dim_of(self.c, kind))
-        assert m["zero_ok"], (self.name, kind, "a channel whose reference is exactly 0 is not met exactly")
-        for ms in co.MEASURES:
-            e = self.e32[kind][ms] if e32 is None else e32[ms]
-            tol = max(K * e, FLOOR[kind])
-            STATS.append((self.name, label or kind, kind, ms, e, m[ms], kernel))
-            print(f"[{self.name}] {label or kind:5s} {ms:3s} e32 {e:.2e} hip {m[ms]:.2e} ratio {m[ms] / max(e, FLOOR[kind] / K):.2f} "
-                  f"tol {tol:.2e}  {kernel}")
-            if not m[ms] <= tol:
-                self.bad.append((label or kind, ms, f"e32 {e:.3e}", f"hip {m[ms]:.3e}", f"tol {tol:.3e}", kernel))
+        e32 = self.e32[kind] if e32 is None else e32
+        self.gate.tensor(self.name, label or kind, kind, got, self.r64[kind] if ref is None else ref,
+                         lambda g, r: co.measure(g, r, co.dim_of(self.c, kind)), {ms: e32[ms] for ms in co.MEASURES},
+                         (self.name,), (kernel,), width=5)
 
     def done(self):
-        torch.cuda.synchronize()
-        known = OVER_THE_GATE.get(self.name)
-        if known:
-            assert {(b[0], b[1]) for b in self.bad} == known, (self.name, "expected over the gate", known, "found", self.bad)
-            pytest.xfail(f"{self.name}: {self.bad}")
-        assert not self.bad, (self.name, self.bad)
+        self.gate.done(self.name)
 
 
 @pytest.mark.parametrize("name", do.names())
@@ -164,11 +143,11 @@ def test_forward_data_gradient_weight_gradient(name):
     wd, bd = c["w"].cuda(), c["b"].cuda()
     keep, ops.DISPATCH = ops.DISPATCH, set()
     try:
-        y = _Out((N, Cout, 1, H, W), lay)
+        y = _out((N, Cout, 1, H, W), lay)
         ops.conv_dilated_fwd(xv, ops.conv_pack(wd, 0), bd, y.v, d)
         chk("y", y.v, ky)
         assert y.untouched()
-        dx = _Out((N, Cin, 1, H, W), lay)
+        dx = _out((N, Cin, 1, H, W), lay)
         ops.conv_dilated_fwd(dyv, ops.conv_pack(wd, 1), None, dx.v, d, dgrad=True)
         chk("dx", dx.v, kdx)
         assert dx.untouched()

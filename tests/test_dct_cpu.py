@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from dct_oracle import REF_FLAGS_VIT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -16,11 +18,6 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 REF_FLAGS_2D = ["--root_path", "--exp", "--model", "--max_iterations", "--batch_size", "--deterministic", "--base_lr",
                 "--patch_size", "--seed", "--num_classes", "--labeled_bs", "--labeled_num", "--ema_decay",
                 "--consistency_type", "--consistency", "--consistency_rampup"]
-REF_FLAGS_VIT = ["--root_path", "--exp", "--model", "--max_iterations", "--batch_size", "--deterministic", "--base_lr",
-                 "--patch_size", "--seed", "--num_classes", "--cfg", "--opts", "--zip", "--cache-mode", "--resume",
-                 "--accumulation-steps", "--use-checkpoint", "--amp-opt-level", "--tag", "--eval", "--throughput",
-                 "--labeled_bs", "--labeled_num", "--ema_decay", "--consistency_type", "--consistency",
-                 "--consistency_rampup"]
 REF_DEFAULTS = {
     "2D": dict(exp="ACDC/Deep_Co_Training", batch_size=24, labeled_bs=12, labeled_num=3, patch_size=[256, 256],
                model="unet", root_path="../data/ACDC", num_classes=4),

@@ -28,7 +28,6 @@ Measured on an MI355X (this file's own run; MIS_FIXMATCH_STATS=<file> writes eve
     double from the workgroup partials on); every gradient tensor is within 1.45 x its own e32 and below the tensor floor
     (K = 6 is never needed).
 """
-import json
 import os
 import subprocess
 import sys
@@ -38,6 +37,8 @@ import torch
 import torch.multiprocessing as mp
 
 import fixmatch_oracle as fo
+import oracle_kit as kit
+from oracle_kit import NAN, same_bits as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +46,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "cv-ssl-mis_amd")
 TOL_LOGIT = 1e-3            # of tests/test_dct_gpu.py
 TOL_LOSS = 1e-3
-NAN = float("nan")
 PAD = 8
 STATS = []
 
@@ -58,12 +58,10 @@ def _ops():
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    path = os.environ.get("MIS_FIXMATCH_STATS")
-    if path and STATS:
+    if STATS:
         worst = {k: max((r[k] for r in STATS), default=0.0) for k in ("e32_scalar", "hip_scalar", "e32_tensor", "hip_tensor")}
-        with open(path, "w") as f:
-            json.dump(dict(floor_scalar=fo.FLOOR_SCALAR, floor_tensor=fo.FLOOR_TENSOR, K=fo.K, worst=worst, cases=STATS), f,
-                      indent=1)
+        kit.report(STATS, "MIS_FIXMATCH_STATS", dict(floor_scalar=fo.FLOOR_SCALAR, floor_tensor=fo.FLOOR_TENSOR, K=fo.K,
+                                                     worst=worst, cases=STATS), indent=1)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -82,23 +80,15 @@ def _place(t, layout, like=None):
         view = view.view(src.shape)
         assert view.data_ptr() == buf.data_ptr() + 4
         return buf, view
-    off = 2 if layout == "offset" else 0
-    width = row + (0 if layout == "dense" else PAD)
-    buf = torch.full((n + off, width), NAN, device="cuda")
-    if t is not None:
-        buf[off:, :row] = t.reshape(n, row).cuda()
-    view = buf[off:, :row].view(src.shape)
-    assert view.data_ptr() == buf.data_ptr() + off * width * 4
-    return buf, view
+    return kit.place_rows(t, layout, PAD, like)
 
 
 def _untouched_outside(buf, view):
+    if buf.dim() == 2:
+        return kit.untouched_outside(buf, view)
     rest = buf.clone()
     n, row = view.shape[0], view[0].numel()
-    if rest.dim() == 1:
-        rest[1:].view(n, row + 1)[:, :row].fill_(NAN)
-    else:
-        rest[rest.shape[0] - n:, :row].fill_(NAN)
+    rest[1:].view(n, row + 1)[:, :row].fill_(NAN)
     return bool(torch.isnan(rest).all())
 
 
@@ -126,14 +116,6 @@ def _launch(c, x, layout, wmode, grads=(True, True), maps=True):
                       pseudo=pseudo, comp=comp, **wkw)
     torch.cuda.synchronize()
     return out, dw, ds, pseudo, comp
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 @pytest.mark.parametrize("c", fo.matrix(), ids=fo.cid)

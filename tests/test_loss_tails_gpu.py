@@ -38,25 +38,22 @@ out[4] still the weight, zero gradient on the unlabeled rows).  The cross and UA
 state (include/mis_hip.h: their callers fold any gate into the weights); for them gate 0 must change nothing.
 mis_cross_*_tail has no loss_scale argument, mis_dct_tail is 2-D only (odd rotations need square planes) and needs L, U > 0.
 """
-import json
-import os
+import functools
 import zlib
 
 import pytest
 import torch
 
 import loss_tail_oracle as lto
+from loss_tail_cases import K, MAX_IT, PAD, SHAPES, W, plant_ties as _plant_ties, state as _state
+import oracle_kit as kit
+from oracle_kit import NAN
 
 pytestmark = pytest.mark.gpu
 
-K = 6.0
-FLOOR_SCALAR = 2.6e-7      # largest scalar e32 of the matrix: 2.52e-7 (ict)
-FLOOR_TENSOR = 7.7e-7      # largest tensor e32 of the matrix: 7.69e-7 (dct)
-NAN = float("nan")
-W, W_MT = 0.37, 0.11
-MAX_IT = 1000
-SHAPES = {"2d": (1, 32, 48), "3d": (8, 12, 16), "part": (1, 40, 52), "odd": (1, 7, 9), "sq": (1, 36, 36),
-          "bigvec": (140, 140, 143), "bigscalar": (11, 151, 421)}
+FLOOR = {"scalar": 2.6e-7,      # largest scalar e32 of the matrix: 2.52e-7 (ict)
+         "tensor": 7.7e-7}      # largest tensor e32 of the matrix: 7.69e-7 (dct)
+W_MT = 0.11
 N_OUT = {"mt": lambda C: 5 + C, "cross": lambda C: 5, "cross_ce": lambda C: 5, "cross_mt": lambda C: 7,
          "uamt": lambda C: 7 + C, "ict": lambda C: 5 + C, "dct": lambda C: 6 + C}
 GATED = ("mt", "ict", "dct")
@@ -73,21 +70,11 @@ def _report():
     yield
     if not STATS:
         return
-    rows = {}
-    for tail, cid, kind, e32, ehip in STATS:
-        r = rows.setdefault((tail.split("_")[0], kind), dict(lo=1e9, hi=0.0, ratio=0.0, hip=0.0, at=""))
-        r["lo"], r["hi"], r["hip"] = min(r["lo"], e32), max(r["hi"], e32), max(r["hip"], ehip)
-        ratio = ehip / e32 if e32 > 0 else 0.0
-        if ratio > r["ratio"]:
-            r["ratio"], r["at"] = ratio, cid
-    for (tail, kind), r in sorted(rows.items()):
+    for (tail, kind), r in kit.worst_rows(((tail.split("_")[0], kind), cid, e32, ehip, e32) for tail, cid, kind, e32, ehip in STATS):
         print(f"\n[loss tails] {tail:6s} {kind:7s} e32 {r['lo']:.2e} .. {r['hi']:.2e}  hip max {r['hip']:.2e}  "
               f"worst hip/e32 {r['ratio']:.2f} ({r['at']})", end="")
     print()
-    path = os.environ.get("MIS_TAIL_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump(STATS, f)
+    kit.report(STATS, "MIS_TAIL_STATS")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -149,25 +136,6 @@ def _matrix(tail):
 # ---------------------------------------------------------------------------------------------------------------------
 # inputs and references (CPU only)
 # ---------------------------------------------------------------------------------------------------------------------
-def _plant_ties(o, C):
-    """Arg-max ties over three quarters of the voxels of ``o`` [n, C, ...]: all classes equal; the two largest equal at
-    positions (0, 2) ((0, 1) for C == 2); -0.0 at class 0 against +0.0 at class 1, the rest negative."""
-    flat = o.reshape(o.shape[0], C, -1)
-    S = flat.shape[2]
-    idx = torch.arange(S)
-    flat[:, :, idx[idx % 4 == 0]] = 1.5
-    second = 2 if C > 2 else 1
-    sel = idx[idx % 4 == 1]
-    flat[:, :, sel] = flat[:, :, sel].clamp(max=2.0)
-    flat[:, 0, sel] = 7.25
-    flat[:, second, sel] = 7.25
-    sel = idx[idx % 4 == 2]
-    flat[:, :, sel] = -1.0
-    flat[:, 0, sel] = -0.0
-    flat[:, 1, sel] = 0.0
-    return flat.reshape(o.shape)
-
-
 def _inputs(tail, c):
     """CPU fp32 operands of one case: logits operands by name (``ops``: name -> [n, C, D, H, W]), label, extras."""
     g = torch.Generator().manual_seed(zlib.crc32((tail + _cid(c)).encode()))
@@ -234,44 +202,10 @@ def _references(tail, c, x, gate=1.0):
     return o64, g64, o32.double(), [g.double() for g in g32]
 
 
-def _rel(a, ref):
-    m = ref.abs().max().item()
-    return (a - ref).abs().max().item() / m if m > 0 else 0.0
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # device placement and the kernel call
 # ---------------------------------------------------------------------------------------------------------------------
-PAD = 8          # batch stride C*S + 4*k, k = 2
-
-
-def _place(t, layout, like=None):
-    """(buffer, 5-D view, logical-region mask builder) of a CPU tensor [n, C, D, H, W] (or of NaNs shaped ``like``)."""
-    src = like if t is None else t
-    n, row = src.shape[0], src[0].numel()
-    off = 2 if layout == "offset" else 0
-    width = row + (0 if layout == "dense" else PAD)
-    buf = torch.full((n + off, width), NAN, device="cuda")
-    if t is not None:
-        buf[off:, :row] = t.reshape(n, row).cuda()
-    view = buf[off:, :row].view(src.shape)                  # a view: raises if it would have to copy
-    assert view.data_ptr() == buf.data_ptr() + off * width * 4
-    return buf, view
-
-
-def _logical(buf, view):
-    n, row = view.shape[0], view[0].numel()
-    return buf[buf.shape[0] - n:, :row]
-
-
-def _state(c, gate_on):
-    ops = _ops()
-    st = ops.new_step_state()
-    # rampup 0: cons_weight = (float)consistency, the same fp32 value as the float argument
-    ops.step_init(st, 1, c["it"], 0.01, MAX_IT, 0.99, W, 0.0, 150, 0 if gate_on else c["it"] + 1000)
-    s = ops.read_step_state(st)
-    assert s["cons_gate"] == (1.0 if gate_on else 0.0) and s["iter_num"] == c["it"]
-    return st
+_place = functools.partial(kit.place_rows, pad=PAD)      # (buffer, 5-D view) of a CPU tensor [n, C, D, H, W], or of NaNs
 
 
 GRAD_OF = {"dct": ("s", "r")}
@@ -306,14 +240,6 @@ def _launch(tail, c, x, layout, wmode, with_grad=True):
     return out, grads
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # the check
 # ---------------------------------------------------------------------------------------------------------------------
@@ -329,26 +255,23 @@ def _check(tail, c):
     # every element written once and nothing else: results finite, padding / tail of out still NaN
     assert torch.isfinite(out[:n_out]).all() and torch.isnan(out[n_out:]).all(), out
     for buf, view in grads:
-        assert torch.isfinite(view).all()
-        rest = buf.clone()
-        _logical(rest, view).fill_(NAN)
-        assert torch.isnan(rest).all()
+        assert torch.isfinite(view).all() and kit.untouched_outside(buf, view)
     # bit-reproducible
     out2, grads2 = _launch(tail, c, x, c["layout"], c["wmode"])
-    assert _same_bits(out, out2) and all(_same_bits(a[0], b[0]) for a, b in zip(grads, grads2))
+    assert kit.same_bits(out, out2) and all(kit.same_bits(a[0], b[0]) for a, b in zip(grads, grads2))
     # forward only: the same scalars
     out3, _ = _launch(tail, c, x, c["layout"], c["wmode"], with_grad=False)
-    assert _same_bits(out, out3)
+    assert kit.same_bits(out, out3)
     # only addresses differ between a strided / offset view and the dense tensor
     if c["layout"] != "dense":
         outd, gradsd = _launch(tail, c, x, "dense", c["wmode"])
-        assert _same_bits(out, outd) and all(torch.equal(a[1], b[1]) for a, b in zip(grads, gradsd))
+        assert kit.same_bits(out, outd) and all(torch.equal(a[1], b[1]) for a, b in zip(grads, gradsd))
     # the weight from the device state == the weight from the float argument
     if c["wmode"] != "float" and gate == 1.0:
         outf, gradsf = _launch(tail, c, x, c["layout"], "float")
-        assert _same_bits(out, outf) and all(_same_bits(a[0], b[0]) for a, b in zip(grads, gradsf))
+        assert kit.same_bits(out, outf) and all(kit.same_bits(a[0], b[0]) for a, b in zip(grads, gradsf))
     o = out.cpu()
-    assert _same_bits(o[4], torch.tensor(W, dtype=torch.float32))
+    assert kit.same_bits(o[4], torch.tensor(W, dtype=torch.float32))
     if gate == 0.0:
         assert o[3].item() == 0.0
         for (buf, view), rows in zip(grads, (slice(L, None), slice(None))):       # dct: dA[L:] and all of dR
@@ -370,7 +293,7 @@ def _check(tail, c):
         elif c["content"] != "sat":
             assert 0 < o64[5 + C].item() <= total
     cid = _cid(c)
-    bad = []
+    gate = kit.Gate(K, FLOOR, stats=STATS)
     for i in range(n_out):
         hip, ref = o[i].double().item(), o64[i].item()
         if i in exact:
@@ -380,21 +303,17 @@ def _check(tail, c):
             assert hip == 0.0, (i, hip)
             continue
         e32, ehip = abs(o32[i].item() - ref) / abs(ref), abs(hip - ref) / abs(ref)
-        STATS.append((tail, cid, "scalar", e32, ehip))
+        gate.judge(cid, f"out[{i}]", "scalar", "max", e32, ehip, row=(tail, cid, "scalar", e32, ehip), extra=(hip, ref))
         print(f"[{tail} {cid}] out[{i}] f64 {ref:.9e} hip {hip:.9e} e32 {e32:.2e} hip {ehip:.2e}")
-        if ehip > max(K * e32, FLOOR_SCALAR):
-            bad.append(("out", i, hip, ref, e32, ehip))
     for (buf, view), ref, r32 in zip(grads, g64, g32):
         got = view.cpu().double()
         if ref.abs().max().item() == 0.0:
             assert (got == 0).all()
             continue
-        e32, ehip = _rel(r32, ref), _rel(got, ref)
-        STATS.append((tail, cid, "tensor", e32, ehip))
+        e32, ehip = kit.rel(r32, ref), kit.rel(got, ref)
+        gate.judge(cid, "grad", "tensor", "max", e32, ehip, row=(tail, cid, "tensor", e32, ehip), extra=(tuple(ref.shape),))
         print(f"[{tail} {cid}] grad |f64|max {ref.abs().max().item():.3e} e32 {e32:.2e} hip {ehip:.2e}")
-        if ehip > max(K * e32, FLOOR_TENSOR):
-            bad.append(("grad", tuple(ref.shape), e32, ehip))
-    assert not bad, bad
+    gate.done(cid)
     return x, out, grads, o64, g64
 
 
@@ -408,7 +327,7 @@ def test_cross_teaching_tail(c):
     x, out, grads, o64, g64 = _check("cross", c)
     if c["wmode"] == "state0":                  # the cross tails take the weight only: the gate changes nothing
         out1, grads1 = _launch("cross", c, x, c["layout"], "state1")
-        assert _same_bits(out, out1) and _same_bits(grads[0][0], grads1[0][0])
+        assert kit.same_bits(out, out1) and kit.same_bits(grads[0][0], grads1[0][0])
 
 
 @pytest.mark.parametrize("c", _matrix("cross_ce"))
@@ -450,7 +369,7 @@ def test_uamt_tail(c):
         assert out[3].item() == 0.0 and (got == 0).all()
     if c["wmode"] == "state0":                  # UA-MT takes weight and iteration from the state, not the gate
         out1, grads1 = _launch("uamt", c, x, c["layout"], "state1")
-        assert _same_bits(out, out1) and _same_bits(grads[0][0], grads1[0][0])
+        assert kit.same_bits(out, out1) and kit.same_bits(grads[0][0], grads1[0][0])
 
 
 @pytest.mark.parametrize("c", _matrix("ict"))
@@ -580,13 +499,13 @@ def test_softmax_mean_accumulate(C, U, R):
         abuf, aview, a64, a32 = _accumulate(C, U, R, sp, layout, g)
         assert torch.isfinite(aview).all()
         rest = abuf.clone()
-        _logical(rest, aview).fill_(NAN)
+        kit.logical(rest, aview).fill_(NAN)
         assert torch.isnan(rest).all()                      # the first call overwrites NaNs; the padding is untouched
         results[layout] = aview.cpu()
-        e32, ehip = _rel(a32, a64), _rel(results[layout].double(), a64)
+        e32, ehip = kit.rel(a32, a64), kit.rel(results[layout].double(), a64)
         STATS.append(("sma", f"C{C}-U{U}-R{R}-{layout}", "tensor", e32, ehip))
         print(f"[sma C{C} U{U} R{R} {layout}] e32 {e32:.2e} hip {ehip:.2e}")
-        assert ehip <= max(K * e32, FLOOR_TENSOR), (layout, e32, ehip)
+        assert ehip <= max(K * e32, FLOOR["tensor"]), (layout, e32, ehip)
     assert torch.equal(results["dense"], results["strided"]) and torch.equal(results["dense"], results["offset"])
 
 
@@ -624,7 +543,7 @@ def test_mean_prediction_chained_into_uamt_tail(C, it):
     assert o[5 + C].item() == float(keep.sum()) == o64[5 + C].item()
     for i in (0, 1, 2, 3):
         e32, ehip = abs(o32[i].item() - o64[i].item()) / abs(o64[i].item()), abs(o[i].item() - o64[i].item()) / abs(o64[i].item())
-        assert ehip <= max(K * e32, FLOOR_SCALAR), (i, e32, ehip)
-    e32, ehip = _rel(g32.double(), g64), _rel(dview.cpu().double(), g64)
-    assert ehip <= max(K * e32, FLOOR_TENSOR), (e32, ehip)
+        assert ehip <= max(K * e32, FLOOR["scalar"]), (i, e32, ehip)
+    e32, ehip = kit.rel(g32.double(), g64), kit.rel(dview.cpu().double(), g64)
+    assert ehip <= max(K * e32, FLOOR["tensor"]), (e32, ehip)
     assert (dview[L:].cpu()[~keep.unsqueeze(1).expand(-1, C, -1, -1, -1)] == 0).all()

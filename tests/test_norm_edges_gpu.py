@@ -87,24 +87,24 @@ fp32 noise).  rstd is the worst group relative to its own value; y and dgamma ar
     pass.  After, all eighteen pass.  The finalize path (fp32 partials by contract) measures rstd 2.6e-6 at mean/std 32 under
     its factor of 1025.
 """
-import json
-import os
+import functools
 
 import pytest
 import torch
 
 import norm_oracle as no
+import oracle_kit as kit
+from oracle_kit import NAN, SENT
 
 pytestmark = pytest.mark.gpu
 
-K = 6.0
-FLOOR = {"stat": 1.2e-7,      # largest e32 of mean / rstd / running statistics: 1.11e-7 (running_mean, bn-ratio0)
+K = no.K
+FLOOR = {"stat": no.FLOOR_STAT,     # largest e32 of mean / rstd / running statistics: 1.11e-7 (running_mean, bn-ratio0)
          "act": 6.1e-7,       # of y / pooled: 6.02e-7 (in-np257-ratio32: mean / std 32)
          "dx": 2.6e-7,        # of dx / dr: 2.54e-7 (in-S4-N1-C2)
          "sum": 5.8e-6}       # of dgamma / dbeta / group sums / channel sums: 5.70e-6 (dbeta of bn-pre)
-NAN = float("nan")
-SENT = -777.0
 LEAD, TRAIL = 1, 2            # channels of the wider buffer before / after a slice
+_in, _out = functools.partial(kit.place, lead=LEAD, trail=TRAIL), functools.partial(kit.Out, lead=LEAD, trail=TRAIL)
 STATS = []
 
 
@@ -113,106 +113,48 @@ def _ops():
     return ops
 
 
-def finalize_factor(mean64, var64):
-    """Conditioning of one-pass statistics from fp32 partials (module docstring): the factor rstd and running_var get per
-    group in mis_norm_stats_finalize's tests (tests/test_conv_edges_gpu.py holds the split Winograd forward's to it too)."""
-    return 1.0 + mean64 ** 2 / (var64 + no.EPS)
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
     if not STATS:
         return
-    rows = {}
-    for test, cid, key, e32, ehip, factor in STATS:
-        r = rows.setdefault((test, key), dict(lo=1e9, hi=0.0, ratio=0.0, hip=0.0, at=""))
-        r["lo"], r["hi"], r["hip"] = min(r["lo"], e32), max(r["hi"], e32), max(r["hip"], ehip)
-        ratio = ehip / (max(e32, FLOOR[no.KIND_OF[key]] / K) * factor)
-        if ratio > r["ratio"]:
-            r["ratio"], r["at"] = ratio, cid
-    for (test, key), r in sorted(rows.items()):
+    for (test, key), r in kit.worst_rows(((test, key), cid, e32, ehip, max(e32, FLOOR[no.KIND_OF[key]] / K) * factor)
+                                         for test, cid, key, e32, ehip, factor in STATS):
         print(f"\n[norm edges] {test:12s} {key:8s} e32 {r['lo']:.2e} .. {r['hi']:.2e}  hip max {r['hip']:.2e}  "
               f"worst hip/max(e32, floor/K) {r['ratio']:.2f} ({r['at']})", end="")
     print()
-    path = os.environ.get("MIS_NORM_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump(STATS, f)
+    kit.report(STATS, "MIS_NORM_STATS")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # placement and comparison
 # ---------------------------------------------------------------------------------------------------------------------
-def _in(t, layout):
-    """Device copy of an input [N, C, ...]: dense, or the channel slice of a wider NaN-filled buffer."""
-    if t is None:
-        return None
-    if layout == "dense":
-        return t.cuda()
-    N, C = t.shape[:2]
-    buf = torch.full((N, LEAD + C + TRAIL) + tuple(t.shape[2:]), NAN, device="cuda")
-    v = buf[:, LEAD:LEAD + C]
-    v.copy_(t.cuda())
-    assert v.data_ptr() == buf.data_ptr() + LEAD * t[0, 0].numel() * 4
-    return v
-
-
-class _Out:
-    """A NaN-filled output [N, C, ...]: dense, or the channel slice of a wider sentinel-filled buffer."""
-
-    def __init__(self, shape, layout, fill=None):
-        N, C = shape[:2]
-        if layout == "dense":
-            self.buf = None
-            self.v = torch.full(tuple(shape), NAN, device="cuda")
-        else:
-            self.buf = torch.full((N, LEAD + C + TRAIL) + tuple(shape[2:]), SENT, device="cuda")
-            self.v = self.buf[:, LEAD:LEAD + C]
-            self.v.fill_(NAN)
-        if fill is not None:
-            self.v.copy_(fill.cuda())
-
-    def untouched(self):
-        C = self.v.shape[1]
-        return self.buf is None or bool((self.buf[:, :LEAD] == SENT).all() and (self.buf[:, LEAD + C:] == SENT).all())
-
-
-def _nanvec(n):
-    return torch.full((n,), NAN, device="cuda")
-
-
 class _Check:
     def __init__(self, test, name):
         self.test, self.name = test, name
         self.r64, _, self.e32 = no.references(name) if name in no.SPECS else ({}, None, {})
-        self.bad = []
+        self.gate = kit.Gate(K, FLOOR, stats=STATS)
 
     def __call__(self, key, got, ref=None, e32=None, factor=None):
         ref = self.r64[key] if ref is None else ref
         e32 = self.e32[key] if e32 is None else e32
         got = got.detach().cpu().double().reshape(ref.shape)
-        assert torch.isfinite(got).all(), (self.name, key, "not finite")
-        assert (got[ref == 0] == 0).all(), (self.name, key, "a reference of exactly 0 is not met")
+        self.gate.finite(got, (self.name, key))
+        self.gate.zero_ok((got[ref == 0] == 0).all(), (self.name, key))
         scale = ref.abs() if key in no.EACH else ref.abs().max()     # rstd / running_var: each group on its own scale
-        tol = max(K * e32, FLOOR[no.KIND_OF[key]])
         err = (got - ref).abs()
         ehip = (err / scale).max().item() if scale.max().item() > 0 else 0.0
-        fmax = 1.0
+        fmax, ok = 1.0, None
         if factor is not None:                      # per-group conditioning factor (mis_norm_stats_finalize only)
             assert key in no.EACH
             fmax = factor.max().item()
-            ok = bool((err <= tol * factor * scale).all())
-        else:
-            ok = ehip <= tol
-        scale = scale.max().item()
-        STATS.append((self.test, self.name, key, e32, ehip, fmax))
-        print(f"[{self.test} {self.name}] {key:8s} |f64|max {scale:.3e} e32 {e32:.2e} hip {ehip:.2e} tol {tol * fmax:.2e}")
-        if not ok:
-            self.bad.append((key, f"e32 {e32:.3e}", f"hip {ehip:.3e}", f"tol {tol * fmax:.3e}"))
+            ok = bool((err <= max(K * e32, FLOOR[no.KIND_OF[key]]) * factor * scale).all())
+        tol = self.gate.judge(self.name, key, no.KIND_OF[key], "max", e32, ehip, fmax, ok=ok,
+                              row=(self.test, self.name, key, e32, ehip, fmax))
+        print(f"[{self.test} {self.name}] {key:8s} |f64|max {scale.max().item():.3e} e32 {e32:.2e} hip {ehip:.2e} tol {tol:.2e}")
 
     def done(self):
-        assert not self.bad, (self.name, self.bad)
+        self.gate.done(self.name)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -227,7 +169,7 @@ def _hip_stats(c, xv, chk=None):
     if kind == "none":
         return torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
     G = C if kind == "bn" else N * C // cg
-    mean, rstd = _nanvec(G), _nanvec(G)
+    mean, rstd = kit.nan(G), kit.nan(G)
     if kind == "gn":
         ops.group_norm_stats(xv, cg, 1e-5, mean, rstd)
     elif c["rm"] is not None:
@@ -260,14 +202,14 @@ def _run(test, name, layout):
     gamma = None if c["gamma"] is None else c["gamma"].cuda()
     beta = None if c["beta"] is None else c["beta"].cuda()
     mask = None if c["mask"] is None else c["mask"].cuda()      # the explicit mask stays contiguous
-    y = _Out(shape, layout)
+    y = _out(shape, layout)
     rv = _in(c["r"], layout)
     post = c["res"] == "post"
     pooled = idx = None
     if c["r"] is not None:
         ops.norm_res_act_fwd(xv, rv, y.v, per_sample, mean, rstd, gamma, beta, slope, post=post)
     elif c["dpool"] is not None:
-        pooled = _Out(tuple(c["dpool"].shape), layout)
+        pooled = _out(tuple(c["dpool"].shape), layout)
         idx = torch.full((c["dpool"].numel(),), 255, dtype=torch.uint8, device="cuda")
         ops.norm_act_fwd_pool(xv, y.v, pooled.v, idx, per_sample, mean, rstd, gamma, beta, slope, drop_p=p, drop_mask=mask)
     else:
@@ -281,12 +223,12 @@ def _run(test, name, layout):
         assert not (differ & ~r64["near"]).any(), (name, "argmax codes", int(differ.sum()))
 
     dav = _in(c["da"], layout)
-    dx = _Out(shape, layout)
+    dx = _out(shape, layout)
     dg = db = None
     if gamma is not None:
-        dg, db = _nanvec(C), _nanvec(C)
+        dg, db = kit.nan(C), kit.nan(C)
     if c["r"] is not None:
-        dr = _Out(shape, layout)
+        dr = _out(shape, layout)
         ops.norm_res_act_bwd(xv, rv, dav, dx.v, dr.v, False, per_sample, mean, rstd, gamma, beta, slope, dgamma=dg, dbeta=db,
                              post=post)
         chk("dr", dr.v)
@@ -308,7 +250,6 @@ def _run(test, name, layout):
     if dg is not None:
         chk("dgamma", dg)
         chk("dbeta", db)
-    torch.cuda.synchronize()
     chk.done()
     return c, xv, dav, mean, rstd, gamma, beta, mask, dg, db
 
@@ -355,16 +296,16 @@ def test_every_operand_a_channel_slice(name):
     per_sample = c["kind"] != "bn"
     shape = tuple(c["x"].shape)
     assert xv.stride(0) != shape[1] * xv[0, 0].numel() and xv.data_ptr() % 16 == 0
-    y1, y2 = _Out(shape, "slice"), _Out(shape, "dense")
+    y1, y2 = _out(shape, "slice"), _out(shape, "dense")
     for xin, y in ((xv, y1), (c["x"].cuda(), y2)):
         ops.norm_act_fwd(xin, y.v, per_sample, mean, rstd, gamma, beta, c["slope"], drop_p=c["drop_p"], drop_mask=mask,
                          cg=c["cg"])
     assert torch.equal(y1.v, y2.v)
-    d2 = _Out(shape, "dense")
-    dg2, db2 = (None, None) if gamma is None else (_nanvec(shape[1]), _nanvec(shape[1]))
+    d2 = _out(shape, "dense")
+    dg2, db2 = (None, None) if gamma is None else (kit.nan(shape[1]), kit.nan(shape[1]))
     ops.norm_act_bwd(c["x"].cuda(), c["da"].cuda(), d2.v, per_sample, mean, rstd, gamma, beta, c["slope"], drop_p=c["drop_p"],
                      drop_mask=mask, dgamma=dg2, dbeta=db2, cg=c["cg"])
-    d1 = _Out(shape, "slice")
+    d1 = _out(shape, "slice")
     ops.norm_act_bwd(xv, dav, d1.v, per_sample, mean, rstd, gamma, beta, c["slope"], drop_p=c["drop_p"], drop_mask=mask,
                      dgamma=dg, dbeta=db, cg=c["cg"])
     assert torch.equal(d1.v, d2.v) and d1.untouched()
@@ -381,7 +322,7 @@ def test_batchnorm_bookkeeping(name):
     C = c["x"].shape[1]
     g0, b0 = torch.linspace(-3.0, 5.0, C, device="cuda"), torch.linspace(7.0, -2.0, C, device="cuda")
     ag, ab = g0.clone(), b0.clone()
-    dx = _Out(tuple(c["x"].shape), "dense")
+    dx = _out(tuple(c["x"].shape), "dense")
     ops.norm_act_bwd(xv, dav, dx.v, False, mean, rstd, gamma, beta, c["slope"], dgamma=ag, dbeta=ab, accumulate_affine=True)
     assert torch.equal(ag, g0 + dg) and torch.equal(ab, b0 + db)
     assert not torch.equal(ag, dg)
@@ -416,7 +357,7 @@ def test_backward_sums(name):
     sums = torch.full((G, 2), NAN, device="cuda")
     gamma = None if per_sample else c["gamma"].cuda()
     beta = None if per_sample else c["beta"].cuda()
-    dg, db = (None, None) if per_sample else (_nanvec(C), _nanvec(C))
+    dg, db = (None, None) if per_sample else (kit.nan(C), kit.nan(C))
     ops.norm_act_bwd_sums(xv, dav, per_sample, mean, rstd, gamma, beta, c["slope"], sums, dgamma=dg, dbeta=db)
     chk("s1", sums[:, 0])
     chk("s2", sums[:, 1])
@@ -443,8 +384,8 @@ def test_stats_finalize(name):
     per_sample = c["kind"] == "in"
     part = no.tile_partials(c["x"], T, per_sample).cuda()
     G = N * C if per_sample else C
-    mean, rstd = _nanvec(G), _nanvec(G)
-    factor = finalize_factor(r64["mean"], r64["var"])
+    mean, rstd = kit.nan(G), kit.nan(G)
+    factor = no.finalize_factor(r64["mean"], r64["var"])
     if c["ratio"] == 0 and no.group_elems(c["x"].shape, c["kind"]) >= 2000:     # (a group of 8 .. 520 values has a sample mean)
         assert factor.max().item() < 1.01
     if per_sample:
@@ -472,10 +413,10 @@ def test_channel_sum(N, S):
     ref, r32 = no.channel_sum(x, torch.float64), no.channel_sum(x, torch.float32)
     chk = _Check("channel_sum", f"csum-N{N}-S{S}")
     xv = _in(x, "slice")
-    out = _nanvec(x.shape[1])
+    out = kit.nan(x.shape[1])
     ops.channel_sum(xv, out)
     chk("csum", out, ref, no.rel(r32, ref))
-    dense = _nanvec(x.shape[1])
+    dense = kit.nan(x.shape[1])
     ops.channel_sum(x.cuda(), dense)
     assert torch.equal(out, dense)
     acc0 = torch.linspace(-40.0, 90.0, x.shape[1], device="cuda")
@@ -513,7 +454,7 @@ def _operands(shape, misaligned=False):
     else:
         x = torch.full(shape, 0.5, device="cuda")
     outs = [torch.full(shape, NAN, device="cuda") for _ in range(2)]
-    stat = [_nanvec(N * C) for _ in range(4)]
+    stat = [kit.nan(N * C) for _ in range(4)]
     return x, outs, stat
 
 

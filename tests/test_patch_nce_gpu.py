@@ -46,20 +46,19 @@ Measured on an MI355X (this file's own run; `MIS_PATCH_NCE_STATS=<file>` writes 
     147 tests, 546 compared quantities, 7 s wall.
 """
 import functools
-import json
-import os
 import zlib
 
 import pytest
 import torch
 
+import oracle_kit as kit
 import patch_nce_oracle as pno
 
 pytestmark = pytest.mark.gpu
 
 K = 6.0
-FLOOR_SCALAR = {"loss": 2.0e-7, "mean_sii": 1.9e-4, "mean_lse": 3.0e-7}      # largest e32 of each kind over the matrix
-FLOOR_TENSOR = 1.2e-6                                                        # largest tensor e32: 1.15e-6
+FLOOR = {"loss": 2.0e-7, "mean_sii": 1.9e-4, "mean_lse": 3.0e-7,      # largest e32 of each scalar over the matrix
+         "grad": 1.2e-6}                                              # largest tensor e32: 1.15e-6
 
 NS = (1, 2, 15, 16, 17, 63, 100, 784, 1040, 3136)
 CONTENTS = ("signed", "relu", "zero_q", "zero_k", "zero_sample", "onehot", "same", "x1e3", "x1e-3")
@@ -85,10 +84,7 @@ def _report():
         print(f"\n[patch_nce] {kind:6s} e32 {min(e32s):.2e} .. {max(e32s):.2e}  hip max {max(s[3] for s in rows):.2e}  "
               f"worst hip/e32 {worst[3] / worst[2] if worst[2] > 0 else 0.0:.2f} ({worst[0]}: e32 {worst[2]:.2e})", end="")
     print()
-    path = os.environ.get("MIS_PATCH_NCE_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump(STATS, f)
+    kit.report(STATS, "MIS_PATCH_NCE_STATS")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -174,24 +170,19 @@ def _check(cid, out, grad, ref, scalars=("loss", "mean_sii", "mean_lse")):
     """The arbiter, on host copies of the kernel's results; ``out`` holds the named scalars in the kernel's order."""
     _, _, out64, g64, e32s, e32g = ref
     out, grad = out.cpu(), grad.cpu()
-    fails = []
+    gate = kit.Gate(K, FLOOR, stats=STATS)
     for i, name in enumerate(scalars):
         want, got = out64[i].item(), float(out[i])
         err = abs(got - want) / abs(want) if want != 0 else (0.0 if got == 0 else float("inf"))
-        STATS.append((cid + ":" + name, "scalar", e32s[i], err))
+        gate.judge(cid, name, name, "max", e32s[i], err, row=(cid + ":" + name, "scalar", e32s[i], err))
         print(f"{cid} {name}: f64 {want:.9g} hip {got:.9g} err {err:.3e} e32 {e32s[i]:.3e}")
-        if not err <= max(K * e32s[i], FLOOR_SCALAR[name]):
-            fails.append((name, err, e32s[i]))
     errg = _rel(grad, g64)
-    STATS.append((cid + ":grad", "tensor", e32g, errg))
+    gate.judge(cid, "grad", "grad", "max", e32g, errg, row=(cid + ":grad", "tensor", e32g, errg))
     print(f"{cid} grad: |f64|max {g64.abs().max().item():.6g} err {errg:.3e} e32 {e32g:.3e}")
-    if not errg <= max(K * e32g, FLOOR_TENSOR):
-        fails.append(("grad", errg, e32g))
     rows0 = (g64 == 0).all(dim=1, keepdim=True).expand_as(g64)      # pixels the formula gives no gradient at all
     nz = int(torch.count_nonzero(grad[rows0]))
-    if nz:
-        fails.append(("gradient elements of pixels that must be exactly 0", nz))
-    assert not fails, (cid, fails)
+    assert not nz, (cid, "gradient elements of pixels that must be exactly 0", nz)
+    gate.done(cid)
 
 
 POISON = float("nan")

@@ -16,8 +16,8 @@ import pytest
 import torch
 
 import pnet_oracle as po
-import test_norm_edges_gpu as ne
-from test_parity_gpu import F64_ABS, F64_K, F64_LOGIT, F64_MEDIAN_RATIO, F64_REL
+import norm_oracle as no
+from net_gate import F64_LOGIT, check_grads as _check_grads
 
 pytestmark = pytest.mark.gpu
 
@@ -41,28 +41,6 @@ def _model(z):
     return m
 
 
-def _check_grads(model, ref, e32, label):
-    """the per-tensor rule and the median ratio; ``ref`` / ``e32``: {parameter: float64 gradient / the reference's fp32 noise}"""
-    hip = {n: g.cpu().double() for n, g in model.named_flat(model.flat_grad)}
-    assert set(hip) == set(ref)
-    gscale = max(float(g.abs().max()) for g in ref.values())
-    ratios, worst, rel = [], (0.0, ""), (0.0, "")
-    for n, g in ref.items():
-        assert torch.isfinite(hip[n]).all(), n
-        gmax = float(g.abs().max())
-        err = float((hip[n] - g).abs().max())
-        tol = max(F64_K * e32[n], F64_REL) * gmax + F64_ABS * gscale
-        worst = max(worst, (err / tol, n))
-        if gmax > 1e-4 * gscale:            # test_parity_gpu.py's ratio, with its 1e-3 lower bound on e32
-            ratios.append((err / gmax) / max(e32[n], 1e-3))
-            rel = max(rel, (err / gmax, n))
-    print(f"[pnet {label}] worst gradient error / tolerance {worst[0]:.2e} at {worst[1]}; largest relative error {rel[0]:.2e} at "
-          f"{rel[1]} (reference fp32: {e32[rel[1]]:.2e}); HIP error / max(e32, 1e-3): median {np.median(ratios):.2e}, "
-          f"max {max(ratios):.2e}")
-    assert worst[0] <= 1.0, worst
-    assert np.median(ratios) <= F64_MEDIAN_RATIO, np.median(ratios)
-
-
 def test_train_mode_forward_backward_and_eval_forward_match_the_reference(gold):
     m = _model(gold)
     m.train()
@@ -82,14 +60,14 @@ def test_train_mode_forward_backward_and_eval_forward_match_the_reference(gold):
     m.backward_raw(dl.unsqueeze(2).contiguous())
     torch.cuda.synchronize()
     params = [str(k) for k in gold["keys"] if po.is_param(str(k))]
-    _check_grads(m, {k: torch.from_numpy(gold[f"grad/{k}"]) for k in params}, {k: float(gold[f"e32/{k}"]) for k in params}, "golden")
+    _check_grads(m, {k: torch.from_numpy(gold[f"grad/{k}"]) for k in params}, {k: float(gold[f"e32/{k}"]) for k in params}, "pnet golden")
     sd = m.state_dict()
     for k in (str(k) for k in gold["keys"] if not po.is_param(str(k))):
         ref = torch.from_numpy(gold[f"after/{k}"])
         if k.endswith("num_batches_tracked"):
             assert int(sd[k]) == int(ref) == 1
             continue
-        tol = max(ne.K * float(gold[f"e32_after/{k}"]), ne.FLOOR["stat"])
+        tol = max(no.K * float(gold[f"e32_after/{k}"]), no.FLOOR_STAT)
         e = float((sd[k].cpu().double() - ref).abs().max() / ref.abs().max())
         assert e <= tol, (k, e, tol)
     m.eval()
@@ -147,7 +125,7 @@ def test_fixed_channel_dropout_masks_match_the_oracle(gold):
     assert err <= F64_LOGIT, err
     # e32 of the masked pass is not in the golden: the p = 0 pass's (same layers, same tensors) stands in
     params = [str(k) for k in gold["keys"] if po.is_param(str(k))]
-    _check_grads(m, r["grads"], {k: float(gold[f"e32/{k}"]) for k in params}, "masks")
+    _check_grads(m, r["grads"], {k: float(gold[f"e32/{k}"]) for k in params}, "pnet masks")
 
 
 def test_philox_dropout_zeroes_or_scales_whole_feature_maps(gold):

@@ -174,14 +174,14 @@ products lose one third-order piece (a.h * b.l, in gemm_nt_kernel<.., 1 / 2, ..>
 kernels and gemm_tn_reg_kernel<1>) fails all 56 bf16x3 cases here (planes-777x576x192/act_scaled C: 2.21e-5 against a gate of
 3.4e-6, 6.4e-7 with the real library) and none of the 90 others, and passes all 165 tests of tests/test_token_kernels_gpu.py.
 """
-import ctypes
-import json
-import os
+import functools
 
 import pytest
 import torch
 
+import oracle_kit as kit
 import token_oracle as to
+from oracle_kit import NAN, nan as _nan
 
 pytestmark = pytest.mark.gpu
 
@@ -198,9 +198,9 @@ GELU_TAIL = 1.0e-5 + 9e-7 + GELU_TAIL_POLY
 # {case: {(label, measure)}}: tensors known to sit over the gate, by name, each with its measured figure in a comment.  Strict
 # and narrow as in tests/test_conv_edges_gpu.py: the case xfails only when exactly these entries are over the gate.
 OVER_THE_GATE = {}
-NAN = float("nan")
-SENT = -777.0
 LEAD, TRAIL = 4, 8            # columns of the wider buffer before / after a slice (16-byte aligned, row strides % 4 == 0)
+_name = functools.partial(kit.kernel_name, size=96)
+_in, _out = functools.partial(kit.place, lead=LEAD, trail=TRAIL), functools.partial(kit.Out, lead=LEAD, trail=TRAIL)
 STATS = []                    # (group, case, label, kind, measure, e32, hip, kernel)
 
 # the kernel of every GEMM case (plain epilogue), as the library's queries print it; %d = 0 under mask 0, 1 under mask 7
@@ -232,13 +232,6 @@ def _L():
     return lib.load()
 
 
-def _name(query, *args):
-    buf = ctypes.create_string_buffer(96)
-    st = getattr(_L(), query)(*args, buf, 96)
-    assert st == 0, (query, args, st)
-    return buf.value.decode()
-
-
 def report_rows(stats):
     """One row per (kernel, kind): e32 range (max measure), HIP max / rms and their ratios to max(e32, FLOOR / K), worst case."""
     rows = {}
@@ -267,77 +260,25 @@ def _report():
     if not STATS:
         return
     _print_report()
-    path = os.environ.get("MIS_TOKEN_STATS")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"stats": STATS}, f)
+    kit.report(STATS, "MIS_TOKEN_STATS", {"stats": STATS})
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # buffers and comparison
 # ---------------------------------------------------------------------------------------------------------------------
-def _in(t, layout, lead=LEAD, trail=TRAIL, rows_behind=0):
-    """Device copy of a [rows][cols] input: dense, or a column slice of a wider NaN-filled buffer (``rows_behind``: NaN rows
-    behind the last one in the same allocation)."""
-    if layout == "dense" and not rows_behind:
-        return t.cuda()
-    if layout == "dense":
-        lead = trail = 0
-    buf = torch.full((t.shape[0] + rows_behind, lead + t.shape[1] + trail), NAN, device="cuda")
-    v = buf[:t.shape[0], lead:lead + t.shape[1]]
-    v.copy_(t.cuda())
-    return v
-
-
-class _Out:
-    """A NaN-filled [rows][cols] output: dense, or a column slice of a wider sentinel-filled buffer."""
-
-    def __init__(self, shape, layout, fill=None, lead=LEAD, trail=TRAIL):
-        self.lead = lead
-        if layout == "dense":
-            self.buf = None
-            self.v = torch.full(tuple(shape), NAN, device="cuda")
-        else:
-            self.buf = torch.full((shape[0], lead + shape[1] + trail), SENT, device="cuda")
-            self.v = self.buf[:, lead:lead + shape[1]]
-            self.v.fill_(NAN)
-        if fill is not None:
-            self.v.copy_(fill.cuda())
-
-    def untouched(self):
-        cols = self.v.shape[1]
-        return self.buf is None or bool((self.buf[:, :self.lead] == SENT).all() and (self.buf[:, self.lead + cols:] == SENT).all())
-
-
-def _nan(*shape):
-    return torch.full(shape, NAN, device="cuda")
-
-
 class _Check:
     def __init__(self, name):
         self.name = name
         self.c = to.case(name)
         self.group = self.c["group"]
         self.r64 = to.references(name)[0]
-        self.bad = []
+        self.gate = kit.Gate(K, FLOOR, OVER_THE_GATE, STATS)
 
     def __call__(self, key, got, kernel, label=None, ref=None):
         """``got`` against the float64 reference of tensor ``key`` (or ``ref``, held to ``key``'s yardstick)."""
-        label = label or key
-        kind = to.KIND_OF[key]
-        ref = self.r64[key] if ref is None else ref
-        got = got.detach().cpu().double().reshape(ref.shape)
-        assert torch.isfinite(got).all(), (self.name, label, "not finite")
-        m = to.measure_of(key, got, ref)
-        assert m["zero_ok"], (self.name, label, "a column whose reference is exactly 0 is not met exactly")
-        for ms in to.MEASURES:
-            e = to.yardstick(self.name, key, ms)
-            tol = max(K * e, FLOOR[kind])
-            STATS.append((self.group, self.name, label, kind, ms, e, m[ms], kernel))
-            print(f"[{self.name}] {label:12s} {ms:3s} e32 {e:.2e} hip {m[ms]:.2e} tol {tol:.2e}  {kernel}")
-            if not m[ms] <= tol:
-                self.bad.append((label, ms, f"e32 {e:.3e}", f"hip {m[ms]:.3e}", f"tol {tol:.3e}", kernel))
-        return m
+        return self.gate.tensor(self.name, label or key, to.KIND_OF[key], got, self.r64[key] if ref is None else ref,
+                                lambda g, r: to.measure_of(key, g, r), {ms: to.yardstick(self.name, key, ms) for ms in to.MEASURES},
+                                (self.group, self.name), (kernel,), width=12)
 
     def base(self, key):
         """A non-zero base of the tensor's own column scales for the accumulate forms (exactly-zero columns stay zero)."""
@@ -345,12 +286,7 @@ class _Check:
         return ((r.flip(1 if key in to.ROWS_ARE_COLUMNS else 0) if r.dim() == 2 else r) * 0.5).float()
 
     def done(self):
-        torch.cuda.synchronize()
-        known = OVER_THE_GATE.get(self.name)
-        if known:
-            assert {(b[0], b[1]) for b in self.bad} == known, (self.name, "expected over the gate", known, "found", self.bad)
-            pytest.xfail(f"{self.name}: {self.bad}")
-        assert not self.bad, (self.name, self.bad)
+        self.gate.done(self.name)
 
 
 def _layout(c):
@@ -416,12 +352,12 @@ def _run_nt(name, mode, arith):
         return tops._nt_split(A, b3, C, epilogue=ep, **kw)
 
     k0 = kname(0) + (" + gemm_reduce_kernel" if split else "")
-    C = _Out((M, N), lay)
+    C = _out((M, N), lay)
     gemm(C.v, bias=bias)
     chk("C", C.v, k0)
     assert C.untouched()
     base = chk.base("C")
-    acc = _Out((M, N), lay, fill=base)
+    acc = _out((M, N), lay, fill=base)
     gemm(acc.v, accumulate=True)
     chk("C", acc.v, k0, label="C +=", ref=base.double() + chk.r64["C"] - c["bias"].double())
     assert acc.untouched()
@@ -430,7 +366,7 @@ def _run_nt(name, mode, arith):
         kn = lambda ep: k0 if split else kname(ep)
         E1, sc = _in(c["E1"], lay), c["rowscale"].cuda()
         C.v.fill_(NAN)
-        C2 = _Out((M, N), lay)
+        C2 = _out((M, N), lay)
         assert gemm_ex(C.v, tops.EP_GELU_FWD, bias=bias, C2=C2.v)
         chk("C", C.v, kn(1), label="C (gelu)")
         chk("gelu", C2.v, kn(1))
@@ -495,7 +431,7 @@ def test_gemm_residual_layernorm_tail(name):
         kernel = _name("mis_gemm_nt_split_layout_kernel_name", M, N, Kc, 5, 1)
         assert kernel == NT_KERNEL[c["id"]]
         A, E1 = _in(c["A"], lay), _in(c["E1"], lay)
-        X, Y, mean, rstd = _Out((M, N), lay), _Out((M, N), lay), _nan(M), _nan(M)
+        X, Y, mean, rstd = _out((M, N), lay), _out((M, N), lay), _nan(M), _nan(M)
         assert tops.gemm_residual_ln(A, b3, X.v, E1, c["gamma"].cuda(), c["beta"].cuda(), Y.v, mean, rstd, bias=c["bias"].cuda(),
                                      rowscale=c["rowscale"].cuda(), rows_per_scale=c["rps"])
         for key, got in (("X", X.v), ("Y", Y.v), ("mean", mean), ("rstd", rstd)):
@@ -516,7 +452,7 @@ def _run_tn(name, mask, huge=None, rows_behind=0):
     lay = "dense" if rows_behind else _layout(c)
     X = _in(c["X"], lay, rows_behind=rows_behind)
     dY = huge if huge is not None else _in(c["dY"], lay, rows_behind=rows_behind)
-    dW, dW2 = _Out((Cout, Cin), lay), _Out((Cout, Cin), lay)
+    dW, dW2 = _out((Cout, Cin), lay), _out((Cout, Cin), lay)
     want = TN_KERNEL[c["id"]][1 if huge is not None else 0]
     kernel = tops._tn_name(_L(), dY, dY.stride(0), X, X.stride(0), dW.v, dW.v.stride(0), Cout, Cin, T)
     assert kernel == (want % (1 if mask & 2 else 0) if "%d" in want else want), (name, kernel)
@@ -535,7 +471,7 @@ def _run_tn(name, mask, huge=None, rows_behind=0):
     chk("dW", dW2.v, kernel, label="dW +=", ref=bW.double() + chk.r64["dW"])
     chk("db", db2, kernel, label="db +=", ref=bb.double() + chk.r64["db"])
     if huge is None:          # (mis_gemm refuses operands of 2^31 bytes: its NT kernels address them with 32-bit offsets)
-        plain = _Out((Cout, Cin), lay)
+        plain = _out((Cout, Cin), lay)
         tops.gemm(dY, X, plain.v, trans=True)
         assert torch.equal(plain.v, dW.v) and plain.untouched()
     assert dW.untouched() and dW2.untouched()
@@ -699,12 +635,12 @@ def test_layernorm(name):
     kf = f"ln_fwd_reg_kernel{tag}" if tag else "ln_fwd_kernel"
     kb = f"ln_bwd_reg_kernel{tag} + col_final_kernel" if tag else "ln_bwd_dx_kernel + col_partial_kernel + col_final_kernel"
     x, dy, g, b = _in(c["x"], lay), _in(c["dy"], lay), c["gamma"].cuda(), c["beta"].cuda()
-    y, mean, rstd = _Out((M, C), lay), _nan(M), _nan(M)
+    y, mean, rstd = _out((M, C), lay), _nan(M), _nan(M)
     tops.layernorm_fwd(x, y.v, g, b, mean, rstd)
     for key, got in (("y", y.v), ("mean", mean), ("rstd", rstd)):
         chk(key, got, kf)
     assert y.untouched()
-    dx, dx2 = _Out((M, C), lay), _Out((M, C), lay)
+    dx, dx2 = _out((M, C), lay), _out((M, C), lay)
     dg, db, dg2, db2 = _nan(C), _nan(C), _nan(C), _nan(C)
     tops.layernorm_bwd(x, dy, dx.v, g, mean, rstd, dg, db)
     for key, got in (("dx", dx.v), ("dgamma", dg), ("dbeta", db)):
@@ -722,13 +658,13 @@ def test_layernorm(name):
     chk("dbeta", db2, kb, label="dbeta +=", ref=bb.double() + chk.r64["dbeta"])
     # the two halves: bit-identical to the one-call form
     ws = tops.colreduce_workspace(M, C)
-    dx3, dg3, db3 = _Out((M, C), lay), _nan(C), _nan(C)
+    dx3, dg3, db3 = _out((M, C), lay), _nan(C), _nan(C)
     tops.layernorm_bwd_parts(x, dy, dx3.v, g, mean, rstd, ws)
     tops.layernorm_bwd_final(ws, M, C, dg3, db3)
     assert torch.equal(dx.v, dx3.v) and torch.equal(dg, dg3) and torch.equal(db, db3)
     assert dx.untouched() and dx2.untouched() and dx3.untouched()
     # with the residual add's backward in the same pass: d_shortcut = dx (+ base), d_branch = scale * dx
-    ds, dbr = _Out((M, C), lay, fill=bx), _Out((M, C), lay)
+    ds, dbr = _out((M, C), lay, fill=bx), _out((M, C), lay)
     rps = -(-M // 3)
     sc = torch.tensor([1.25, 0.0, 0.5])
     fused = tops.layernorm_bwd_residual_parts(x, dy, None, ds.v, dbr.v, g, mean, rstd, ws, rowscale=sc.cuda(), rows_per_scale=rps,
@@ -763,7 +699,7 @@ def test_layernorm_head(name):
     dl = c["dl"].cuda().view(B, NC, 1, 1, S)
     outs = []
     for _ in range(2):
-        dx, dg, db, dw = _Out((M, C), lay), _nan(C), _nan(C), _nan(NC, C)
+        dx, dg, db, dw = _out((M, C), lay), _nan(C), _nan(C), _nan(NC, C)
         tops.ln_head_bwd(x, g, b, w, mean, rstd, dl, dx.v, dg, db, dw)
         outs.append((dx, dg, db, dw))
     (dx, dg, db, dw), (dx2, dg2, db2, dw2) = outs
@@ -798,7 +734,7 @@ def test_output_head(name):
     tops.head_fwd(x, w, lg)
     chk("logits", lg, "head_fwd_kernel")
     dl = c["dl"].cuda().view(B, NC, 1, 14, 14)
-    dx, dw, dx2, dw2 = _Out((B * S, C), lay), _nan(NC, C), _Out((B * S, C), lay), _nan(NC, C)
+    dx, dw, dx2, dw2 = _out((B * S, C), lay), _nan(NC, C), _out((B * S, C), lay), _nan(NC, C)
     tops.head_bwd(x, w, dl, dx.v, dw)
     chk("dx", dx.v, "head_bwd_kernel")
     chk("dw", dw, "head_bwd_kernel")

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_dct_cpu import REF_FLAGS_VIT
+from dct_oracle import REF_FLAGS_VIT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")

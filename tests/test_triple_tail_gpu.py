@@ -32,12 +32,14 @@ import torch
 
 import loss_tail_oracle as lto
 import triple_oracle as tvo
-from test_loss_tails_gpu import (K, NAN, SHAPES, W, _logical, _place, _plant_ties, _rel, _same_bits, _state)
+import oracle_kit as kit
+from loss_tail_cases import K, PAD, SHAPES, W, plant_ties as _plant_ties, state as _state
+from oracle_kit import NAN
 
 pytestmark = pytest.mark.gpu
 
-FLOOR_SCALAR = 2.2e-7      # largest scalar e32 of the matrix: 2.10e-7
-FLOOR_TENSOR = 3.6e-7      # largest tensor e32 of the matrix: 3.57e-7
+FLOOR = {"scalar": 2.2e-7,      # largest scalar e32 of the matrix: 2.10e-7
+         "tensor": 3.6e-7}      # largest tensor e32 of the matrix: 3.57e-7
 N_OUT = 6
 STATS = []
 
@@ -50,14 +52,11 @@ def _ops():
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    for kind in ("scalar", "tensor"):
-        rows = [s for s in STATS if s[1] == kind]
-        if rows:
-            worst = max(rows, key=lambda s: s[3] / s[2] if s[2] > 0 else 0.0)
-            print(f"\n[triple tail] {kind:7s} e32 {min(s[2] for s in rows):.2e} .. {max(s[2] for s in rows):.2e}  hip max "
-                  f"{max(s[3] for s in rows):.2e}  worst hip/e32 {worst[3] / worst[2] if worst[2] > 0 else 0.0:.2f} "
-                  f"({worst[0]})", end="")
+    for kind, r in kit.worst_rows((kind, cid, e32, ehip, e32) for cid, kind, e32, ehip in STATS):
+        print(f"\n[triple tail] {kind:7s} e32 {r['lo']:.2e} .. {r['hi']:.2e}  hip max {r['hip']:.2e}  worst hip/e32 "
+              f"{r['ratio']:.2f} ({r['at']})", end="")
     print()
+    kit.report(STATS, "MIS_TRIPLE_TAIL_STATS")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -137,7 +136,7 @@ def _e32(c):
     o64, g64, o32, g32 = _references(c, x)
     es = max(abs(a[i].item() - r[i].item()) / abs(r[i].item())
              for a, r in zip(o32, o64) for i in (0, 1, 2, 3, 5) if r[i].item() != 0.0)
-    et = max(_rel(a, r) for a, r in zip(g32, g64))
+    et = max(kit.rel(a, r) for a, r in zip(g32, g64))
     return es, et
 
 
@@ -148,10 +147,10 @@ def _launch(c, x, layout, wmode, with_grad=True):
     """One call through mis_hip.ops with NaN-filled outs / dlogits / workspace; returns (outs, [(buffer, view)] * 3)."""
     ops = _ops()
     lay = [layout if m in c["which"] else "dense" for m in range(3)]
-    views = [_place(z, lay[m])[1] for m, z in enumerate(x["zs"])]
+    views = [kit.place_rows(z, lay[m], PAD)[1] for m, z in enumerate(x["zs"])]
     label = x["label"].cuda()
     outs = [torch.full((16,), NAN, device="cuda") for _ in range(3)]
-    grads = [_place(None, lay[m], like=x["zs"][m]) for m in range(3)] if with_grad else []
+    grads = [kit.place_rows(None, lay[m], PAD, like=x["zs"][m]) for m in range(3)] if with_grad else []
     ops.scratch(1, "tail").view(torch.float32).fill_(NAN)
     wkw = dict(cons_weight=W) if wmode == "float" else dict(state=_state(c, wmode == "state1"))
     ops.triple_view_tail(views[0], views[1], views[2], label, c["L"], outs,
@@ -161,8 +160,8 @@ def _launch(c, x, layout, wmode, with_grad=True):
 
 
 def _same(outs, grads, outs2, grads2):
-    return (all(_same_bits(a, b) for a, b in zip(outs, outs2)) and
-            all(_same_bits(a[0], b[0]) for a, b in zip(grads, grads2)))
+    return (all(kit.same_bits(a, b) for a, b in zip(outs, outs2)) and
+            all(kit.same_bits(a[0], b[0]) for a, b in zip(grads, grads2)))
 
 
 @pytest.mark.parametrize("c", _matrix())
@@ -175,51 +174,44 @@ def test_triple_view_tail(c):
     for out in outs:
         assert torch.isfinite(out[:N_OUT]).all() and torch.isnan(out[N_OUT:]).all(), out
     for buf, view in grads:
-        assert torch.isfinite(view).all()
-        rest = buf.clone()
-        _logical(rest, view).fill_(NAN)
-        assert torch.isnan(rest).all()
+        assert torch.isfinite(view).all() and kit.untouched_outside(buf, view)
     # bit-reproducible
     assert _same(outs, grads, *_launch(c, x, c["layout"], c["wmode"]))
     # forward only (dlogits=None): the same scalars
     outs3, _ = _launch(c, x, c["layout"], c["wmode"], with_grad=False)
-    assert all(_same_bits(a, b) for a, b in zip(outs, outs3))
+    assert all(kit.same_bits(a, b) for a, b in zip(outs, outs3))
     # only addresses differ between a strided / offset view and the dense tensor
     if c["layout"] != "dense":
         outsd, gradsd = _launch(c, x, "dense", c["wmode"])
-        assert all(_same_bits(a, b) for a, b in zip(outs, outsd))
+        assert all(kit.same_bits(a, b) for a, b in zip(outs, outsd))
         assert all(torch.equal(a[1], b[1]) for a, b in zip(grads, gradsd))
     # the weight from the device state == the weight from the float argument; there is no gate
     if c["wmode"] != "float":
         assert _same(outs, grads, *_launch(c, x, c["layout"], "float"))
     cid = _cid(c)
     w32 = torch.tensor(W, dtype=torch.float32)
-    bad = []
+    gate = kit.Gate(K, FLOOR, stats=STATS)
     for m in range(3):
         o = outs[m].cpu()
-        assert _same_bits(o[4], w32)
+        assert kit.same_bits(o[4], w32)
         for i in (0, 1, 2, 3, 5):
             hip, ref = o[i].double().item(), o64[m][i].item()
             if ref == 0.0:
                 assert hip == 0.0, (m, i, hip)
                 continue
             e32, ehip = abs(o32[m][i].item() - ref) / abs(ref), abs(hip - ref) / abs(ref)
-            STATS.append((cid, "scalar", e32, ehip))
+            gate.judge(cid, f"out{m + 1}[{i}]", "scalar", "max", e32, ehip, row=(cid, "scalar", e32, ehip), extra=(hip, ref))
             print(f"[triple {cid}] out{m + 1}[{i}] f64 {ref:.9e} hip {hip:.9e} e32 {e32:.2e} hip {ehip:.2e}")
-            if ehip > max(K * e32, FLOOR_SCALAR):
-                bad.append(("out", m, i, hip, ref, e32, ehip))
         got, ref = grads[m][1].cpu().double(), g64[m]
         assert ref.abs().max().item() > 0
-        e32, ehip = _rel(g32[m], ref), _rel(got, ref)
-        STATS.append((cid, "tensor", e32, ehip))
+        e32, ehip = kit.rel(g32[m], ref), kit.rel(got, ref)
+        gate.judge(cid, f"grad{m + 1}", "tensor", "max", e32, ehip, row=(cid, "tensor", e32, ehip))
         print(f"[triple {cid}] grad{m + 1} |f64|max {ref.abs().max().item():.3e} e32 {e32:.2e} hip {ehip:.2e}")
-        if ehip > max(K * e32, FLOOR_TENSOR):
-            bad.append(("grad", m, e32, ehip))
         if L == 0:
             assert o64[m][1].item() == 0.0 and o64[m][2].item() == 0.0
         if L == B:
             assert o64[m][3].item() == 0.0 and o64[m][5].item() == 0.0
-    assert not bad, bad
+    gate.done(cid)
     if 0 < L < B:
         # the two pseudo terms of a student come from different peers
         assert all(outs[m][3].item() != outs[m][5].item() for m in range(3))

@@ -63,6 +63,7 @@ import zlib
 import torch
 import torch.nn.functional as F
 
+from oracle_kit import one_thread as _one_thread
 from conv_oracle import ceil2, measure          # noqa: F401  (re-exported: the same measures as the convolutions)
 
 F64, F32 = torch.float64, torch.float32
@@ -287,15 +288,6 @@ def evaluate(c, dtype, kernel_order=False):
     else:
         raise KeyError(op)
     return {k: v.detach().double() for k, v in r.items()}
-
-
-def _one_thread(fn, *args, **kw):
-    threads = torch.get_num_threads()
-    torch.set_num_threads(1)          # the summation order, and with it the last digits, would follow the thread count
-    try:
-        return fn(*args, **kw)
-    finally:
-        torch.set_num_threads(threads)
 
 
 def reference64(c):
