@@ -60,11 +60,16 @@ struct WinoArgs {
     int ks; long long y_ks;
 };
 
+constexpr int wino_pad49(int raw) { return raw + (49 - raw % 64 + 64) % 64; }
+constexpr int WINO_MAX_COUT = 384, WINO_LDS_LIMIT = 160 * 1024;
+// LDS of a ring of `nbuf` stages (4 channels of `cs` floats + `cob` filter blocks each) + statistics scratch, bias, DMA geometry
+constexpr int wino_lds_bytes(int nbuf, int cs, int cob, int nch) { return nbuf * (4 * cs + cob * 4096) * 4 + 512 + WINO_MAX_COUT * 4 + nch * 256; }
+
 // group = GZ x GY x GX tiles (16) per wave; workgroup = WZ x WY x WX groups x COB blocks of 16 output channels (4 waves)
 // FLAT = 1: the box is GZ x GY x GX tiles (<= 64, any shape) and the 4 waves take its tiles 16 at a time in (z, y, x) order
 // (lanes past the last tile idle): boxes that do not split into 4 x 16-tile groups, e.g. 3 x 3 x 6 tiles for a 12^3 volume
 // (54 of 64 lanes busy instead of the 27 of 64 that partly filled 8 x 8 x 8 boxes give)
-template <int GZ_, int GY_, int GX_, int WZ_, int WY_, int WX_, int COB_, int NBUF_, int DW_ = 0, int FLAT_ = 0>
+template <int GZ_, int GY_, int GX_, int WZ_, int WY_, int WX_, int COB_, int NBUF_, int NARROW_ = 0, int FLAT_ = 0>
 struct WinoCfg {
     static constexpr int GZ = GZ_, GY = GY_, GX = GX_, WZ = WZ_, WY = WY_, WX = WX_, COB = COB_, NBUF = NBUF_, FLAT = FLAT_;
     static constexpr int BZ = GZ * WZ, BY = GY * WY, BX = GX * WX;          // tiles per box
@@ -72,9 +77,13 @@ struct WinoCfg {
     static constexpr int HZ = OZ + 2, HY = OY + 2;
     // LDS rows hold x in [x0 - 4, x0 + OX + 4): whole 16-byte groups of the image row (W % 4 == 0), so a row arrives as
     // NQ buffer_load_dwordx4 ... lds lanes; the halo column x0 - 1 sits at float 3 of the row
-    // DW = 1 (narrow boxes, OX = 8: the padded rows would not fit 4 ring stages): rows hold exactly [x0 - 1, x0 + OX + 1)
-    // and arrive as single dwords (buffer_load_dword ... lds), 64 halo elements per instruction
-    static constexpr int DW = DW_;
+    // NARROW = 1 (boxes of OX <= 12, which also run partly filled): the padded rows are up to twice the box, so they are used
+    // only where the ring still fits LDS with them (6 x 6 x 12 boxes: 5 DMAs per channel instead of 14).  Where it does not
+    // (8 x 8 x 8 boxes: 171 KB), DW = 1: rows hold exactly [x0 - 1, x0 + OX + 1) and arrive as single dwords
+    // (buffer_load_dword ... lds), 64 halo elements per instruction
+    static constexpr int NARROW = NARROW_;
+    static constexpr int GROUPS16 = HZ * HY * ((OX + 8) / 4);
+    static constexpr int DW = NARROW && wino_lds_bytes(NBUF, wino_pad49(GROUPS16 * 4), COB, (GROUPS16 + 63) / 64) > WINO_LDS_LIMIT;
     static constexpr int NQ = DW ? OX + 2 : (OX + 8) / 4, RX = DW ? OX + 2 : NQ * 4, X0 = DW ? 0 : 3;
     static constexpr int GROUPS = HZ * HY * NQ;                              // DMA lanes (16-byte groups / dwords) per channel
     static constexpr int NCH = (GROUPS + 63) / 64;                           // DMA instructions per channel
@@ -82,19 +91,31 @@ struct WinoCfg {
     // channel stride (floats) == 49 (mod 64): the 4 channel lanes (0, 49, 34, 19 mod 64) x 16 tile lanes (stride 2) of a
     // ds_read_b32 then cover the 64 banks almost exactly once.  An odd stride is fine for the DMA: buffer_load_dwordx4 ...
     // lds only needs a 4-byte aligned LDS address (measured: same results; 8x8x8 boxes 133 -> 115 us, the others unchanged)
-    static constexpr int CS = CS_RAW + (49 - CS_RAW % 64 + 64) % 64;
+    static constexpr int CS = wino_pad49(CS_RAW);
     static constexpr int IN_FLOATS = 4 * CS;
     static constexpr int W_FLOATS = COB * 4096;
     static constexpr int STAGE = IN_FLOATS + W_FLOATS;
-    static constexpr int MAX_COUT = 384;
-    static constexpr int LDS_BYTES = NBUF * STAGE * 4 + 512 + MAX_COUT * 4 + NCH * 256;   // + statistics scratch, bias, DMA geometry
+    static constexpr int MAX_COUT = WINO_MAX_COUT;
+    static constexpr int LDS_BYTES = wino_lds_bytes(NBUF, CS, COB, NCH);
     static constexpr int WPW = COB * 4;                                     // 1 KiB filter pieces per wave
-    static constexpr int P = NCH + WPW;                                     // DMA instructions per wave and stage
-    static_assert(FLAT ? (GZ * GY * GX <= 64 && WZ * WY * WX == 1 && COB == 1 && DW == 1) : (GZ * GY * GX == 16), "16 tiles per wave");
+    static constexpr int P = NCH + WPW;                                     // DMA pieces of a stage per wave: input, then filter
+    static constexpr int RF = 0, PS = P;                                    // pieces a stage issues (see ResidentFilter)
+    static_assert(FLAT ? (GZ * GY * GX <= 64 && WZ * WY * WX == 1 && COB == 1 && NARROW == 1) : (GZ * GY * GX == 16), "16 tiles per wave");
     static_assert(FLAT || WZ * WY * WX * COB == 4, "4 waves");
     static_assert(NBUF == 3 || NBUF == 4, "ring depth");
     static_assert(2 * P <= 63 && P <= 21, "vmcnt range (two stages in flight), DMA slots");
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    static_assert(LDS_BYTES <= WINO_LDS_LIMIT, "LDS");
+};
+
+// Launches whose whole transformed filter is one ring of filter areas: Cin == 4 * NBUF and a single block of 16 * COB output
+// channels (the 16 -> 16 convolutions at 96^3 and the data gradients that mirror them).  Chunk s of every box lands in ring
+// slot s, so the NBUF filter areas hold the NBUF filter chunks at fixed addresses for the life of the persistent workgroup:
+// the prologue fetches them once (NBUF * WPW pieces per wave) and a stage issues its NCH input pieces only.  An LDS-DMA is
+// paid where it is issued, however late its data is needed: 4 of 10 instructions per stage go.  Same bytes at the same LDS
+// addresses as the streamed form: every result bit is unchanged.
+template <class C>
+struct ResidentFilter : C {
+    static constexpr int RF = 1, PS = C::NCH;
 };
 
 #ifndef MIS_WINO_DBG_CT
@@ -180,7 +201,7 @@ __device__ __forceinline__ void slots(const f32x4* __restrict__ wl, const f32x4*
             }
         }
         constexpr int SP = C::P <= 12 ? 5 : 3;      // DMA spacing in slots
-        if constexpr (K >= 2 && (K - 2) % SP == 0 && (K - 2) / SP < C::P && !(DBG & 8)) is.template piece<(K - 2) / SP>(wave);
+        if constexpr (K >= 2 && (K - 2) % SP == 0 && (K - 2) / SP < C::PS && !(DBG & 8)) is.template piece<(K - 2) / SP>(wave);
         if constexpr (K >= 16 && K < 40 && !(DBG & 16) && (DBG & 512)) in_unit<K - 16>(nxt);      // development: interleaved
         __builtin_amdgcn_sched_barrier(0);
         slots<C, FIRST, K + 1>(wl, wl_next, raw, cur, nxt, acc, ar, is, wave);
@@ -326,10 +347,15 @@ __device__ __forceinline__ void wino_fwd_body(const WinoArgs& a) {
     const unsigned nslot_u = (unsigned)nslot;
     Box bb = decode(box), nb = bb;       // the box being computed, the box under the DMA cursor
     cursor_box(bb, true);
+    if constexpr (C::RF) {                 // the whole filter, once: chunk c into ring slot c (nst == NBUF, one channel group)
 #pragma unroll
-    for (int s = 0; s < A; ++s) { cursor_set((unsigned)s, s); is.template pieces<0, C::P>(wave); }   // nst > A
+        for (int c = 0; c < C::NBUF; ++c) { cursor_set((unsigned)c, c); is.template pieces<C::NCH, C::P>(wave); }
+    }
+#pragma unroll
+    for (int s = 0; s < A; ++s) { cursor_set((unsigned)s, s); is.template pieces<0, C::PS>(wave); }   // nst > A
     static_assert(A == 3, "the waits below are written for a ring of 4");
-    vmwait<2 * C::P>::go();                // stage 0 has landed when only the later prologue stages are in flight
+    // the waits count pieces per stage (PS); vmcnt retires in order, so the resident filter, issued first, lands with stage 0
+    vmwait<2 * C::PS>::go();               // stage 0 has landed when only the later prologue stages are in flight
     __syncthreads();
     f32x2 ua[32], ub[32];
     f32x4 acc[64];
@@ -344,7 +370,7 @@ __device__ __forceinline__ void wino_fwd_body(const WinoArgs& a) {
     }
     ar[0] = wl_of(0)[0]; ar[1] = wl_of(0)[64];
     in_units<0, 24>(ua);                   // chunk 0 of the first box: not overlapped
-    vmwait<C::P>::go();                    // stage 1
+    vmwait<C::PS>::go();                   // stage 1
     __syncthreads();
 
     unsigned gs = 0;                       // global stage counter of the compute
@@ -373,8 +399,8 @@ __device__ __forceinline__ void wino_fwd_body(const WinoArgs& a) {
         // older than them -- the stage this wait is for -- has landed all the same)
         // (a uniform branch around the wait only: two copies of the MFMA run behind a branch make hipcc move the
         // accumulators through VGPRs -- 593 spills)
-        if (NB && relaxed) vmwait<C::P + 16>::go();
-        else vmwait<(DBG & 1024) ? 2 * C::P : C::P>::go();
+        if (NB && relaxed) vmwait<C::PS + 16>::go();
+        else vmwait<(DBG & 1024) ? 2 * C::PS : C::PS>::go();
         if (!(DBG & 64)) __syncthreads();  // ... and everyone's; everyone is done with stage gs-1
     };
 
@@ -499,7 +525,7 @@ __device__ __forceinline__ void wino_fwd_body(const WinoArgs& a) {
                                                               (int)((unsigned)(2 * h + rr) * s_bytes), 0);
                     }
                 }
-            if constexpr (C::DW) {      // this variant also runs partly filled boxes: tiles outside the volume do not count
+            if constexpr (C::NARROW) {  // these variants also run partly filled boxes / idle lanes: tiles outside the volume do not count
                 if (!ok) { s1 = f32x2{0.f, 0.f}; s2 = s1; }
             }
             run1[2 * h] += s1[0]; run1[2 * h + 1] += s1[1]; run2[2 * h] += s2[0]; run2[2 * h + 1] += s2[1];
@@ -578,8 +604,17 @@ int launch_wino(WinoArgs a, hipStream_t stream) {
     return mis_launch_status();
 }
 
+using WinoV0 = WinoCfg<1, 1, 16, 2, 2, 1, 1, 4>;
+using WinoV1 = WinoCfg<1, 2, 8, 2, 2, 1, 1, 4>;
 using WinoV2 = WinoCfg<1, 4, 4, 4, 1, 1, 1, 4, 1>;
 using WinoV3 = WinoCfg<3, 3, 6, 1, 1, 1, 1, 4, 1, 1>;
+static_assert(!WinoV0::DW && !WinoV1::DW && WinoV2::DW && !WinoV3::DW, "halo rows: single dwords at 8 x 8 x 8 only");
+
+// ResidentFilter serves this launch: the filter is exactly the ring's NBUF filter areas (see ResidentFilter).  Variant 0 only:
+// no launch of unet_3D / V-Net / UNETR at the 48^3 level (variant 1) has 16 input and 16 output channels.
+bool wino_filter_resident(int Cin, int Cout, int variant) {
+    return variant == 0 && (Cin + 3) / 4 == WinoV0::NBUF && Cout == 16 * WinoV0::COB;
+}
 
 // Contraction slices for a launch with too few (box, channel group) entries for the chip (the 6^3 level: 8 ... 128 entries of
 // 32 ... 64 chunks each; half batches at 12^3): the smallest count that brings the entries to >= 192, slices of an even
@@ -666,16 +701,24 @@ long long boxes_per_image(int D, int H, int W) {
 // mis_conv_fwd_stat_tiles does for the direct kernel
 extern "C" long long mis_conv3d_wino_stat_tiles(int D, int H, int W, int variant) {
     if (D <= 0 || H <= 0 || W <= 0) return MIS_ERR_ARG;
-    if (variant == 0) return boxes_per_image<WinoCfg<1, 1, 16, 2, 2, 1, 1, 4>>(D, H, W);
-    if (variant == 1) return boxes_per_image<WinoCfg<1, 2, 8, 2, 2, 1, 1, 4>>(D, H, W);
-    if (variant == 2) return boxes_per_image<WinoCfg<1, 4, 4, 4, 1, 1, 1, 4, 1>>(D, H, W);
-    if (variant == 3) return boxes_per_image<WinoCfg<3, 3, 6, 1, 1, 1, 1, 4, 1, 1>>(D, H, W);
+    if (variant == 0) return boxes_per_image<WinoV0>(D, H, W);
+    if (variant == 1) return boxes_per_image<WinoV1>(D, H, W);
+    if (variant == 2) return boxes_per_image<WinoV2>(D, H, W);
+    if (variant == 3) return boxes_per_image<WinoV3>(D, H, W);
     return MIS_ERR_UNSUPPORTED;
 }
 
-// kernel name as rocprofv3 prints it (minus the anonymous-namespace prefix), for bench.py's attribution
+// kernel name as rocprofv3 prints it (minus the anonymous-namespace prefix), for bench.py's attribution.  `variant` alone: the
+// instantiation that streams its filter (what every launch of the variant ran before ResidentFilter); MIS_WINO_LAUNCH(variant,
+// Cin, Cout): the instantiation a launch with these channel counts runs
 extern "C" int mis_conv3d_wino_kernel_name(int variant, char* name, int name_len) {
-    if (!name || name_len <= 0) return MIS_ERR_ARG;
+    if (!name || name_len <= 0 || variant < 0) return MIS_ERR_ARG;
+    const int Cin = (variant >> 4) & 0xfff, Cout = variant >> 16;
+    variant &= 15;
+    if (wino_filter_resident(Cin, Cout, variant)) {
+        snprintf(name, name_len, "wino_fwd_kernel<ResidentFilter<WinoCfg<1, 1, 16, 2, 2, 1, 1, 4, 0, 0> >, false>");
+        return MIS_OK;
+    }
     if (variant == 0) snprintf(name, name_len, "wino_fwd_kernel<WinoCfg<1, 1, 16, 2, 2, 1, 1, 4, 0, 0>, false>");
     else if (variant == 1) snprintf(name, name_len, "wino_fwd_kernel<WinoCfg<1, 2, 8, 2, 2, 1, 1, 4, 0, 0>, false>");
     else if (variant == 2) snprintf(name, name_len, "wino_fwd_kernel<WinoCfg<1, 4, 4, 4, 1, 1, 1, 4, 1, 0>, false>");
@@ -700,12 +743,13 @@ extern "C" int mis_conv3d_wino_fwd(const float* x, long long x_bs, const float* 
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
     a.nci4 = (Cin + 3) / 4;
     a.stat = reinterpret_cast<float2*>(stat); a.stat_sc = stat_sc; a.stat_sn = stat_sn;
-    if (variant == 0) return launch_wino<WinoCfg<1, 1, 16, 2, 2, 1, 1, 4>>(a, stream);
-    if (variant == 1) return launch_wino<WinoCfg<1, 2, 8, 2, 2, 1, 1, 4>>(a, stream);
-    if (variant == 2) return launch_wino<WinoCfg<1, 4, 4, 4, 1, 1, 1, 4, 1>>(a, stream);
+    if (variant == 0 && wino_filter_resident(Cin, Cout, 0)) return launch_wino<ResidentFilter<WinoV0>>(a, stream);
+    if (variant == 0) return launch_wino<WinoV0>(a, stream);
+    if (variant == 1) return launch_wino<WinoV1>(a, stream);
+    if (variant == 2) return launch_wino<WinoV2>(a, stream);
     if (variant == 3) {
         if (W != 12 || D % 6 || H % 6) return MIS_ERR_UNSUPPORTED;
-        return launch_wino<WinoCfg<3, 3, 6, 1, 1, 1, 1, 4, 1, 1>>(a, stream);
+        return launch_wino<WinoV3>(a, stream);
     }
     return MIS_ERR_UNSUPPORTED;
 }
@@ -781,6 +825,7 @@ extern "C" int mis_conv3d_wino_dgrad_norm(const float* dy, long long dy_bs, cons
     a.nci4 = (Cin + 3) / 4;
     a.stat = reinterpret_cast<float2*>(part); a.stat_sc = part_sc; a.stat_sn = part_sn;
     a.xn = xn; a.xn_bs = xn_bs; a.thr = mean; a.slope = slope;
-    if (variant == 0) return launch_wino<WinoCfg<1, 1, 16, 2, 2, 1, 1, 4>, true>(a, stream);
-    return launch_wino<WinoCfg<1, 2, 8, 2, 2, 1, 1, 4>, true>(a, stream);
+    if (variant == 0 && wino_filter_resident(Cin, Cout, 0)) return launch_wino<ResidentFilter<WinoV0>, true>(a, stream);
+    if (variant == 0) return launch_wino<WinoV0, true>(a, stream);
+    return launch_wino<WinoV1, true>(a, stream);
 }

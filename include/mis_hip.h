@@ -113,6 +113,11 @@ int mis_conv_fwd_kernel_name(int N, int Cin, int Cout, int D, int H, int W, int 
  * mis_conv3d_wino_stat_tiles: partial-statistics entries per image (boxes) of that variant. */
 int mis_conv3d_wino_select(int N, int Cin, int Cout, int D, int H, int W);
 long long mis_conv3d_wino_stat_tiles(int D, int H, int W, int variant);
+/* mis_conv3d_wino_kernel_name(variant): the instantiation that streams its filter chunk with every stage;
+ * mis_conv3d_wino_kernel_name(MIS_WINO_LAUNCH(variant, Cin, Cout)): the one a launch with these channel counts runs -- a
+ * 16 -> 16 launch of variant 0 keeps its whole transformed filter in LDS (fetched once per workgroup, not once per box:
+ * "ResidentFilter<...>" in the name).  For mis_conv3d_wino_dgrad_norm read ", true>" for the closing ", false>". */
+#define MIS_WINO_LAUNCH(variant, Cin, Cout) ((variant) | (Cin) << 4 | (Cout) << 16)
 int mis_conv3d_wino_kernel_name(int variant, char* name, int name_len);
 int mis_conv3d_wino_fwd(const float* x, long long x_bs, const float* wt, const float* bias, float* y, long long y_bs,
                         int N, int Cin, int Cout, int D, int H, int W, float* stat, long long stat_sc,
